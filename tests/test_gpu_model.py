@@ -429,7 +429,7 @@ def test_bench_runs_under_torchrun_with_rccl(tmp_path):
     env = dict(os.environ, RPO_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -469,7 +469,7 @@ def test_bench_two_rank_flow_on_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(RPO_DIST_BACKEND="gloo", RPO_ALL_RANKS_ON_GPU0="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "4", "--no-cpu-baseline"]
+           "--batch", "4", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -498,7 +498,7 @@ def test_bench_eight_rank_flow_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(RPO_DIST_BACKEND="gloo", RPO_ALL_RANKS_ON_GPU0="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--batch", "4", "--no-cpu-baseline"]
+           "--batch", "4", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -518,6 +518,40 @@ def test_bench_eight_rank_flow_on_one_gpu():
     assert len(rk["all"]) == 8 and rk["min"] <= rk["max"] and abs(rk["max"] - d["ms_per_step"]) < 1e-3
     assert "pinned" in d["config"]["host"]
     assert not glob.glob(os.path.join(tempfile.gettempdir(), "rpo_amd_weights_*")), "shared weight directory left behind"
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` line (no --full) holds the headline and nothing measured beside it, and --dump-outputs writes
+    what the last timed step computed: float32 arrays of the step's shapes, the line's own final loss, and the same
+    values from a second run with the same arguments (the inputs are seeded)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "RPO_FORCE_DIST")}
+    runs = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+               "--batch", "4", "--dump-outputs", str(tmp_path / name)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    for k in ("cpu_baseline", "precision", "sibling_modes", "tolerance_met"):
+        assert k not in d
+    assert "kernels" not in d["roofline"] and "empirical" not in d["roofline"] and d["config"]["host_us_per_step"] is None
+    K, dt, dv, n_cls = 24, 512, 768, 19
+    shapes = {"loss": (1,), "logits": (4, n_cls), "g_text": (K, dt), "g_img": (K, dv), "text_prompt": (K, dt),
+              "img_prompt": (K, dv)}
+    got = [{n: np.load(tmp_path / name / f"{n}.npy") for n in shapes} for name in ("a", "b")]
+    for n, shp in shapes.items():
+        assert got[0][n].dtype == np.float32 and got[0][n].shape == shp and np.isfinite(got[0][n]).all(), n
+        np.testing.assert_array_equal(got[0][n], got[1][n], err_msg=n)
+    assert abs(float(got[0]["loss"][0]) - d["config"]["final_loss"]) <= 1e-5
+    assert np.abs(got[0]["g_text"]).max() > 0 and np.abs(got[0]["g_img"]).max() > 0
 
 
 _EDGE_ORACLE = {}

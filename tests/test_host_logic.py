@@ -541,3 +541,22 @@ def test_default_import_path_touches_no_experimental_code():
     for name in exp_switches:
         assert f'"{name}"' not in code_only, f"engine.py reads the experiment switch {name}"
     assert "xenv" not in code_only and len(src.splitlines()) <= 1000
+
+
+def test_bench_dump_outputs_float32_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array lands as float32 DIR/<name>.npy; one above its share of the size limit is cut
+    to a fixed, seeded sample of its rows -- the same rows on every run."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8192)
+    big = np.arange(1000 * 8, dtype=np.float64).reshape(1000, 8)
+    small = np.linspace(-1, 1, 6, dtype=np.float32).astype(np.float16).reshape(3, 2)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a_big, b_big = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    a_small = np.load(tmp_path / "a" / "small.npy")
+    assert a_big.dtype == np.float32 and a_small.dtype == np.float32
+    assert a_big.nbytes <= 8192 // 2 and a_big.shape[1] == 8 and a_big.shape[0] > 1
+    np.testing.assert_array_equal(a_big, b_big)
+    rows = (a_big[:, 0] / 8).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a_big, big[rows].astype(np.float32))
+    np.testing.assert_array_equal(a_small, small.astype(np.float32))

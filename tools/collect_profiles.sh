@@ -23,32 +23,32 @@ keep() {
 }
 # the -DRPO_TIMELINE library once, compiler output in its own log (the timeline tools load it)
 bash tools/build_debug.sh > $O/build_debug.log 2>&1 || { echo "FAILED: build_debug.sh" >&2; FAILED="$FAILED build_debug"; }
-timeout 300 python bench.py > $O/bench.json 2> $O/bench.err
-timeout -k 5 240 rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-precision > $O/bench_traced.json 2> $O/trace.err
+timeout 300 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout -k 5 240 rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-precision > $O/bench_traced.json 2> $O/trace.err
 for shape in qkv out_proj c_fc c_proj; do
 for c in "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "FETCH_SIZE" "WRITE_SIZE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   n=$(echo $c | cut -d" " -f1)
   timeout -k 5 100 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${shape}_$n -o p -- python tools/bench_gemm.py --only $shape > $O/pmc_${shape}_$n.log 2>&1
 done
 done
-timeout -k 5 200 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $O/pmc_step_MFMA -o p -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-precision > $O/pmc_step_MFMA.log 2>&1
+timeout -k 5 200 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $O/pmc_step_MFMA -o p -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-precision > $O/pmc_step_MFMA.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 5 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_step_$c -o p -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-precision > $O/pmc_step_$c.log 2>&1
+  timeout -k 5 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_step_$c -o p -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-precision > $O/pmc_step_$c.log 2>&1
 done
 # the other BASELINE.json configs and the widened rows through the same bench.py
 B="--no-cpu-baseline --no-precision"
-timeout 200 python bench.py --model ViT-L/14 --batch 16 --steps 30 --warmup 5 $B > $O/bench_vitl14.json 2>> $O/bench.err
+timeout 200 python bench.py --full --model ViT-L/14 --batch 16 --steps 30 --warmup 5 $B > $O/bench_vitl14.json 2>> $O/bench.err
 : > $O/bench_ksweep.json
-for k in 4 8 16 24 48; do timeout 200 python bench.py --K $k --steps 30 --warmup 5 $B >> $O/bench_ksweep.json 2>> $O/bench.err; done
+for k in 4 8 16 24 48; do timeout 200 python bench.py --full --K $k --steps 30 --warmup 5 $B >> $O/bench_ksweep.json 2>> $O/bench.err; done
 : > $O/bench_batchsweep.json
-for b in 4 8 16 64 128; do timeout 200 python bench.py --batch $b --steps 40 --warmup 5 $B >> $O/bench_batchsweep.json 2>> $O/bench.err; done
-timeout 200 python bench.py --dtype f32 --steps 20 --warmup 5 $B > $O/bench_f32.json 2>> $O/bench.err
-timeout 200 python bench.py --dtype f16 --steps 40 --warmup 5 --no-cpu-baseline > $O/bench_f16.json 2>> $O/bench.err
-timeout 200 python bench.py --steps 20 --warmup 5 --eval-batch 100 $B > $O/bench_eval.json 2>> $O/bench.err
-[ -z "${QUICK:-}" ] && timeout 200 python bench.py --steps 20 --warmup 5 --input-pipeline $B > $O/bench_input_pipeline.json 2>> $O/bench.err
+for b in 4 8 16 64 128; do timeout 200 python bench.py --full --batch $b --steps 40 --warmup 5 $B >> $O/bench_batchsweep.json 2>> $O/bench.err; done
+timeout 200 python bench.py --full --dtype f32 --steps 20 --warmup 5 $B > $O/bench_f32.json 2>> $O/bench.err
+timeout 200 python bench.py --full --dtype f16 --steps 40 --warmup 5 --no-cpu-baseline > $O/bench_f16.json 2>> $O/bench.err
+timeout 200 python bench.py --full --steps 20 --warmup 5 --eval-batch 100 $B > $O/bench_eval.json 2>> $O/bench.err
+[ -z "${QUICK:-}" ] && timeout 200 python bench.py --full --steps 20 --warmup 5 --input-pipeline $B > $O/bench_input_pipeline.json 2>> $O/bench.err
 # the sibling trainers at the reference's own defaults (CoOp: batch 32, n_ctx 16; CoCoOp: batch 1, n_ctx 4), graph-captured steps
-timeout 300 python bench.py --trainer coop --steps 30 --warmup 5 --no-precision > $O/bench_coop.json 2>> $O/bench.err
-timeout 300 python bench.py --trainer cocoop --steps 30 --warmup 5 --no-precision > $O/bench_cocoop.json 2>> $O/bench.err
+timeout 300 python bench.py --full --trainer coop --steps 30 --warmup 5 --no-precision > $O/bench_coop.json 2>> $O/bench.err
+timeout 300 python bench.py --full --trainer cocoop --steps 30 --warmup 5 --no-precision > $O/bench_cocoop.json 2>> $O/bench.err
 keep attn_timeline.txt 200 python tools/attn_timeline.py 8 16 32
 keep attn_bwd_timeline.txt 200 python tools/attn_bwd_timeline.py
 keep gemm_timeline.txt 200 python tools/gemm_timeline.py
@@ -64,9 +64,9 @@ keep bench_text_attn.txt 100 python tools/bench_text_attn.py
 [ -z "${QUICK:-}" ] && keep half_batch_probe.txt 200 python tools/probe_half_batch.py 32 1 2 4
 # ---- round 6 ----------------------------------------------------------------------------------------------------------
 # the reference's ImageNet-size class set (configs/trainers/RPO/imagenet_k24_ep15.yaml): bench line + kernel trace
-timeout 600 python bench.py --n-cls 1000 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_ncls1000.json 2>> $O/bench.err
-timeout 300 python bench.py --n-cls 100 --steps 30 --warmup 5 --no-cpu-baseline --no-precision --no-f16-sibling > $O/bench_ncls100.json 2>> $O/bench.err
-timeout -k 5 400 rocprofv3 --kernel-trace --stats -d $O/trace1000 -o t -- python bench.py --n-cls 1000 --steps 6 --warmup 2 --no-cpu-baseline --no-precision --no-f16-sibling > $O/bench_traced1000.json 2> $O/trace1000.err
+timeout 600 python bench.py --full --n-cls 1000 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_ncls1000.json 2>> $O/bench.err
+timeout 300 python bench.py --full --n-cls 100 --steps 30 --warmup 5 --no-cpu-baseline --no-precision --no-f16-sibling > $O/bench_ncls100.json 2>> $O/bench.err
+timeout -k 5 400 rocprofv3 --kernel-trace --stats -d $O/trace1000 -o t -- python bench.py --full --n-cls 1000 --steps 6 --warmup 2 --no-cpu-baseline --no-precision --no-f16-sibling > $O/bench_traced1000.json 2> $O/trace1000.err
 keep trace_ncls1000.txt 60 python tools/prof_stats.py $(find $O/trace1000 -name "*_results.db" | head -1) 30
 rm -rf $O/trace1000
 # N > 1 readiness on one GPU: a one-rank RCCL communicator, three collective schedules, bit-identical (bench.py --dry-scale)

@@ -14,7 +14,7 @@ if db:
     tl = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "prof_timeline.py"), db[0]],
                         capture_output=True, text=True).stdout
     with open(os.path.join(out, f"{tag}_kernel_trace_stats.txt"), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline\n"
+        f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline\n"
                 "# NB: kernel tracing serialises the two HIP queues; per-kernel durations are valid, overlap is not.\n")
         f.write(txt + "\n# last step:\n" + tl)
 SH = {"qkv": "in-proj 7072x2304x768 bias (gemm_w4_kernel: 256x256 tiles, one wave per SIMD, asm k-loop), 25.0 GFLOP, algorithmic bytes 10.9+3.5+32.6 MB",
@@ -114,7 +114,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
 if step:
     with open(os.path.join(out, f"{tag}_step_hbm_traffic.txt"), "w") as fo:
         fo.write("# HBM traffic of ONE train step (all kernels between two sgd launches), rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE\n"
-                 "# over `python bench.py --steps 6 --warmup 2` (separate passes).  Units: KB.  FETCH_SIZE under-reports wide\n"
+                 "# over `python bench.py --full --steps 6 --warmup 2` (separate passes).  Units: KB.  FETCH_SIZE under-reports wide\n"
                  "# coalesced reads by 2x on gfx950 (MI355X_MICROARCH.md), so traffic = 2*FETCH + WRITE.\n")
         for k, v in step.items():
             fo.write(f"{k} {v:.6g}\n")
@@ -154,7 +154,7 @@ if f:
                 ms = json.loads(open(os.path.join(raw, "bench.json")).read())["ms_per_step"]
             except Exception:
                 pass
-            fo.write("# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES -- python bench.py --steps 6 --warmup 2\n"
+            fo.write("# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES -- python bench.py --full --steps 6 --warmup 2\n"
                      "# SQ_VALU_MFMA_BUSY_CYCLES summed over the kernels of ONE train step (SIMD-cycles, 1024 SIMDs).  Per-dispatch\n"
                      "# GRBM_GUI_ACTIVE is inflated by the profiler for small kernels, so the step-level utilisation is taken against the\n"
                      "# UN-profiled step time of the same refresh's bench.json instead.\n")
