@@ -329,6 +329,23 @@ int rpo_head_fwd_bwd_act(const float* img_f, const float* text_f, const int64_t*
                          float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_f_act,
                          void* d_text_f_act, int act_dtype, int B, int C, int K, int e, float* workspace, void* stream);
 
+/* Linear-probe head, cross-entropy and the gradient of the probe layer (trainers/linear_prob.py:61-95, :151-184):
+ *   z      = img_f . w^T + bias                 (lp_layer = nn.Linear(e, e) on the UN-normalised image feature, :89-90)
+ *   logits = scale_exp * z . text_f_n^T          (text_f_n: the normalised text features of preprocess, :77-83)
+ *   loss   = mean_b CE(logits[b], label[b])
+ *   g_w    = dz^T . img_f,  g_bias = sum_b dz,   dz = scale_exp ((softmax - onehot) / B) . text_f_n
+ * img_f [B,e], w [e,e] (out x in), bias [e], text_f_n [C,e], z [B,e], logits [B,C], loss [1], g_w [e,e], g_bias [e]; all
+ * fp32, row-major; img_f, w, z, text_f_n 16-byte aligned.  label: int64 device array [B], or NULL for eval (only z and
+ * logits are written; loss, g_w and g_bias are not touched).  A target outside [0, C) makes the loss NaN (and that
+ * image's share of the gradients) and reads nothing out of bounds.  g_bias may be g_w + e*e (one flat [W | b] gradient).
+ * workspace: fp32, at least rpo_lp_head_workspace_floats(B, C, e) elements; no initialisation needed.
+ * e a multiple of 32 up to 1024, 1 <= B <= 128, 1 <= C <= 32768, else RPO_E_SHAPE.  Four launches for training, two for
+ * eval, all GEMM-shaped parts on the fp32 matrix pipe, fixed summation orders (the same bits on every call). */
+int64_t rpo_lp_head_workspace_floats(int B, int C, int e);
+int rpo_lp_head_fwd_bwd(const float* img_f, const float* w, const float* bias, const float* text_f_n,
+                        const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
+                        float* g_w, float* g_bias, int B, int C, int e, float* workspace, void* stream);
+
 /* torch.optim.SGD (dampening 0, no nesterov) on n fp32 scalars (trainers/rpo.py:274,309):
  *   g' = grad_scale * g + wd * p;  buf = first ? g' : momentum * buf + g';  p -= lr * buf
  * grad_scale = 1 / world_size after a sum all-reduce. */

@@ -451,6 +451,27 @@ def head_fwd_bwd(img_f, text_f, label, scale_exp: float, logits, loss, d_img_f, 
     return logits
 
 
+def lp_head_workspace_floats(B: int, Cc: int, e: int) -> int:
+    return int(_lib.load().rpo_lp_head_workspace_floats(B, Cc, e))
+
+
+def lp_head_fwd_bwd(img_f, w, bias, text_f_n, label, scale_exp: float, z, logits, loss, g_w, g_bias, ws):
+    """The linear-probe head (include/rpo_amd.h rpo_lp_head_fwd_bwd): label None = eval (z and logits only)."""
+    B, e = img_f.shape
+    Cc = text_f_n.shape[0]
+    assert w.shape == (e, e) and bias.shape == (e,) and text_f_n.shape == (Cc, e)
+    assert z.shape == (B, e) and logits.shape == (B, Cc)
+    ts = [img_f, w, bias, text_f_n, z, logits] + ([] if label is None else [loss, g_w, g_bias])
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in ts + [ws])
+    assert label is None or (label.dtype == torch.int64 and label.numel() == B)
+    assert label is None or (g_w.shape == (e, e) and g_bias.shape == (e,))
+    assert ws.numel() >= lp_head_workspace_floats(B, Cc, e)
+    check(_lib.load().rpo_lp_head_fwd_bwd(img_f.data_ptr(), w.data_ptr(), bias.data_ptr(), text_f_n.data_ptr(), _p(label),
+                                          scale_exp, z.data_ptr(), logits.data_ptr(), _p(loss), _p(g_w), _p(g_bias),
+                                          B, Cc, e, ws.data_ptr(), _stream()), "rpo_lp_head_fwd_bwd")
+    return logits
+
+
 def metanet_fwd(img_f, w1, b1, w2, b2, f_norm, hidden, bias):
     B, e = img_f.shape
     h, d = w1.shape[0], w2.shape[0]

@@ -660,8 +660,10 @@ def checkpoint_dict(prompt_state, epoch: int, momentum: Optional[torch.Tensor], 
             "scheduler": {"last_epoch": int(epoch)}, "val_result": val_result, "steps": int(steps)}
 
 
-def write_checkpoint(directory: str, ck: dict, epoch: int, is_best: bool = False) -> str:
-    path = os.path.join(directory, "prompt_learner")
+def write_checkpoint(directory: str, ck: dict, epoch: int, is_best: bool = False, name: str = "prompt_learner") -> str:
+    """`<directory>/<name>/model.pth.tar-<epoch>` (+ Dassl's `checkpoint` pointer file and `model-best.pth.tar`); `name` is
+    the registered model's name (`prompt_learner`, or `lp_layer` for the linear probe)."""
+    path = os.path.join(directory, name)
     os.makedirs(path, exist_ok=True)
     fn = os.path.join(path, f"model.pth.tar-{epoch}")
     torch.save(ck, fn)
