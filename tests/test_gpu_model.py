@@ -1347,6 +1347,220 @@ def test_cocoop_trainer_sgd_steps_match_oracle():
                                                          "token_prefix", "token_suffix"}
 
 
+# ---- CoOp / CoCoOp beyond the depth-2, 19-class goldens: against the CPU oracle (depth 1) --------------------------------
+# The goldens' prompts are 8-22 tokens long and have 19 classes.  These cases reach what they do not: hundreds of classes
+# (the wide rpo_reduce_groups from 64 classes on, the head on the fp32 matrix pipe above 128, text GEMMs of >= 8192 rows),
+# prompts of up to 76 tokens (keys 64-79 of rpo_text_attn_bwd_dense) and the ViT-L/14 widths (d_t 768, 12 heads,
+# meta-net h = 48).
+SIB_LONG = [60, 49, 20, 9, 55]                     # base lengths: + n_ctx 16 -> 76, 65, 36, 25, 71 tokens
+SIB_MANY = {n: [4 + (7 * c) % 22 for c in range(n)] for n in (7, 100, 397, 1000)}
+_SIB_ORACLE = {}
+
+
+def _sibling_case(kind, model, base_lens, n_ctx, B, position="end", csc=False):
+    """(cfg, sd, tokens, ctx, meta, image, label, oracle logits, oracle loss, oracle gradients) of one sibling case; the
+    oracle (oracle.rpo_oracle.coop_loss_and_grad / cocoop_loss_and_grads, pinned to the reference by
+    tests/test_oracle_golden.py) runs once per case whatever the storage modes compared with it."""
+    from oracle.rpo_oracle import cocoop_loss_and_grads, coop_loss_and_grad, plain_clip_forward
+    from rpo_amd.config import vit_b16, vit_l14
+    key = (kind, model, tuple(base_lens), n_ctx, B, position, csc)
+    if key not in _SIB_ORACLE:
+        cfg = (vit_b16 if model == "ViT-B/16" else vit_l14)(layers_v=1, layers_t=1, K=1, n_cls=len(base_lens))
+        toks = synth.coop_tokens(synth.synthetic_tokens(cfg, base_lens, seed=17), n_ctx)
+        sd = synth.clip_state_dict(cfg, seed=23, token_rows=np.unique(toks).tolist() + [49407])
+        rng = np.random.default_rng(29)
+        ctx = (0.02 * rng.standard_normal((cfg.n_cls, n_ctx, cfg.d_t) if csc else (n_ctx, cfg.d_t))).astype(np.float32)
+        image, label = synth.images(cfg, B, seed=31), synth.labels(cfg, B, seed=37)
+        # the first image belongs to the LAST class: its text gradient (softmax - 1, not ~1 / n_cls) sits in the last
+        # group the class reduction sums, where a reduction that drops or double-counts a group goes wrong
+        label[0] = cfg.n_cls - 1
+        meta = None
+        if kind == "coop":
+            logits, loss, g = coop_loss_and_grad(sd, image, toks, ctx, label, cfg.patch, class_token_position=position)
+            grads = {"ctx": g.numpy()}
+        else:
+            e, h = cfg.embed, cfg.embed // 16            # nn.Linear's default init ranges (trainers/cocoop.py:93-97)
+            u = lambda shape, fan: rng.uniform(-fan ** -0.5, fan ** -0.5, shape).astype(np.float32)
+            meta = dict(w1=u((h, e), e), b1=u((h,), e), w2=u((cfg.d_t, h), h), b2=u((cfg.d_t,), h))
+            # the 16-bit image towers move the meta-net's pre-activations by a fraction of a percent of their spread: none
+            # may sit so close to 0 that the ReLU could flip between the oracle and the device (a flipped unit is a whole
+            # gradient row).  b1 is shifted by whole margins, unit by unit, until every image clears the kink.
+            _, imf, _ = plain_clip_forward(sd, image, toks, cfg.patch)
+            a = (imf / imf.norm(dim=-1, keepdim=True)).double().numpy() @ meta["w1"].T.astype(np.float64)
+            margin = 0.03 * float(np.abs(a).max())
+            for j in range(h):
+                shift = next(k * margin for k in sorted(range(-B - 1, B + 2), key=abs)
+                             if np.abs(a[:, j] + meta["b1"][j] + k * margin).min() >= margin)
+                meta["b1"][j] += np.float32(shift)
+            pre = a + meta["b1"].astype(np.float64)
+            assert np.abs(pre).min() >= 0.99 * margin and (pre < 0).any() and (pre > 0).any()
+            logits, loss, g = cocoop_loss_and_grads(sd, image, toks, ctx, meta, label, cfg.patch)
+            grads = {k: v.numpy() for k, v in g.items()}
+        _SIB_ORACLE[key] = (cfg, sd, toks, ctx, meta, image, label, logits.numpy(), float(loss), grads)
+    return _SIB_ORACLE[key]
+
+
+def _sibling_bounds(act, o_logits, Lmax):
+    """(loss bound, logit bound, gradient bound) of a storage mode.  The logit bound scales with the logits' magnitude,
+    as in test_many_classes_k24_against_oracle (the modes' bounds were set on |logits| <= 8.7), and doubles for prompts
+    longer than 64 tokens, as in test_edge_shapes_against_oracle_16bit's 71-token case: the 16-bit storage of 76 rows of
+    activations moves a logit by up to 1.28e-2 in f16 (CoOp, class token in the middle) while the f32 mode of the same
+    case stays at 1.4e-5."""
+    if act == torch.float32:
+        return TOL_F32, TOL_F32, TOL_F32
+    la, gr = (F16_LOGIT_ATOL, F16_GRAD_REL) if act == torch.float16 else (BF16_LOGIT_ATOL, BF16_GRAD_REL)
+    return la, la * max(1.0, float(np.abs(o_logits).max()) / 8.7) * (2 if Lmax > 64 else 1), gr
+
+
+def _check_coop(act, case, **kw):
+    from rpo_amd.coop import CoOpCustomCLIP
+    cfg, sd, toks, ctx, _, image, label, o_logits, o_loss, o_g = case
+    m = CoOpCustomCLIP(sd, toks, ctx.shape[-2], "cuda:0", act, max_batch=image.shape[0], ctx=ctx, cfg=cfg, **kw)
+    eng = m.engine
+    im, lb = torch.from_numpy(image).cuda(), torch.from_numpy(label).cuda()
+    logits = eng.coop_forward_backward(im, lb).cpu().numpy()
+    loss, g = eng.loss.item(), eng.coop_grad.cpu().numpy()
+    assert g.shape == o_g["ctx"].shape
+    le, ll, gr = float(np.abs(logits - o_logits).max()), abs(loss - o_loss), _relmax(g, o_g["ctx"])
+    lb_loss, lb_logits, gb = _sibling_bounds(act, o_logits, eng.Lmax)
+    print(f"[coop {cfg.name} n_cls={cfg.n_cls} Lmax={eng.Lmax} {kw} {act}] logits err {le:.3e} (max |logit| "
+          f"{np.abs(o_logits).max():.2f}) loss err {ll:.3e} ctx_grad rel {gr:.3e}")
+    assert ll <= lb_loss and le <= lb_logits and gr <= gb
+    eng.coop_forward_backward(im, lb)                 # the same batch again: the same bits
+    assert np.array_equal(eng.coop_grad.cpu().numpy(), g)
+
+
+def _check_cocoop(act, case):
+    from rpo_amd.coop import CoCoOpCustomCLIP
+    cfg, sd, toks, ctx, meta, image, label, o_logits, o_loss, o_g = case
+    B = image.shape[0]
+    m = CoCoOpCustomCLIP(sd, toks, ctx.shape[0], "cuda:0", act, max_batch=B, ctx=ctx, meta=meta, cfg=cfg)
+    eng = m.engine
+    im, lb = torch.from_numpy(image).cuda(), torch.from_numpy(label).cuda()
+    m.prompt_learner.train()
+    loss = m(im, lb).item()
+    logits = eng.logits[:B].cpu().numpy()
+    got = dict(ctx=eng.coop_grad, w1=eng.meta_grad[0], b1=eng.meta_grad[1], w2=eng.meta_grad[2], b2=eng.meta_grad[3])
+    rel = {k: _relmax(v.cpu().numpy(), o_g[k]) for k, v in got.items()}
+    le, ll = float(np.abs(logits - o_logits).max()), abs(loss - o_loss)
+    lb_loss, lb_logits, gb = _sibling_bounds(act, o_logits, eng.Lmax)
+    print(f"[cocoop {cfg.name} n_cls={cfg.n_cls} B={B} Lmax={eng.Lmax} {act}] logits err {le:.3e} (max |logit| "
+          f"{np.abs(o_logits).max():.2f}) loss err {ll:.3e} grads rel " + " ".join(f"{k} {v:.2e}" for k, v in rel.items()))
+    assert ll <= lb_loss and le <= lb_logits
+    assert all(v <= gb for v in rel.values()), rel
+
+
+ACTS = [torch.float32, torch.float16, torch.bfloat16]
+ACT_IDS = ["float32", "float16", "bfloat16"]
+
+
+@pytest.mark.parametrize("n_cls", [397, 1000])
+@pytest.mark.parametrize("act", ACTS, ids=ACT_IDS)
+def test_coop_many_classes_against_oracle(n_cls, act):
+    """CoOp at SUN397's and ImageNet's class counts (n_ctx 4, B 2, prompts of 8-29 tokens): loss, logits and d loss /
+    d ctx against the oracle -- the context gradient is summed over the classes by the wide rpo_reduce_groups, the head
+    runs on the fp32 matrix pipe, the text tower's GEMMs see 11 513 / 29 000 rows.  Measured worst (logits / ctx grad rel):
+    f32 2.7e-5 / 3.3e-6; f16 1.4e-2 / 2.4e-3 and bf16 0.107 / 1.8e-2 at |logits| <= 15.7 (bounds 1.8e-2 and 0.22)."""
+    _check_coop(act, _sibling_case("coop", "ViT-B/16", SIB_MANY[n_cls], 4, 2))
+
+
+@pytest.mark.parametrize("position,csc", [("end", False), ("middle", False), ("front", False), ("end", True)],
+                         ids=["end", "middle", "front", "csc"])
+@pytest.mark.parametrize("act", ACTS, ids=ACT_IDS)
+def test_coop_long_prompts_against_oracle(position, csc, act):
+    """CoOp with n_ctx 16 on class names that make prompts of 76 / 65 / 36 / 25 / 71 tokens (CLIP's context less the one
+    unused RPO row): the dense attention backward's keys 64-75, for every class-token position and class-specific
+    contexts.  Measured worst (logits / loss / ctx grad rel): f32 1.7e-5 / 6.9e-6 / 2.9e-6; f16 1.3e-2 / 5.3e-3 / 3.7e-3;
+    bf16 6.2e-2 / 3.3e-2 / 1.6e-2."""
+    _check_coop(act, _sibling_case("coop", "ViT-B/16", SIB_LONG, 16, 2, position, csc),
+                class_token_position=position, csc=csc)
+
+
+@pytest.mark.parametrize("shape", ["100cls_b4", "long_b2"])
+@pytest.mark.parametrize("act", ACTS, ids=ACT_IDS)
+def test_cocoop_many_classes_and_long_prompts_against_oracle(shape, act):
+    """CoCoOp over 100 classes x 4 images (each image's replica of the class set reduced by the wide rpo_reduce_groups)
+    and on 76-token prompts (n_ctx 16): loss, logits and the gradients of ctx and the four meta-net tensors.  Measured
+    worst (logits / loss / gradients rel): f32 2.1e-5 / 8.1e-6 / 5.3e-6; f16 1.17e-2 at |logits| 10.7 (bound 1.23e-2) /
+    4.3e-3 / 3.0e-3; bf16 8.2e-2 / 3.2e-2 / 2.0e-2."""
+    case = (_sibling_case("cocoop", "ViT-B/16", SIB_MANY[100], 4, 4) if shape == "100cls_b4"
+            else _sibling_case("cocoop", "ViT-B/16", SIB_LONG, 16, 2))
+    _check_cocoop(act, case)
+
+
+@pytest.mark.parametrize("kind", ["coop", "cocoop"])
+@pytest.mark.parametrize("act", ACTS, ids=ACT_IDS)
+def test_siblings_vit_l14_widths_against_oracle(kind, act):
+    """Both sibling trainers at ViT-L/14 widths (d_v 1024 / patch 14, d_t 768 with 12 heads, embed 768, meta-net h 48).
+    Measured worst (logits / gradients rel): f32 9.5e-6 / 3.5e-6; f16 5.2e-3 / 1.9e-3; bf16 5.8e-2 / 1.6e-2."""
+    case = _sibling_case(kind, "ViT-L/14", SIB_MANY[7], 4, 2)
+    _check_coop(act, case) if kind == "coop" else _check_cocoop(act, case)
+
+
+# ---- graph replay == eager for the sibling trainers at the bench's configurations ----------------------------------------
+@functools.lru_cache(maxsize=1)
+def _sibling_bench_workload():
+    from rpo_amd.config import vit_b16
+    cfg = vit_b16(K=1)                                # bench.py bench_sibling: full ViT-B/16, 19 classes
+    base = synth.default_tokens(cfg)
+    return cfg, base, synth.clip_state_dict(cfg, seed=0, token_rows=np.unique(base).tolist() + [49407])
+
+
+def _graph_vs_eager(trainer, n_ctx, B, act, amp=False, poison_step=None):
+    """Five steps of two trainers on the same batches, eager launches against graph replay (step 0 eager, step 1 captured,
+    recaptured at steps 2 and 4 where the warm-up + cosine schedule changes the LR over 2-batch epochs): the per-step
+    losses, the parameters and the momentum must agree bit for bit."""
+    from rpo_amd.coop import CoCoOp, CoOp
+    from rpo_amd.trainer import OptimConfig
+    cfg, base, sd = _sibling_bench_workload()
+    toks = synth.coop_tokens(base, n_ctx)
+    oc = OptimConfig(lr=0.002, max_epoch=10, lr_scheduler="cosine", warmup_epoch=1, warmup_cons_lr=1e-5)
+    Tr = CoOp if trainer == "coop" else CoCoOp
+    runs = []
+    for use_graph in (False, True):
+        torch.manual_seed(0)                          # the same initial ctx / meta-net draws
+        tr = Tr(sd, toks, n_ctx, oc, "cuda:0", act, batch_size=B, num_batches=2, use_graph=use_graph, amp=amp)
+        ls, lrs = [], []
+        for step in range(5):
+            img = torch.from_numpy(synth.images(cfg, B, seed=300 + step))
+            if step == poison_step:
+                img[0, 0, 0, 0] = float("inf")
+            lrs.append(tr.lr)
+            ls.append(tr.forward_backward({"img": img, "label": torch.from_numpy(synth.labels(cfg, B, seed=400 + step))})["loss"])
+        if use_graph:
+            assert tr._graph is not None and tr._graph[1] == lrs[-1], "the step was not replayed from a graph"
+        torch.cuda.synchronize()
+        runs.append((np.array(ls), tr.engine.coop_params.clone(), tr.engine.coop_moms.clone(), tr.skipped_steps))
+        del tr
+    assert len(set(lrs)) == 3, lrs
+    (la, pa, ma, sa), (lb, pb, mb, sb) = runs
+    print(f"[{trainer} graph B={B} {act} amp={amp}] losses {la.tolist()} skipped {sa}")
+    assert la.tobytes() == lb.tobytes(), f"losses: eager {la.tolist()} vs graph {lb.tolist()}"
+    assert torch.equal(pa, pb) and torch.equal(ma, mb), "graph replay must be bit-identical to eager launches"
+    assert sa == sb
+    return la, sa
+
+
+def test_coop_graph_replay_equals_eager():
+    """bench.py --trainer coop's step (n_ctx 16, B 32, bf16), graph-replayed as the bench times it."""
+    la, _ = _graph_vs_eager("coop", 16, 32, torch.bfloat16)
+    assert np.isfinite(la).all()
+
+
+@pytest.mark.parametrize("B", [1, 4])
+def test_cocoop_graph_replay_equals_eager(B):
+    """bench.py --trainer cocoop's step (n_ctx 4, B 1, bf16) and a 4-image batch: the per-image head loop and the
+    meta-net inside the graph."""
+    la, _ = _graph_vs_eager("cocoop", 4, B, torch.bfloat16)
+    assert np.isfinite(la).all()
+
+
+def test_coop_amp_graph_replay_skips_as_eager():
+    """amp: a poisoned batch at a replayed step (step 3) skips the update in the graph exactly as in eager mode."""
+    la, skipped = _graph_vs_eager("coop", 16, 32, torch.bfloat16, amp=True, poison_step=3)
+    assert skipped == 1 and np.isnan(la[3]) and np.isfinite(np.delete(la, 3)).all()
+
+
 def test_weight_prefetch_hints_do_not_change_the_step(monkeypatch):
     """The prefetch hints of the step (every GEMM names the weights its successor reads) are
     timing-only: two optimiser steps at the bench's shape with them and without them (RPO_NO_WPREFETCH=1) leave

@@ -950,6 +950,148 @@ def test_text_attn_fwd_bwd(mode, lens, Kr):
         close(outc[sl], ref, mode, f"text causal attn class {c}", tol=None if mode == "f32" else 8e-3)
 
 
+def _relerr(got, ref):
+    got, ref = got.detach().to(torch.float64).cpu(), ref.to(torch.float64)
+    return (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
+
+
+# CoOp / CoCoOp's causal attention backward with dK / dV over every token (rpo_text_attn_bwd_dense).  Keys 0-63 live in
+# the kernel's first score set and keys 64-79 in its second (j1 = lane + 64): Lmax 64 leaves the second set empty, 65 /
+# 77 / 80 fill part or all of it, and the lengths put classes on both sides of the 64 boundary in one launch.  The
+# 1000-class grid is ImageNet's class count at the prompts' usual 4-25 tokens.
+# Measured worst relative errors: f32 6.3e-7, f16 4.0e-4, bf16 3.6e-3.
+DENSE_CASES = [(1, 64, [64, 1, 63, 17]), (8, 65, [65, 64, 1, 63, 30]), (12, 77, [1, 63, 64, 65, 77, 40]),
+               (8, 80, [80, 65, 64, 63, 1, 79]), (12, 80, [80, 2, 66]),
+               (8, 25, [4 + (7 * c) % 22 for c in range(1000)])]
+
+
+@pytest.mark.parametrize("H,Lmax,lens", DENSE_CASES, ids=["H1_L64", "H8_L65", "H12_L77", "H8_L80", "H12_L80", "H8_1000cls"])
+@pytest.mark.parametrize("mode", ["f32", "bf16", "f16"])
+def test_text_attn_bwd_dense_against_float64(mode, H, Lmax, lens):
+    """dq, dk, dv of rpo_text_attn_bwd_dense against float64 autograd of the causal attention of each class's first
+    len[c] rows (R.attn_causal_fwd), in the engine's layout: q / k / v column views of one packed [n Lmax, 3d] buffer,
+    d_out with a leading dimension of its own, dq / dk / dv column views of one NaN-filled [n Lmax, 3d] output.  Rows at
+    or past len[c] must come out exactly 0 (the dX GEMM after it reads every row), nothing may stay NaN, and a second
+    launch gives the same bits."""
+    from rpo_amd._lib import RPOLibraryError
+    o = ops()
+    n, d = len(lens), 64 * H
+    assert max(lens) == Lmax
+    qkv = rnd((n * Lmax, 3 * d), 101)
+    qkv[:, :d] *= 1.5                                 # sharper softmax rows
+    dout = torch.zeros(n * Lmax, d + 96)              # d_out: [:, 32:32 + d] of a wider buffer
+    dout[:, 32:32 + d] = rnd((n * Lmax, d), 102)
+    t = qkv.to(dev(), DT[mode])
+    do_d = dout.to(dev(), DT[mode])[:, 32:32 + d]
+    len_d = torch.tensor(lens, dtype=torch.int32, device=dev())
+    g = torch.full((n * Lmax, 3 * d), float("nan"), dtype=DT[mode], device=dev())
+    o.text_attn_bwd_dense(t[:, :d], t[:, d:2 * d], t[:, 2 * d:], do_d, g[:, :d], g[:, d:2 * d], g[:, 2 * d:], len_d, n,
+                          Lmax, H, 0.125)
+    got = g.cpu()
+    assert not torch.isnan(got).any(), "an output element was never written"
+    q3, do3 = q(qkv, mode), q(dout[:, 32:32 + d], mode)
+    ref = torch.zeros(n * Lmax, 3 * d, dtype=torch.float64)
+    valid = torch.zeros(n * Lmax, dtype=torch.bool)
+    for c, L in enumerate(lens):
+        sl = slice(c * Lmax, c * Lmax + L)
+        qa, ka, va = (q3[sl, i * d:(i + 1) * d].clone().requires_grad_(True) for i in range(3))
+        out = R.attn_causal_fwd(qa, ka, va, H, torch.arange(1, L + 1))
+        ref[sl] = torch.cat(torch.autograd.grad(out, (qa, ka, va), do3[sl]), dim=1)
+        valid[sl] = True
+    tol = None if mode == "f32" else 8e-3
+    errs = {}
+    for i, name in enumerate(("dq", "dk", "dv")):
+        cs = slice(i * d, (i + 1) * d)
+        errs[name] = _relerr(got[valid, cs], ref[valid, cs])
+        close(got[valid, cs], ref[valid, cs], mode, f"dense attn bwd {name}", tol=tol)
+        pad = got[~valid, cs]
+        assert pad.numel() == 0 or torch.count_nonzero(pad).item() == 0, f"{name}: rows at or past len[c] are not 0"
+    print(f"[dense attn bwd {mode} H={H} Lmax={Lmax} n={n}] rel err " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    g2 = torch.full_like(g, float("nan"))
+    o.text_attn_bwd_dense(t[:, :d], t[:, d:2 * d], t[:, 2 * d:], do_d, g2[:, :d], g2[:, d:2 * d], g2[:, 2 * d:], len_d,
+                          n, Lmax, H, 0.125)
+    assert torch.equal(g2.cpu().view(torch.int16 if mode != "f32" else torch.int32),
+                       got.view(torch.int16 if mode != "f32" else torch.int32)), "a second launch changed bits"
+    if Lmax == 80:                                    # beyond the kernel's 80-key staging: refused, nothing launched
+        with pytest.raises(RPOLibraryError):
+            o.text_attn_bwd_dense(t[:, :d], t[:, d:2 * d], t[:, 2 * d:], do_d, g2[:, :d], g2[:, d:2 * d], g2[:, 2 * d:],
+                                  len_d, n, 81, H, 0.125)
+
+
+# CoCoOp's meta-net (rpo_metanet_fwd / _bwd): ViT-B/16 (e 512, h 32, d_t 512) at batch 1 and 3, ViT-L/14 (768, 48, 768),
+# a ragged shape (h not a multiple of the 4 waves, d not a multiple of 256) and the backward's LDS limit: B h 4 bytes =
+# 48 KB at B = 384, h = 32.  Measured worst relative error: 8.8e-7 (g_b1 at B = 3).
+METANET_TOL = 1e-5
+METANET_CASES = [(1, 512, 32, 512), (3, 512, 32, 512), (32, 768, 48, 768), (5, 100, 7, 600), (384, 512, 32, 512)]
+
+
+@pytest.mark.parametrize("B,e,h,d", METANET_CASES)
+def test_metanet_fwd_bwd_against_float64(B, e, h, d):
+    """f_norm, hidden, bias and the four gradients against float64 autograd of linear2(relu(linear1(f / |f|))) under a
+    random upstream d_bias.  b1 kills some hidden units for every image and leaves others alive for some images only,
+    so the ReLU mask decides gradients.  The gradients go into one flat [w1 | b1 | w2 | b2] buffer (the engine's
+    coop_grads layout) between NaN guard regions that must stay untouched; a repeat call gives the same bits."""
+    o = ops()
+    f = rnd((B, e), 111, 3.0)
+    w1, w2 = rnd((h, e), 112), rnd((d, h), 113, h ** -0.5)
+    b1 = rnd((h,), 114, 0.5)
+    b1[0::3] = -50.0                                  # |w1 . f_norm| <= |w1 row| ~ sqrt(e) < 50: dead for every image
+    b2, dbias = rnd((d,), 115), rnd((B, d), 116)
+    f64 = f.double()
+    P = {k: v.double().requires_grad_(True) for k, v in dict(w1=w1, b1=b1, w2=w2, b2=b2).items()}
+    fn64 = f64 / f64.norm(dim=1, keepdim=True)
+    hid64 = torch.relu(fn64 @ P["w1"].t() + P["b1"])
+    bias64 = hid64 @ P["w2"].t() + P["b2"]
+    gref = dict(zip(P, torch.autograd.grad(bias64, list(P.values()), dbias.double())))
+    alive = hid64 > 0
+    assert (~alive).all(0).any(), "no unit is dead for every image"
+    if B >= 3:
+        assert (alive.any(0) & ~alive.all(0)).any(), "no unit is alive for some images only"
+    nan = lambda *s: torch.full(s, float("nan"), device=dev())
+    fn, hid, bias = nan(B, e), nan(B, h), nan(B, d)
+    wd = {k: v.to(dev()) for k, v in dict(w1=w1, b1=b1, w2=w2, b2=b2).items()}
+    o.metanet_fwd(f.to(dev()), wd["w1"], wd["b1"], wd["w2"], wd["b2"], fn, hid, bias)
+    G = 1000
+    sizes = [h * e, h, d * h, d]
+    flat = nan(G + sum(sizes) + G)
+    offs = np.cumsum([G] + sizes)
+    gw1, gb1, gw2, gb2 = (flat[offs[i]:offs[i + 1]] for i in range(4))
+    o.metanet_bwd(dbias.to(dev()), fn, hid, wd["w2"], gw1.view(h, e), gb1, gw2.view(d, h), gb2)
+    got = dict(f_norm=(fn, fn64), hidden=(hid, hid64), bias=(bias, bias64), g_w1=(gw1.view(h, e), gref["w1"]),
+               g_b1=(gb1, gref["b1"]), g_w2=(gw2.view(d, h), gref["w2"]), g_b2=(gb2, gref["b2"]))
+    errs = {k: _relerr(a, r) for k, (a, r) in got.items()}
+    print(f"[metanet B={B} e={e} h={h} d={d}] rel err " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    for k, (a, r) in got.items():
+        close(a, r.detach(), "f32", f"metanet {k}", tol=METANET_TOL)
+    # dead units: exactly zero activations and zero linear1 gradients
+    dead = (~alive).all(0)
+    assert torch.count_nonzero(hid.cpu()[:, dead]).item() == 0
+    assert torch.count_nonzero(gw1.view(h, e).cpu()[dead]).item() == 0 and torch.count_nonzero(gb1.cpu()[dead]).item() == 0
+    flat_c = flat.cpu()
+    assert torch.isnan(flat_c[:G]).all() and torch.isnan(flat_c[-G:]).all(), "a guard region was written"
+    before = [t.clone() for t in (fn, hid, bias, flat)]
+    o.metanet_fwd(f.to(dev()), wd["w1"], wd["b1"], wd["w2"], wd["b2"], fn, hid, bias)
+    o.metanet_bwd(dbias.to(dev()), fn, hid, wd["w2"], gw1.view(h, e), gb1, gw2.view(d, h), gb2)
+    for a, b in zip(before, (fn, hid, bias, flat)):
+        assert torch.equal(a.cpu().view(torch.int32), b.cpu().view(torch.int32)), "a repeat call changed bits"
+
+
+def test_metanet_refuses_what_does_not_fit_lds():
+    """The backward keeps dhid [B, h] in 48 KB of LDS (B = 385 at h = 32 is one image too many); the forward keeps
+    f_norm [e] and hidden [h] there ((e + h) 4 bytes > 48 KB is refused).  Refused with RPOLibraryError, nothing launched."""
+    from rpo_amd._lib import RPOLibraryError
+    o = ops()
+    z = lambda *s: torch.zeros(*s, device=dev())
+    B, e, h, d = 385, 512, 32, 512
+    with pytest.raises(RPOLibraryError):
+        o.metanet_bwd(z(B, d), z(B, e), z(B, h), z(d, h), z(h, e), z(h), z(d, h), z(d))
+    o.metanet_bwd(z(B - 1, d), z(B - 1, e), z(B - 1, h), z(d, h), z(h, e), z(h), z(d, h), z(d))   # 384: exactly fits
+    e = 48 * 1024 // 4 - h + 1
+    with pytest.raises(RPOLibraryError):
+        o.metanet_fwd(z(1, e), z(h, e), z(h), z(d, h), z(d), z(1, e), z(1, h), z(1, d))
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("B,C,K,e", [(4, 19, 24, 512), (32, 19, 24, 512), (100, 37, 16, 512), (5, 128, 8, 768),
                                      (3, 300, 4, 768), (1, 2, 1, 64), (7, 3, 5, 100),
                                      # the matrix-pipe path (C > 128) at the reference's ImageNet size and just past the fused path's 128
