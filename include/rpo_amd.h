@@ -73,7 +73,10 @@ enum {
      W'[n,k] = gamma[k] W[n,k], s[n] = sum_k W'[n,k], b'[n] = b[n] + sum_k beta[k] W[n,k]:
          LN(x) . W^T + b  =  rstd[m] * (x . W'^T - mu[m] * s[n]) + b'[n]
      so A is the RAW residual row (16-bit copy written by the producing GEMM, `out2` below), W = W', bias = b',
-     ln_colsum = s, and mu / rstd come from the per-row partial statistics the producer left in ln_stats. */
+     ln_colsum = s, and mu / rstd come from the per-row partial statistics the producer left in ln_stats.
+     Limit: A is x rounded to the act dtype, so a row whose spread is far below the act-dtype ulp of its mean (a
+     near-constant row: sigma 1e-4 at mean 3) loses its variation before the GEMM; the unfolded LayerNorm reads fp32 x.
+     Rows with channels in the hundreds or means up to 50 sigma stay within the unfolded path's tolerance. */
   RPO_EPI_LN_BIAS = 6,       /* C = LN-fold(acc)                        (ln_1 + in-proj)                     */
   RPO_EPI_LN_BIAS_QGELU = 7  /* C = quickgelu(LN-fold(acc)), aux as BIAS_QGELU   (ln_2 + c_fc)               */
 };

@@ -43,3 +43,28 @@ def oracle_for(tag):
     m = OracleRPO(sd, toks, cfg.K, cfg.patch)
     m.set_prompts(tp, ip)
     return m, image, label
+
+
+# fp32 unit roundoff: the kernels accumulate in fp32 whatever the storage mode
+U32 = 2.0 ** -24
+
+
+def assert_within(got, ref, bound, what, floor=0.0):
+    """Scale-aware check: every element of ``got`` is finite and within ``bound + floor`` of ``ref``, where ``bound``
+    (same shape, or broadcastable: per row) is a tolerance times the magnitude of the same computation taken over
+    absolute values -- so an outlier channel does not widen the budget of the rest of the tensor, which a bound on
+    max|err| / max|ref| over the whole tensor would.  Returns the worst err / (bound + floor)."""
+    got = got.detach().to(torch.float64).cpu()
+    ref = ref.detach().to(torch.float64).cpu()
+    lim = torch.broadcast_to(torch.as_tensor(bound, dtype=torch.float64).cpu(), ref.shape) + floor
+    bad = ~torch.isfinite(got)
+    assert not bad.any(), f"{what}: {int(bad.sum())} NaN / Inf, first at {tuple(bad.nonzero()[0].tolist())}"
+    assert torch.isfinite(ref).all() and torch.isfinite(lim).all(), f"{what}: non-finite reference"
+    err = (got - ref).abs()
+    ratio = err / lim.clamp_min(1e-300)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    if worst > 1.0:
+        i = tuple(int(v) for v in (ratio == ratio.max()).nonzero()[0].tolist())
+        raise AssertionError(f"{what}: err {err[i]:.3e} > bound {lim[i]:.3e} at {i} (got {got[i]:.6e}, ref {ref[i]:.6e}; "
+                             f"{int((ratio > 1).sum())} of {ratio.numel()} elements over, worst ratio {worst:.2f})")
+    return worst
