@@ -192,6 +192,15 @@ int rpo_gemm_stats_group(const rpo_gemm_args* args);
  * (resid_hi, resid_lo, out_lo, c_row0 above), else 0.  Looks at the same fields as rpo_gemm_stats_group plus ln_group. */
 int rpo_gemm_hilo_ok(const rpo_gemm_args* args);
 
+/* What rpo_gemm_nt would do with these arguments, without launching anything: the tile_config value that forces the
+ * kernel it would run (> 0: 5 = 64x64, 6 = 64x128, 2 = 128x128, 9 = 128x128 with 4 waves, 3 / 7 / 8 = 256x256,
+ * 10 = 224x384 / 288x256 row-unit tiles, 11 = 224x96 / 256x96 / 288x64 split-k tiles), or the negative RPO_E_* it would
+ * return.  Same argument checks and the same choice as the call (one code path); pointers are checked, not dereferenced.
+ * A launch error (> 0 from the call) is not predicted. */
+int rpo_gemm_nt_plan(const rpo_gemm_args* args);
+/* The same for rpo_gemm_ws: its geometry as the tile_config code 100 * MT + 10 * NT (> 0), or the RPO_E_* it would return. */
+int rpo_gemm_ws_plan(const rpo_gemm_args* args);
+
 /* y = LayerNorm(x) * gamma + beta, statistics in fp32, eps as given (1e-5).
  * x fp32 [rows, d] (ldx), y in y_dtype.  d % 4 == 0, d <= 2048.  In-place (y == x, fp32) is allowed.
  * Replaces clip/model.py:153-159 (ln_1, ln_2, ln_pre, ln_post, ln_final). */

@@ -101,6 +101,8 @@ SIGNATURES = {
     "rpo_version": (c_i32, []),
     "rpo_gemm_stats_group": (c_i32, [C.POINTER(GemmArgs)]),
     "rpo_gemm_hilo_ok": (c_i32, [C.POINTER(GemmArgs)]),
+    "rpo_gemm_nt_plan": (c_i32, [C.POINTER(GemmArgs)]),
+    "rpo_gemm_ws_plan": (c_i32, [C.POINTER(GemmArgs)]),
     "rpo_error_string": (C.c_char_p, [c_i32]),
     "rpo_gemm_nt": (c_i32, [C.POINTER(GemmArgs), c_vp]),
     "rpo_gemm_ws": (c_i32, [C.POINTER(GemmArgs), c_vp]),

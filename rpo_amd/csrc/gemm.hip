@@ -937,27 +937,35 @@ int launch_cfg(const GemmParams& p, hipStream_t s) {
   return rpo_launch_status();
 }
 
-// shape heuristic (measured on MI355X, tools/bench_gemm.py): see the Cfg comments
+// Which kernels an instantiation has: the 224x96 / 288x64 split-k residual kernel (tile_config 11), and the 256x256-class
+// kernels of the wide 16-bit forward GEMMs (3, 7, 8, 10)
 template <typename TIn, typename TOut, int EPI>
-int launch(const GemmParams& p, hipStream_t s) {
+constexpr bool w4k_ok_v = EPI == RPO_EPI_BIAS_RESID && sizeof(TIn) == 2 && sizeof(TOut) == 4;
+template <typename TIn, typename TOut, int EPI>
+constexpr bool big_ok_v = sizeof(TIn) == 2 && sizeof(TOut) == 2 &&
+                          (EPI == RPO_EPI_BIAS || EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_LN_BIAS || EPI == RPO_EPI_LN_BIAS_QGELU);
+
+// Shape heuristic (measured on MI355X, tools/bench_gemm.py): see the Cfg comments.  Returns the tile_config value that
+// forces the kernel this call runs (> 0; launch() switches on it, rpo_gemm_nt_plan() reports it) or the RPO_E_* the call
+// refuses with.  Nothing is dereferenced.
+template <typename TIn, typename TOut, int EPI>
+int choose(const GemmParams& p) {
   // N = 768-class GEMMs with a residual epilogue (out-proj, c_proj): one round of 224x96 split-k tiles when the caller's
   // row units allow it (gemm_w4k.inc).  Its row statistics are over 96 columns, the generic epilogues' over 64: the
   // caller says which it expects (rpo_gemm_args.ln_group) and gets an error instead of the other layout.
-  if constexpr (EPI == RPO_EPI_BIAS_RESID && sizeof(TIn) == 2 && sizeof(TOut) == 4) {
+  if constexpr (w4k_ok_v<TIn, TOut, EPI>) {
     W4KPlan kplan;
     const bool fits32 = (int64_t)p.M * p.lda * 2 < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
     const int kgrp = w4k_plan(p, &kplan);                           // 0, or the geometry's statistics group (96 / 64)
     const bool k_ok = p.split_k == 1 && fits32 && kgrp != 0 && aligned16(p.C) && p.ldc % 4 == 0 &&
                       (p.ln_stats == nullptr || p.ln_group == kgrp);
-    if (k_ok && (p.force_cfg == 11 || p.force_cfg == 0)) return launch_w4k<TIn>(p, s);
+    if (k_ok && (p.force_cfg == 11 || p.force_cfg == 0)) return 11;
     if (p.force_cfg == 11 || (p.ln_stats != nullptr && p.ln_group != LN_GROUP)) return RPO_E_SHAPE;
   }
   if (p.resid_hi != nullptr || p.out_lo != nullptr || p.c_row0 > 0) return RPO_E_SHAPE;   // only the kernel above implements hi / lo
   // measured (tools/bench_gemm.py, profiles/): 256x256 wins for the wide-N forward GEMMs of the image tower
   // (in-proj 31.6 vs 36.1 us); a 4-stage 128x128 variant was slower than 2 stages on every shape
-  constexpr bool big_ok = sizeof(TIn) == 2 && sizeof(TOut) == 2 &&
-                          (EPI == RPO_EPI_BIAS || EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_LN_BIAS || EPI == RPO_EPI_LN_BIAS_QGELU);
-  if constexpr (big_ok) {
+  if constexpr (big_ok_v<TIn, TOut, EPI>) {
     // one 256x256 workgroup per CU: only worth it when the tiles fill whole rounds of the 256 CUs
     // (in-proj at B=32: 252 tiles; c_fc: 336 tiles = 1.3 rounds -> 65 us vs 55 us with 128x128; ViT-L/14 in-proj at
     //  B=16: 216 tiles = 84 % of one round, step 7.42 -> 7.28 ms with it)
@@ -985,14 +993,14 @@ int launch(const GemmParams& p, hipStream_t s) {
       const bool big_shape = p.force_cfg == 0 && p.M >= 2048 && p.N >= 1536;
       // ... or whole rounds of row-unit tiles (64 / 128 images: 2 / 4 rounds; 256x256 tiles would need 2.6 / 5.3)
       if (g_ok && (p.force_cfg == 10 || (big_shape && (!fills || (gplan.from_units && gplan.tiles_m * gplan.tiles_n % RPO_W4G_MOD == 0)))))
-        return launch_w4g<TOut, EPI>(p, s);
+        return 10;
     }
     // a single round that fills at least 55 % of the CUs still favours the one-wave-per-SIMD kernel (K / V projection of
     // the frozen rows in the last image block, 6304 x 1536 x 768 = 150 tiles: 22.1 vs 25.6 us ping-pong, 28.6 us 128x128)
     const bool one_round_ok = p.force_cfg == 0 && p.M >= 2048 && p.N >= 1536 && rounds == 1 && tiles * 100 >= 256 * 55;
-    if (w4_ok && (p.force_cfg == 8 || wants_big || one_round_ok)) return launch_w4<TOut, EPI>(p, s);
-    if (ok && (p.force_cfg == 7 || wants_big)) return launch_pp<TOut, EPI>(p, s);
-    if (ok && p.force_cfg == 3) return launch_cfg<TIn, TOut, EPI, CfgBig>(p, s);
+    if (w4_ok && (p.force_cfg == 8 || wants_big || one_round_ok)) return 8;
+    if (ok && (p.force_cfg == 7 || wants_big)) return 7;
+    if (ok && p.force_cfg == 3) return 3;
   }
   // small-M GEMMs (prompt rows: backward, text tower) are a latency chain on few CUs: 64x64 tiles give 4x
   // the workgroups and half the per-k-tile DMA issue per wave (da 9.2 -> 5.9 us, text c_proj 19.7 -> 11.3 us);
@@ -1002,45 +1010,76 @@ int launch(const GemmParams& p, hipStream_t s) {
 #endif
   // ... except wide, short-K outputs from 1024 rows on (in-proj / c_fc of the image forward at a batch of 5 .. 9): 64x128
   // tiles with 8 waves, bit-identical (c_fc at M = 1768: 17.2 vs 22.2 us; the long-K c_proj stays on 64x64: 25 vs 31 us)
-  if (p.force_cfg == 0 && p.M >= 1024 && p.M < 2048 && p.N >= 1536 && p.K <= 1024 && p.split_k == 1)
-    return launch_cfg<TIn, TOut, EPI, CfgTall>(p, s);
-  if (p.force_cfg == 5 || (p.force_cfg == 0 && p.M < 2048 && p.N <= RPO_TINY_MAXN)) return launch_cfg<TIn, TOut, EPI, CfgTiny>(p, s);
+  if (p.force_cfg == 0 && p.M >= 1024 && p.M < 2048 && p.N >= 1536 && p.K <= 1024 && p.split_k == 1) return 6;
+  if (p.force_cfg == 5 || (p.force_cfg == 0 && p.M < 2048 && p.N <= RPO_TINY_MAXN)) return 5;
 #ifndef RPO_TALL_N
 #define RPO_TALL_N 1024
 #endif
   if constexpr (sizeof(TIn) == 2) {
-    if (p.force_cfg == 9) return launch_cfg<TIn, TOut, EPI, CfgQuad>(p, s);
+    if (p.force_cfg == 9) return 9;
   }
   // ... up to 8192 rows: from there on (the text tower over hundreds of classes: 24 000 prompt rows at ImageNet's 1000) the
   // 64x128 tiles' DMA bytes lose to 128x128 (tools/bench_gemm.py --only "t1k_*", profiles/r06_bench_gemm_t1k.txt: q-proj
   // 26.8 -> 23.6 us, c_proj 75.6 -> 68.4, d c_fc 71.2 -> 64.0 at 24 000 x 512)
-  if (p.force_cfg == 6 || (p.force_cfg == 0 && p.N <= RPO_TALL_N && p.M < 8192)) return launch_cfg<TIn, TOut, EPI, CfgTall>(p, s);
-  return launch_cfg<TIn, TOut, EPI, CfgMid>(p, s);
+  if (p.force_cfg == 6 || (p.force_cfg == 0 && p.N <= RPO_TALL_N && p.M < 8192)) return 6;
+  return 2;
+}
+
+// plan_only: return choose()'s verdict without launching (rpo_gemm_nt_plan)
+template <typename TIn, typename TOut, int EPI>
+int launch(const GemmParams& p, hipStream_t s, bool plan_only) {
+  const int cfg = choose<TIn, TOut, EPI>(p);
+  if (plan_only || cfg < 0) return cfg;
+  switch (cfg) {
+    case 11:
+      if constexpr (w4k_ok_v<TIn, TOut, EPI>) return launch_w4k<TIn>(p, s);
+      break;
+    case 10:
+      if constexpr (big_ok_v<TIn, TOut, EPI>) return launch_w4g<TOut, EPI>(p, s);
+      break;
+    case 8:
+      if constexpr (big_ok_v<TIn, TOut, EPI>) return launch_w4<TOut, EPI>(p, s);
+      break;
+    case 7:
+      if constexpr (big_ok_v<TIn, TOut, EPI>) return launch_pp<TOut, EPI>(p, s);
+      break;
+    case 3:
+      if constexpr (big_ok_v<TIn, TOut, EPI>) return launch_cfg<TIn, TOut, EPI, CfgBig>(p, s);
+      break;
+    case 9:
+      if constexpr (sizeof(TIn) == 2) return launch_cfg<TIn, TOut, EPI, CfgQuad>(p, s);
+      break;
+    case 6: return launch_cfg<TIn, TOut, EPI, CfgTall>(p, s);
+    case 5: return launch_cfg<TIn, TOut, EPI, CfgTiny>(p, s);
+    case 2: return launch_cfg<TIn, TOut, EPI, CfgMid>(p, s);
+    default: break;
+  }
+  return RPO_E_SHAPE;            // (not reached: choose() names only kernels this instantiation has)
 }
 
 template <typename TIn, typename TOut>
-int dispatch_epi(int epi, const GemmParams& p, hipStream_t s) {
+int dispatch_epi(int epi, const GemmParams& p, hipStream_t s, bool plan_only) {
   switch (epi) {
-    case RPO_EPI_NONE: return launch<TIn, TOut, RPO_EPI_NONE>(p, s);
-    case RPO_EPI_BIAS: return launch<TIn, TOut, RPO_EPI_BIAS>(p, s);
-    case RPO_EPI_BIAS_QGELU: return launch<TIn, TOut, RPO_EPI_BIAS_QGELU>(p, s);
-    case RPO_EPI_QGELU_BWD: return launch<TIn, TOut, RPO_EPI_QGELU_BWD>(p, s);
+    case RPO_EPI_NONE: return launch<TIn, TOut, RPO_EPI_NONE>(p, s, plan_only);
+    case RPO_EPI_BIAS: return launch<TIn, TOut, RPO_EPI_BIAS>(p, s, plan_only);
+    case RPO_EPI_BIAS_QGELU: return launch<TIn, TOut, RPO_EPI_BIAS_QGELU>(p, s, plan_only);
+    case RPO_EPI_QGELU_BWD: return launch<TIn, TOut, RPO_EPI_QGELU_BWD>(p, s, plan_only);
     case RPO_EPI_LN_BIAS:
-      if constexpr (sizeof(TOut) == 2) return launch<TIn, TOut, RPO_EPI_LN_BIAS>(p, s);
+      if constexpr (sizeof(TOut) == 2) return launch<TIn, TOut, RPO_EPI_LN_BIAS>(p, s, plan_only);
       return RPO_E_DTYPE;
     case RPO_EPI_LN_BIAS_QGELU:
-      if constexpr (sizeof(TOut) == 2) return launch<TIn, TOut, RPO_EPI_LN_BIAS_QGELU>(p, s);
+      if constexpr (sizeof(TOut) == 2) return launch<TIn, TOut, RPO_EPI_LN_BIAS_QGELU>(p, s, plan_only);
       return RPO_E_DTYPE;
     default: return RPO_E_DTYPE;
   }
 }
 
 template <typename TIn>
-int dispatch_f32out(int epi, const GemmParams& p, hipStream_t s) {
+int dispatch_f32out(int epi, const GemmParams& p, hipStream_t s, bool plan_only) {
   switch (epi) {
-    case RPO_EPI_BIAS_RESID: return launch<TIn, float, RPO_EPI_BIAS_RESID>(p, s);
-    case RPO_EPI_PATCH: return launch<TIn, float, RPO_EPI_PATCH>(p, s);
-    default: return dispatch_epi<TIn, float>(epi, p, s);
+    case RPO_EPI_BIAS_RESID: return launch<TIn, float, RPO_EPI_BIAS_RESID>(p, s, plan_only);
+    case RPO_EPI_PATCH: return launch<TIn, float, RPO_EPI_PATCH>(p, s, plan_only);
+    default: return dispatch_epi<TIn, float>(epi, p, s, plan_only);
   }
 }
 
@@ -1158,22 +1197,30 @@ extern "C" int rpo_gemm_hilo_ok(const rpo_gemm_args* a) {
   return kgrp != 0 && a->ldc % 4 == 0 && want == kgrp ? 1 : 0;
 }
 
-extern "C" int rpo_gemm_nt(const rpo_gemm_args* a, void* stream) {
+// rpo_gemm_nt, or with plan_only its verdict (rpo_gemm_nt_plan): one path through the checks and the kernel choice
+static int gemm_nt_run(const rpo_gemm_args* a, hipStream_t s, bool plan_only) {
   GemmParams p;
   if (int rc = gemm_prepare(a, p)) return rc;
   const bool in_f16 = a->in_dtype == RPO_F16;
   const bool in_bf16 = a->in_dtype == RPO_BF16 || in_f16, out_bf16 = a->out_dtype == RPO_BF16 || a->out_dtype == RPO_F16;
   const int epi = a->epilogue;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   if (in_f16) {
-    if (out_bf16) return dispatch_epi<f16_t, f16_t>(epi, p, s);
-    return dispatch_f32out<f16_t>(epi, p, s);
+    if (out_bf16) return dispatch_epi<f16_t, f16_t>(epi, p, s, plan_only);
+    return dispatch_f32out<f16_t>(epi, p, s, plan_only);
   }
   if (in_bf16) {
-    if (out_bf16) return dispatch_epi<bf16_t, bf16_t>(epi, p, s);
-    return dispatch_f32out<bf16_t>(epi, p, s);
+    if (out_bf16) return dispatch_epi<bf16_t, bf16_t>(epi, p, s, plan_only);
+    return dispatch_f32out<bf16_t>(epi, p, s, plan_only);
   }
-  return dispatch_f32out<float>(epi, p, s);
+  return dispatch_f32out<float>(epi, p, s, plan_only);
+}
+
+extern "C" int rpo_gemm_nt(const rpo_gemm_args* a, void* stream) {
+  return gemm_nt_run(a, static_cast<hipStream_t>(stream), false);
+}
+
+extern "C" int rpo_gemm_nt_plan(const rpo_gemm_args* a) {
+  return gemm_nt_run(a, nullptr, true);
 }
 
 #ifdef RPO_EXPERIMENTAL   // measured-slower experiments (include/rpo_amd_experimental.h): rpo_mlp_fused, rpo_gemm_nt_pair

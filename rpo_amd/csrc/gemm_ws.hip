@@ -492,8 +492,10 @@ int ws_launch_t(WsParams& p, hipStream_t s) {
   return rpo_launch_status();
 }
 
+// plan_only: the geometry's tile_config code instead of a launch (rpo_gemm_ws_plan)
 template <typename T, typename TOut, int EPI>
-int ws_launch(WsParams& p, const WsPlan& q, hipStream_t s) {
+int ws_launch(WsParams& p, const WsPlan& q, hipStream_t s, bool plan_only) {
+  if (plan_only) return ws_geometry_ok(q.mt, q.nt) ? 100 * q.mt + 10 * q.nt : RPO_E_SHAPE;
   if (q.mt == 3 && q.nt == 3) return ws_launch_t<T, TOut, EPI, WsCfg<3, 3>>(p, s);
   if (q.mt == 2 && q.nt == 2) return ws_launch_t<T, TOut, EPI, WsCfg<2, 2>>(p, s);
   if (q.mt == 1 && q.nt == 2) return ws_launch_t<T, TOut, EPI, WsCfg<1, 2>>(p, s);
@@ -502,22 +504,22 @@ int ws_launch(WsParams& p, const WsPlan& q, hipStream_t s) {
 }
 
 template <typename T>
-int ws_dispatch(int epi, bool out16, WsParams& p, const WsPlan& q, hipStream_t s) {
+int ws_dispatch(int epi, bool out16, WsParams& p, const WsPlan& q, hipStream_t s, bool plan_only) {
   switch (epi) {
     case RPO_EPI_NONE:
-      return out16 ? ws_launch<T, T, RPO_EPI_NONE>(p, q, s) : ws_launch<T, float, RPO_EPI_NONE>(p, q, s);
+      return out16 ? ws_launch<T, T, RPO_EPI_NONE>(p, q, s, plan_only) : ws_launch<T, float, RPO_EPI_NONE>(p, q, s, plan_only);
     case RPO_EPI_QGELU_BWD:
-      return out16 ? ws_launch<T, T, RPO_EPI_QGELU_BWD>(p, q, s) : RPO_E_DTYPE;
+      return out16 ? ws_launch<T, T, RPO_EPI_QGELU_BWD>(p, q, s, plan_only) : RPO_E_DTYPE;
     case RPO_EPI_BIAS:
-      return out16 ? ws_launch<T, T, RPO_EPI_BIAS>(p, q, s) : RPO_E_DTYPE;
+      return out16 ? ws_launch<T, T, RPO_EPI_BIAS>(p, q, s, plan_only) : RPO_E_DTYPE;
     case RPO_EPI_BIAS_QGELU:
-      return out16 ? ws_launch<T, T, RPO_EPI_BIAS_QGELU>(p, q, s) : RPO_E_DTYPE;
+      return out16 ? ws_launch<T, T, RPO_EPI_BIAS_QGELU>(p, q, s, plan_only) : RPO_E_DTYPE;
     case RPO_EPI_LN_BIAS:
-      return out16 ? ws_launch<T, T, RPO_EPI_LN_BIAS>(p, q, s) : RPO_E_DTYPE;
+      return out16 ? ws_launch<T, T, RPO_EPI_LN_BIAS>(p, q, s, plan_only) : RPO_E_DTYPE;
     case RPO_EPI_LN_BIAS_QGELU:
-      return out16 ? ws_launch<T, T, RPO_EPI_LN_BIAS_QGELU>(p, q, s) : RPO_E_DTYPE;
+      return out16 ? ws_launch<T, T, RPO_EPI_LN_BIAS_QGELU>(p, q, s, plan_only) : RPO_E_DTYPE;
     case RPO_EPI_BIAS_RESID:
-      return out16 ? RPO_E_DTYPE : ws_launch<T, float, RPO_EPI_BIAS_RESID>(p, q, s);
+      return out16 ? RPO_E_DTYPE : ws_launch<T, float, RPO_EPI_BIAS_RESID>(p, q, s, plan_only);
     default: return RPO_E_SHAPE;
   }
 }
@@ -620,13 +622,22 @@ extern "C" int rpo_gemm_ws_ok(const rpo_gemm_args* a) {
   return ws_prepare(&b, p, q) == 0 ? 1 : 0;
 }
 
-extern "C" int rpo_gemm_ws(const rpo_gemm_args* a, void* stream) {
+// rpo_gemm_ws, or with plan_only its verdict (rpo_gemm_ws_plan): one path through the checks, the tile choice
+// (ws_prepare -> ws_choose) and the epilogue / output-dtype dispatch
+static int ws_run(const rpo_gemm_args* a, hipStream_t s, bool plan_only) {
   WsParams p;
   WsPlan q;
   if (a == nullptr || a->A == nullptr || a->W == nullptr || a->C == nullptr) return RPO_E_BADARG;
   if (int rc = ws_prepare(a, p, q)) return rc;
   const bool out16 = a->out_dtype != RPO_F32;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a->in_dtype == RPO_F16) return ws_dispatch<f16_t>(a->epilogue, out16, p, q, s);
-  return ws_dispatch<bf16_t>(a->epilogue, out16, p, q, s);
+  if (a->in_dtype == RPO_F16) return ws_dispatch<f16_t>(a->epilogue, out16, p, q, s, plan_only);
+  return ws_dispatch<bf16_t>(a->epilogue, out16, p, q, s, plan_only);
+}
+
+extern "C" int rpo_gemm_ws(const rpo_gemm_args* a, void* stream) {
+  return ws_run(a, static_cast<hipStream_t>(stream), false);
+}
+
+extern "C" int rpo_gemm_ws_plan(const rpo_gemm_args* a) {
+  return ws_run(a, nullptr, true);
 }

@@ -216,6 +216,20 @@ def gemm_stats_group(M: int, N: int, K: int, dtype: torch.dtype, row_units: Opti
     return g
 
 
+def gemm_nt_plan(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epilogue: int = EPI_NONE, **kw) -> int:
+    """The tile_config value that forces the kernel `gemm_nt` would run with these arguments (> 0), or the negative RPO_E_*
+    it would return (rpo_gemm_nt_plan).  Nothing is launched."""
+    args = gemm_args(a, w, out, epilogue, **kw)
+    return int(_lib.load().rpo_gemm_nt_plan(C.byref(args)))
+
+
+def gemm_ws_plan(a: torch.Tensor, w: PackedWeight, out: torch.Tensor, epilogue: int = EPI_NONE, **kw) -> int:
+    """`gemm_nt_plan` for `gemm_ws`: its geometry as the tile_config code 100 * MT + 10 * NT (> 0), or the negative RPO_E_*
+    it would return (rpo_gemm_ws_plan).  Nothing is launched."""
+    args = gemm_args(a, _WView(w), out, epilogue, **kw)
+    return int(_lib.load().rpo_gemm_ws_plan(C.byref(args)))
+
+
 def gemm_hilo_ok(M: int, N: int, K: int, dtype: torch.dtype, row_units: Optional[tuple], ln_group: int = 0) -> bool:
     """Would a BIAS_RESID GEMM of these shapes run on a kernel that implements the hi / lo residual stream
     (rpo_gemm_hilo_ok)?"""
