@@ -358,6 +358,33 @@ int rpo_lp_head_fwd_bwd(const float* img_f, const float* w, const float* bias, c
                         const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
                         float* g_w, float* g_bias, int B, int C, int e, float* workspace, void* stream);
 
+/* ---- CLIP ResNet image tower (clip/model.py:10-152, rpo_amd/csrc/conv.hip) ------------------------------------------
+ * Activations are NHWC in the act dtype (`dtype`: RPO_F32 / RPO_BF16 / RPO_F16): row m = (b, y, x), channels contiguous.
+ * Eval-mode BatchNorm is folded into weight and bias by the caller.  Every sum runs in a fixed order (same bits per call).
+ *
+ * rpo_conv2d_nhwc: y[B,H,W,Cout] = relu?(conv(x[B,H,W,Cin], w) + bias [+ resid]), kernel `ksize` 1 or 3 (pad 1), stride 1,
+ *   as an implicit GEMM (k = (tap, channel)); w [Cout][ksize][ksize][Cin] act dtype, bias fp32 [Cout], resid (optional)
+ *   [B,H,W,Cout] act dtype, added in fp32 before the single rounding.  Cin % 16 (f32) / % 32 (16-bit) == 0,
+ *   Cout % 32 == 0, else RPO_E_SHAPE; x, w, y, resid 16-byte aligned (RPO_E_ALIGN).  tile_config: 0 = choose
+ *   (rpo_conv2d_plan: 64x64, the fastest measured), 1 = 64x64, 2 = 128x128, 3 = 128x64 tiles (bit-identical results).  Nothing is launched on an error. */
+int rpo_conv2d_plan(int B, int H, int W, int Cout);
+int rpo_conv2d_nhwc(const void* x, const void* w, const float* bias, const void* resid, void* y, int dtype,
+                    int B, int H, int W, int Cin, int Cout, int ksize, int relu, int tile_config, void* stream);
+/* Stem conv1 (clip/model.py:101): 3x3, stride 2, pad 1 on the fp32 NCHW image [B,3,H,W] -> y [B,H/2,W/2,Cout] NHWC act
+ * dtype; w [Cout][3][3][3] act dtype, bias fp32.  H, W even, Cout % 8 == 0, Cout <= 128, else RPO_E_SHAPE. */
+int rpo_conv_stem(const float* image, const void* w, const float* bias, void* y, int dtype, int B, int H, int W,
+                  int Cout, int relu, void* stream);
+/* AvgPool2d(k) (kernel = stride = k, clip/model.py:22,35,108) on NHWC: y [B,H/k,W/k,C].  H, W multiples of k, C % 8 == 0. */
+int rpo_avgpool_nhwc(const void* x, void* y, int dtype, int B, int H, int W, int C, int k, void* stream);
+/* Attention-pool tokens (clip/model.py:67-69): tokens[B, HW+1, C] = [mean_p x[b,p] | x[b,0..HW)] + pos[HW+1, C] (pos fp32;
+ * the mean in fp32).  C % 8 == 0, HW + 1 <= 256. */
+int rpo_attnpool_tokens(const void* x, const float* pos, void* tokens, int dtype, int B, int HW, int C, void* stream);
+/* The attention pool's one query (x[0], clip/model.py:70-91): out[b, h*64 + d] = softmax_j(scale q_b,h . k_j,h) . v_j,h
+ * over the T = HW + 1 tokens of image b; q fp32 [B][ldq] (after the bias, before the scale), kv [B*T, 2C] act dtype
+ * (k | v), out [B, C] act dtype.  C == 64 * heads, T <= 256. */
+int rpo_attnpool_attn(const float* q, int64_t ldq, const void* kv, void* out, int dtype, int B, int T, int C, int heads,
+                      float scale, void* stream);
+
 /* torch.optim.SGD (dampening 0, no nesterov) on n fp32 scalars (trainers/rpo.py:274,309):
  *   g' = grad_scale * g + wd * p;  buf = first ? g' : momentum * buf + g';  p -= lr * buf
  * grad_scale = 1 / world_size after a sum all-reduce. */

@@ -143,6 +143,13 @@ SIGNATURES = {
     "rpo_lp_head_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "rpo_lp_head_fwd_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                     c_vp, c_vp]),
+    "rpo_conv2d_plan": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "rpo_conv2d_nhwc": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                c_vp]),
+    "rpo_conv_stem": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rpo_avgpool_nhwc": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rpo_attnpool_tokens": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rpo_attnpool_attn": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_sgd_step": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "rpo_sgd_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp]),
     "rpo_convert": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),

@@ -46,6 +46,16 @@ class RPOConfig:
     # RPO
     K: int = 24
     n_cls: int = 19
+    # image tower kind: "vit", or "rn" for CLIP's ModifiedResNet (clip/model.py:94-152).  For "rn", d_v is the ResNet
+    # feature width (rn_width * 32, the attention pool's embed dim), patch = 32 (the tower's total stride: grid is the
+    # attention pool's grid, n_frozen its H*W + 1 tokens, heads_v its heads) and layers_v = 0
+    vision: str = "vit"
+    rn_layers: tuple = ()
+    rn_width: int = 0
+
+    @property
+    def is_rn(self) -> bool:
+        return self.vision == "rn"
 
     @property
     def heads_v(self) -> int:
@@ -92,6 +102,54 @@ def vit_l14(**kw) -> RPOConfig:
                 layers_t=12, embed=768)
     base.update(kw)
     return RPOConfig(**base)
+
+
+def rn_clip(layers=(3, 4, 6, 3), width: int = 64, embed: int = 1024, image_size: int = 224, **kw) -> RPOConfig:
+    """CLIP ResNet (clip/model.py:94-152, built by :412-419): RN50 = (3, 4, 6, 3) / width 64 / embed 1024, RN101 =
+    (3, 4, 23, 3) / 64 / 512; text tower as ViT-B/16's (512 wide, 12 layers) unless given."""
+    name = RN_NAMES.get((tuple(layers), width), f"RN{tuple(layers)}x{width}")
+    base = dict(name=name, vision="rn", rn_layers=tuple(int(l) for l in layers), rn_width=width, d_v=width * 32, patch=32,
+                layers_v=0, image_size=image_size, embed=embed)
+    base.update(kw)
+    return RPOConfig(**base)
+
+
+# (blocks per stage, stem width) -> name (clip/clip.py:30-34 lists these five ResNets)
+RN_NAMES = {((3, 4, 6, 3), 64): "RN50", ((3, 4, 23, 3), 64): "RN101", ((4, 6, 10, 6), 80): "RN50x4",
+            ((6, 8, 18, 8), 96): "RN50x16", ((3, 15, 36, 10), 128): "RN50x64"}
+
+
+def rn_plan(cfg: RPOConfig):
+    """The convolutions of the ResNet tower in execution order (clip/model.py:99-152): one dict per Bottleneck with its
+    input size / channels, planes, stride and whether it has a downsample branch."""
+    w, H = cfg.rn_width, cfg.image_size // 4
+    inpl, blocks = w, []
+    for s, n in enumerate(cfg.rn_layers):
+        planes = w * (1 << s)
+        for i in range(n):
+            stride = 2 if (s > 0 and i == 0) else 1
+            blocks.append(dict(name=f"layer{s + 1}.{i}", H=H, cin=inpl, planes=planes, stride=stride,
+                               down=stride > 1 or inpl != planes * 4))
+            inpl = planes * 4
+            H //= stride
+    return blocks
+
+
+def flops_rn_image(cfg: RPOConfig) -> float:
+    """Algorithmic forward FLOPs per image of the ResNet tower (2 per MAC): the three stem convolutions, every Bottleneck's
+    three convolutions and downsample, and the attention pool (K / V of all H*W + 1 tokens, q of token 0, its scores and
+    weighted sum, c_proj).  Pools, BatchNorm (folded) and ReLU are not counted."""
+    w, R = cfg.rn_width, cfg.image_size
+    h1 = R // 2
+    f = 2.0 * h1 * h1 * 27 * (w // 2) + 2.0 * h1 * h1 * 9 * (w // 2) * (w // 2) + 2.0 * h1 * h1 * 9 * (w // 2) * w
+    for b in rn_plan(cfg):
+        H, Ho, cin, p = b["H"], b["H"] // b["stride"], b["cin"], b["planes"]
+        f += 2.0 * H * H * cin * p + 2.0 * H * H * 9 * p * p + 2.0 * Ho * Ho * p * 4 * p
+        if b["down"]:
+            f += 2.0 * Ho * Ho * cin * 4 * p
+    C, T = cfg.d_v, cfg.n_frozen
+    f += 2.0 * T * C * 2 * C + 2.0 * C * C + 2.0 * 2 * T * C + 2.0 * C * cfg.embed
+    return f
 
 
 # ---------------------------------------------------------------------------

@@ -320,6 +320,9 @@ class CoCoOpCustomCLIP:
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])
+        if cfg.is_rn:
+            raise NotImplementedError(f"CoCoOp on a ResNet ({cfg.name}) is not implemented: its meta-net at vis_dim "
+                                      f"{cfg.embed} has not been built for this engine (ViT backbones only)")
         self.cfg = cfg
         self.engine = eng = make_engine(cfg, state_dict, tokens, torch.device(device), act_dtype, max_batch)
         e, dt = cfg.embed, cfg.d_t

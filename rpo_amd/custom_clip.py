@@ -67,7 +67,11 @@ def init_prompts(state_dict: Dict[str, np.ndarray], K: int, d_t: int, d_v: int):
 
 
 def config_from_state_dict(sd, K: int, n_cls: int, name: Optional[str] = None) -> RPOConfig:
-    """Tower dimensions from a CLIP state dict, the way clip/model.py:403-432 `build_model` infers them."""
+    """Tower dimensions from a CLIP state dict, the way clip/model.py:403-432 `build_model` infers them.  A state dict
+    without `visual.proj` is a ResNet (:404, :412-419): block counts from `visual.layer{1..4}.*`, the stem width from
+    `visual.layer1.0.conv1.weight`, the resolution 32 x the attention pool's grid."""
+    if "visual.proj" not in sd:
+        return _rn_config_from_state_dict(sd, K, n_cls, name)
     d_v = sd["visual.conv1.weight"].shape[0]
     patch = sd["visual.conv1.weight"].shape[-1]
     layers_v = len({k.split(".")[3] for k in sd if k.startswith("visual.transformer.resblocks.")})
@@ -80,6 +84,30 @@ def config_from_state_dict(sd, K: int, n_cls: int, name: Optional[str] = None) -
         name = {(768, 16): "ViT-B/16", (768, 32): "ViT-B/32", (1024, 14): "ViT-L/14"}.get((d_v, patch), f"ViT-{d_v}/{patch}")
     return RPOConfig(name=name, image_size=grid * patch, patch=patch, d_v=d_v, layers_v=layers_v, d_t=d_t,
                      layers_t=layers_t, context=context, vocab=vocab, embed=embed, K=K, n_cls=n_cls)
+
+
+def _rn_config_from_state_dict(sd, K: int, n_cls: int, name: Optional[str]) -> RPOConfig:
+    from .config import rn_clip
+    layers = tuple(len({k.split(".")[2] for k in sd if k.startswith(f"visual.layer{b}.")}) for b in (1, 2, 3, 4))
+    width = sd["visual.layer1.0.conv1.weight"].shape[0]
+    T = sd["visual.attnpool.positional_embedding"].shape[0]
+    grid = round((T - 1) ** 0.5)
+    assert grid * grid + 1 == T, "visual.attnpool.positional_embedding: not grid**2 + 1 rows"
+    embed = sd["text_projection"].shape[1]
+    context, d_t = sd["positional_embedding"].shape
+    vocab = sd["token_embedding.weight"].shape[0]
+    layers_t = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks.")})
+    kw = {} if name is None else dict(name=name)
+    return rn_clip(layers, width, embed, image_size=32 * grid, d_t=d_t, layers_t=layers_t, context=context, vocab=vocab,
+                   K=K, n_cls=n_cls, **kw)
+
+
+def refuse_rn(cfg: RPOConfig, what: str) -> None:
+    """RPO is defined on ViT tokens: the reference's RPO reads conv1 / class_embedding / transformer of a ViT
+    (trainers/rpo.py:52,110-117) and cannot run a ResNet either."""
+    if cfg.is_rn:
+        raise NotImplementedError(f"{what} needs a ViT image tower; {cfg.name} is a ResNet (RPO's prompts are ViT tokens: "
+                                  "use ZeroshotCLIP or CoOp for ResNet backbones)")
 
 
 class CustomCLIP(nn.Module):
@@ -97,6 +125,7 @@ class CustomCLIP(nn.Module):
             device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
         if act_dtype is None:
             act_dtype = torch.bfloat16
+        refuse_rn(cfg, "CustomCLIP (RPO)")
         self.cfg = cfg
         device = torch.device(device)
         if tokens is None:

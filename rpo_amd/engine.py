@@ -33,6 +33,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_LN_BIAS, EPI_LN
 from .config import RPOConfig
 from .engine_coop import CoopEngineMixin
 from .engine_lp import LpEngineMixin
+from .engine_rn import RnEngineMixin
 
 import contextlib
 
@@ -68,7 +69,7 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, LpEngineMixin):
+class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under
@@ -132,7 +133,7 @@ class Engine(CoopEngineMixin, LpEngineMixin):
             self._alloc()
         self.text_cache_ready = False
         self._stats_group = {}          # batch size -> columns per partial LayerNorm statistic (64 or 96)
-        self.img_cls_f = None
+        self.img_cls_f = self.rn_img_f if cfg.is_rn else None     # (the ResNet tower writes its features there)
         self.plain_text_f = None
         self.text_x_final = None
         self._eval_graphs = {}          # batch size -> (captured image tower + head, its static input)
@@ -246,7 +247,9 @@ class Engine(CoopEngineMixin, LpEngineMixin):
 
     def _pack(self, sd, tokens) -> None:
         cfg = self.cfg
-        self.vis = [self._block(sd, f"visual.transformer.resblocks.{l}.", fold=self.fold_ln) for l in range(cfg.layers_v)]
+        # a ResNet image tower (engine_rn.py) has none of the ViT's weights
+        self.vis = [] if cfg.is_rn else [self._block(sd, f"visual.transformer.resblocks.{l}.", fold=self.fold_ln)
+                                         for l in range(cfg.layers_v)]
         self.txt = [self._block(sd, f"transformer.resblocks.{l}.", fold=self.fold_ln) for l in range(cfg.layers_t)]
         # packed twins (rpo_gemm_ws) of every weight a prompt-row GEMM reads: the dX operands of both chains, the text
         # tower's forward weights (its q rows of the in-projection only) and the last image block's (prompt rows only)
@@ -255,19 +258,14 @@ class Engine(CoopEngineMixin, LpEngineMixin):
         for blk, d in [(b, cfg.d_t) for b in self.txt] + ([(self.vis[-1], cfg.d_v)] if self.vis else []):
             for w in (blk.w_in[:d], None if blk.w_in_ln is None else blk.w_in_ln[:d], blk.w_out, blk.w_fc, blk.w_fc_ln, blk.w_proj):
                 self._ws_reg(w)
-        self.kpatch = _round_up(cfg.patch_dim, self.kmult)
-        conv = torch.zeros(cfg.d_v, self.kpatch, device=self.dev)
-        conv[:, :cfg.patch_dim] = self._f32(sd["visual.conv1.weight"]).reshape(cfg.d_v, -1)
-        self.conv_w = self._act(conv)
-        self.cls = self._f32(sd["visual.class_embedding"])
-        self.pos = self._f32(sd["visual.positional_embedding"])
-        self.ln_pre = (self._f32(sd["visual.ln_pre.weight"]), self._f32(sd["visual.ln_pre.bias"]))
-        self.ln_post = (self._f32(sd["visual.ln_post.weight"]), self._f32(sd["visual.ln_post.bias"]))
+        if cfg.is_rn:
+            self._rn_pack(sd)
+        else:
+            self._pack_vit_embed(sd)
         self.ln_final = (self._f32(sd["ln_final.weight"]), self._f32(sd["ln_final.bias"]))
-        vp, tp = self._f32(sd["visual.proj"]), self._f32(sd["text_projection"])      # [d, e]
-        self.img_proj_t, self.img_proj = self._act(vp.t()), self._act(vp)           # fwd W=[e,d]; bwd W=[d,e]
+        tp = self._f32(sd["text_projection"])                                        # [d, e]
         self.text_proj_t, self.text_proj = self._act(tp.t()), self._act(tp)
-        for w in (self.img_proj_t, self.img_proj, self.text_proj_t, self.text_proj):
+        for w in (self.text_proj_t, self.text_proj):
             self._ws_reg(w)
         # small batches (config 1: batch 4): below 1024 image token rows -- B x (N + K) < 1024 -- the WHOLE image forward is a
         # small-M problem with no one-round geometry, so every block's forward weights get a packed twin too
@@ -285,6 +283,22 @@ class Engine(CoopEngineMixin, LpEngineMixin):
         # embedding is added, trainers/coop.py:136-183)
         self.text_tok = self._f32(sd["token_embedding.weight"][tokens][:, :self.Lmax].reshape(cfg.n_cls * self.Lmax, cfg.d_t))
 
+    def _pack_vit_embed(self, sd) -> None:
+        """The ViT's patch embedding, class / positional embeddings, ln_pre / ln_post and visual.proj."""
+        cfg = self.cfg
+        self.kpatch = _round_up(cfg.patch_dim, self.kmult)
+        conv = torch.zeros(cfg.d_v, self.kpatch, device=self.dev)
+        conv[:, :cfg.patch_dim] = self._f32(sd["visual.conv1.weight"]).reshape(cfg.d_v, -1)
+        self.conv_w = self._act(conv)
+        self.cls = self._f32(sd["visual.class_embedding"])
+        self.pos = self._f32(sd["visual.positional_embedding"])
+        self.ln_pre = (self._f32(sd["visual.ln_pre.weight"]), self._f32(sd["visual.ln_pre.bias"]))
+        self.ln_post = (self._f32(sd["visual.ln_post.weight"]), self._f32(sd["visual.ln_post.bias"]))
+        vp = self._f32(sd["visual.proj"])                                            # [d, e]
+        self.img_proj_t, self.img_proj = self._act(vp.t()), self._act(vp)           # fwd W=[e,d]; bwd W=[d,e]
+        for w in (self.img_proj_t, self.img_proj):
+            self._ws_reg(w)
+
     # ------------------------------------------------------------------ workspace
     def _alloc(self) -> None:
         cfg, dev, act = self.cfg, self.dev, self.act
@@ -293,36 +307,39 @@ class Engine(CoopEngineMixin, LpEngineMixin):
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         a = lambda *s: torch.empty(*s, dtype=act, device=dev)
         Lv, Lt = cfg.layers_v, cfg.layers_t
-        self.im2col = a(B * cfg.n_patches, self.kpatch)
-        self.x_pre = f32(R, dv)
-        # Residual stream at the layer boundaries, fp32.  INVARIANT of the hi / lo mode (16-bit modes at batch sizes with a
-        # one-round geometry, the default there): after a forward pass only the PROMPT rows [B*N, B*(N+K)) of x[l] (l >= 1)
-        # and xm[l] hold this pass's values -- the stream of all rows lives in h (hi) + h_lo, updated in place, and the
-        # frozen rows of these tensors keep whatever an earlier call left (advisor, round 3).  Nothing in-tree reads them
-        # outside forward_plain / the sibling trainers (full_last: fp32 for every row); a tool that inspects frozen rows
-        # must run with RPO_NO_HILO=1 (tools/probe_alias_buffers.py does).
-        self.x = [f32(R, dv) for _ in range(Lv + 1)]
-        self.xm = [f32(R, dv) for _ in range(Lv)]
-        self.h = a(R, dv)
-        self.h_lo = a(R, dv)                         # lo half of the residual stream (hi / lo mode: _image_forward)
-        self.ln_stats = f32(R, dv // 64, 2)          # per-row partial LayerNorm statistics of the tensor self.h copies
-        self.qkv = [a(R, 3 * dv) for _ in range(Lv)]
-        self.att = a(R, dv)
-        self.g = a(R, 4 * dv)
-        # saved for the QuickGELU backward, prompt rows only: fp32 pre-activations in the f32 mode, the derivative itself
-        # in the act dtype in the 16-bit modes (rpo_gemm_args.aux_dtype)
         au = f32 if os.environ.get("RPO_AUX_F32") == "1" else a      # A/B switch: fp32 pre-activations in every mode
-        self.u = [au(Rp, 4 * dv) for _ in range(Lv)]
-        self.y_post = a(Rp, dv)
-        self.img_f = f32(Rp, e)
-        # backward temporaries (prompt rows)
-        self.d_img_f = f32(Rp, e)
-        self.d_img_f_a = a(Rp, e)
-        self.dy_v = f32(max(SPLIT_FC, SPLIT_Q, 4), Rp, dv)       # (rpo_gemm_ws splits d c_fc in up to four)
-        self.dxa_v, self.dxb_v = f32(Rp, dv), f32(Rp, dv)
-        self.dxc_v = a(Rp, dv)
-        self.du_v = a(Rp, 4 * dv)
-        self.da_v, self.dq_v = a(Rp, dv), a(Rp, dv)
+        if cfg.is_rn:                                   # the ResNet tower's NHWC buffers (engine_rn.py) instead
+            self._rn_alloc()
+        else:
+            self.im2col = a(B * cfg.n_patches, self.kpatch)
+            self.x_pre = f32(R, dv)
+            # Residual stream at the layer boundaries, fp32.  INVARIANT of the hi / lo mode (16-bit modes at batch sizes with a
+            # one-round geometry, the default there): after a forward pass only the PROMPT rows [B*N, B*(N+K)) of x[l] (l >= 1)
+            # and xm[l] hold this pass's values -- the stream of all rows lives in h (hi) + h_lo, updated in place, and the
+            # frozen rows of these tensors keep whatever an earlier call left (advisor, round 3).  Nothing in-tree reads them
+            # outside forward_plain / the sibling trainers (full_last: fp32 for every row); a tool that inspects frozen rows
+            # must run with RPO_NO_HILO=1 (tools/probe_alias_buffers.py does).
+            self.x = [f32(R, dv) for _ in range(Lv + 1)]
+            self.xm = [f32(R, dv) for _ in range(Lv)]
+            self.h = a(R, dv)
+            self.h_lo = a(R, dv)                         # lo half of the residual stream (hi / lo mode: _image_forward)
+            self.ln_stats = f32(R, dv // 64, 2)          # per-row partial LayerNorm statistics of the tensor self.h copies
+            self.qkv = [a(R, 3 * dv) for _ in range(Lv)]
+            self.att = a(R, dv)
+            self.g = a(R, 4 * dv)
+            # saved for the QuickGELU backward, prompt rows only: fp32 pre-activations in the f32 mode, the derivative itself
+            # in the act dtype in the 16-bit modes (rpo_gemm_args.aux_dtype)
+            self.u = [au(Rp, 4 * dv) for _ in range(Lv)]
+            self.y_post = a(Rp, dv)
+            self.img_f = f32(Rp, e)
+            # backward temporaries (prompt rows)
+            self.d_img_f = f32(Rp, e)
+            self.d_img_f_a = a(Rp, e)
+            self.dy_v = f32(max(SPLIT_FC, SPLIT_Q, 4), Rp, dv)       # (rpo_gemm_ws splits d c_fc in up to four)
+            self.dxa_v, self.dxb_v = f32(Rp, dv), f32(Rp, dv)
+            self.dxc_v = a(Rp, dv)
+            self.du_v = a(Rp, 4 * dv)
+            self.da_v, self.dq_v = a(Rp, dv), a(Rp, dv)
         # text tower (prompt rows per step)
         Rt = cfg.n_cls * K
         self.Rt = Rt
@@ -826,6 +843,7 @@ class Engine(CoopEngineMixin, LpEngineMixin):
         """logits[B, n_cls] (trainers/rpo.py:232).  The image tower + head of a batch size are captured in a HIP graph
         on first use and replayed afterwards: launched eagerly the ~100 kernels of this path are launch-bound
         (round 1: 6.4 ms per 100 images)."""
+        self._refuse_rn("forward_eval")
         B = self._check(image)
         main = torch.cuda.current_stream()
         # text features depend on the prompts only: in evaluation they are computed once, not per batch
@@ -900,12 +918,15 @@ class Engine(CoopEngineMixin, LpEngineMixin):
             ops.layernorm_fwd(eot, self.ln_final[0], self.ln_final[1], y)
             self.plain_text_f = torch.empty(n, e, dtype=torch.float32, device=self.dev)
             ops.gemm_nt(y, self.text_proj_t, self.plain_text_f, EPI_NONE)
-        self._image_forward(image, train=False, full_last=True)
-        cls_rows = self.x[-1][:B * N].view(B, N, dv)[:, 0, :]                  # [B, dv], row stride N * dv
-        ops.layernorm_fwd(cls_rows, self.ln_post[0], self.ln_post[1], self.y_post[:B])
-        if self.img_cls_f is None:
-            self.img_cls_f = torch.empty(self.max_batch, e, dtype=torch.float32, device=self.dev)
-        ops.gemm_nt(self.y_post[:B], self.img_proj_t, self.img_cls_f[:B], EPI_NONE)
+        if cfg.is_rn:
+            self.rn_forward(image)                                             # -> img_cls_f[:B] (engine_rn.py)
+        else:
+            self._image_forward(image, train=False, full_last=True)
+            cls_rows = self.x[-1][:B * N].view(B, N, dv)[:, 0, :]              # [B, dv], row stride N * dv
+            ops.layernorm_fwd(cls_rows, self.ln_post[0], self.ln_post[1], self.y_post[:B])
+            if self.img_cls_f is None:
+                self.img_cls_f = torch.empty(self.max_batch, e, dtype=torch.float32, device=self.dev)
+            ops.gemm_nt(self.y_post[:B], self.img_proj_t, self.img_cls_f[:B], EPI_NONE)
         ops.head_fwd_bwd(self.img_cls_f[:B].view(B, 1, e), self.plain_text_f.view(n, 1, e), None, self.logit_scale_exp,
                          self.logits[:B], None, None, None, self.head_ws)
         return self.logits[:B]
@@ -913,6 +934,7 @@ class Engine(CoopEngineMixin, LpEngineMixin):
     def forward_backward(self, image: torch.Tensor, label: torch.Tensor) -> None:
         """Enqueue loss + both prompt gradients (trainers/rpo.py:229-230, :308).  Results land in
         self.loss, self.logits, self.grads (= [g_text | g_img]).  Capturable in a HIP graph."""
+        self._refuse_rn("forward_backward")
         B = self._check(image)
         self.text_f_version = -1
         assert label.dtype == torch.int64 and label.shape == (B,)
@@ -940,6 +962,10 @@ class Engine(CoopEngineMixin, LpEngineMixin):
         ops.head_fwd_bwd(self.img_f[:B * K].view(B, K, e), self.text_f.view(n, K, e), label, self.logit_scale_exp,
                          self.logits[:B], self.loss, self.d_img_f[:B * K].view(B, K, e),
                          self.d_text_f.view(n, K, e), self.head_ws, **self._head_act(B))
+
+    def _refuse_rn(self, what: str) -> None:
+        from .custom_clip import refuse_rn
+        refuse_rn(self.cfg, f"Engine.{what} (the RPO step)")
 
     def _check(self, image: torch.Tensor) -> int:
         cfg = self.cfg

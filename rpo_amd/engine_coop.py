@@ -198,6 +198,8 @@ class CoopEngineMixin:
         B = image.shape[0]
         assert image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and B <= self.max_batch
         assert image.device == self.dev and torch.cuda.current_device() == self.dev.index
+        if cfg.is_rn:
+            return self.rn_forward(image)                                      # -> img_cls_f[:B] (engine_rn.py)
         N, dv = cfg.n_frozen, cfg.d_v
         self._image_forward(image, train=False, full_last=True)
         cls_rows = self.x[-1][:B * N].view(B, N, dv)[:, 0, :]

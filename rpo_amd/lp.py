@@ -60,6 +60,9 @@ class LPCustomCLIP:
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])     # one (unused) prompt row per image
+        if cfg.is_rn:
+            raise NotImplementedError(f"LP on a ResNet ({cfg.name}) is not implemented: the probe at embed {cfg.embed} has not "
+                                      f"been built for this engine (ViT backbones only)")
         if cfg.embed != cfg.d_t:
             raise ValueError(f"the reference's lp_layer is nn.Linear(d_t, d_t) applied to the image feature (:69-72): it "
                              f"needs embed == d_t, this model has embed {cfg.embed}, d_t {cfg.d_t}")

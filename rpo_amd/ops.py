@@ -569,3 +569,71 @@ def probe_peaks(device: torch.device, which: int = 0, copy: bool = True) -> dict
     torch.cuda.synchronize(device)
     return {"mfma_tflops": flops.value / (ev[0].elapsed_time(ev[1]) * 1e-3) / 1e12,
             "copy_gbs": 2.0 * n * reps / (ev[2].elapsed_time(ev[3]) * 1e-3) / 1e9}
+
+
+# ---- CLIP ResNet image tower (include/rpo_amd.h, csrc/conv.hip) --------------------------------------------------------
+
+def _nhwc(t: torch.Tensor, what: str) -> None:
+    assert t.is_cuda and t.is_contiguous() and t.dim() == 4, f"{what}: contiguous [B, H, W, C] device tensor"
+
+
+def conv2d_nhwc(x, w, bias, y, resid=None, relu: bool = True, tile_config: int = 0):
+    """y = relu?(conv(x, w) + bias [+ resid]) (include/rpo_amd.h rpo_conv2d_nhwc): x [B,H,W,Cin], w [Cout,k,k,Cin] act dtype,
+    bias fp32 [Cout], resid / y [B,H,W,Cout]."""
+    _nhwc(x, "x"); _nhwc(y, "y")
+    B, H, W, Cin = x.shape
+    Cout, kh, kw, cin_w = w.shape
+    assert kh == kw and cin_w == Cin and w.is_contiguous() and w.dtype == x.dtype == y.dtype
+    assert tuple(y.shape) == (B, H, W, Cout) and bias.dtype == torch.float32 and bias.numel() == Cout
+    if resid is not None:
+        _nhwc(resid, "resid")
+        assert resid.shape == y.shape and resid.dtype == y.dtype
+    check(_lib.load().rpo_conv2d_nhwc(x.data_ptr(), w.data_ptr(), bias.data_ptr(), _p(resid), y.data_ptr(),
+                                      dtype_code(x.dtype), B, H, W, Cin, Cout, kh, int(relu), tile_config, _stream()),
+          "rpo_conv2d_nhwc")
+    return y
+
+
+def conv_stem(image, w, bias, y, relu: bool = True):
+    """Stem conv1 (rpo_conv_stem): fp32 NCHW image [B,3,H,W] -> y [B,H/2,W/2,Cout] NHWC, w [Cout,3,3,3] act dtype."""
+    assert image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 4 and image.shape[1] == 3
+    _nhwc(y, "y")
+    B, _, H, W = image.shape
+    Cout = w.shape[0]
+    assert tuple(w.shape) == (Cout, 3, 3, 3) and w.is_contiguous() and w.dtype == y.dtype
+    assert tuple(y.shape) == (B, H // 2, W // 2, Cout) and bias.dtype == torch.float32 and bias.numel() == Cout
+    check(_lib.load().rpo_conv_stem(image.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), dtype_code(y.dtype),
+                                    B, H, W, Cout, int(relu), _stream()), "rpo_conv_stem")
+    return y
+
+
+def avgpool_nhwc(x, y, k: int):
+    """AvgPool2d(k) on NHWC (rpo_avgpool_nhwc)."""
+    _nhwc(x, "x"); _nhwc(y, "y")
+    B, H, W, C = x.shape
+    assert tuple(y.shape) == (B, H // k, W // k, C) and y.dtype == x.dtype
+    check(_lib.load().rpo_avgpool_nhwc(x.data_ptr(), y.data_ptr(), dtype_code(x.dtype), B, H, W, C, k, _stream()),
+          "rpo_avgpool_nhwc")
+    return y
+
+
+def attnpool_tokens(x, pos, tokens):
+    """[mean | pixels] + positional embedding (rpo_attnpool_tokens): x [B,H,W,C], pos fp32 [HW+1, C], tokens [B, HW+1, C]."""
+    _nhwc(x, "x")
+    B, H, W, C = x.shape
+    assert pos.dtype == torch.float32 and pos.is_contiguous() and tuple(pos.shape) == (H * W + 1, C)
+    assert tokens.is_contiguous() and tuple(tokens.shape) == (B, H * W + 1, C) and tokens.dtype == x.dtype
+    check(_lib.load().rpo_attnpool_tokens(x.data_ptr(), pos.data_ptr(), tokens.data_ptr(), dtype_code(x.dtype), B, H * W, C,
+                                          _stream()), "rpo_attnpool_tokens")
+    return tokens
+
+
+def attnpool_attn(q, kv, out, heads: int, scale: float):
+    """The attention pool's query (rpo_attnpool_attn): q fp32 [B, C] (row stride free), kv [B, T, 2C], out [B, C]."""
+    B, T, C2 = kv.shape
+    C = C2 // 2
+    assert q.dtype == torch.float32 and q.dim() == 2 and q.stride(1) == 1 and tuple(q.shape) == (B, C)
+    assert kv.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (B, C) and out.dtype == kv.dtype
+    check(_lib.load().rpo_attnpool_attn(q.data_ptr(), q.stride(0), kv.data_ptr(), out.data_ptr(), dtype_code(kv.dtype), B, T,
+                                        C, heads, scale, _stream()), "rpo_attnpool_attn")
+    return out

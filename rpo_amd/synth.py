@@ -122,6 +122,129 @@ def clip_state_dict(cfg: RPOConfig, seed: int = 0, token_rows: Iterable[int] | N
     return sd
 
 
+def _text_tower(cfg: RPOConfig, seed: int, token_rows, logit_scale: float) -> Dict[str, np.ndarray]:
+    """The text half of clip_state_dict (same names, same streams: the same bits as there)."""
+    full = clip_state_dict(cfg.with_(vision="vit", layers_v=0, d_v=64, patch=32, rn_layers=(), rn_width=0), seed,
+                           token_rows, logit_scale)
+    return {k: v for k, v in full.items() if not k.startswith("visual.")}
+
+
+def _bn(seed: int, prefix: str, c: int, gamma_mean: float, out: Dict[str, np.ndarray]) -> None:
+    """Eval-mode BatchNorm2d with NON-trivial statistics: gamma != 1 (and != 0 for bn3, unlike clip/model.py:315-318,
+    which would hide every residual branch's conv3), beta and running mean != 0, running var != 1, so the fold is
+    exercised."""
+    out[prefix + "weight"] = normal(seed, prefix + "weight", (c,), 0.1 * gamma_mean, gamma_mean)
+    out[prefix + "bias"] = normal(seed, prefix + "bias", (c,), 0.1)
+    out[prefix + "running_mean"] = normal(seed, prefix + "running_mean", (c,), 0.1)
+    v = normal(seed, prefix + "running_var", (c,), 0.25, 1.0)
+    out[prefix + "running_var"] = np.abs(v).astype(np.float32) + np.float32(0.25)
+    out[prefix + "num_batches_tracked"] = np.array(0, dtype=np.int64)
+
+
+def _conv(seed: int, name: str, cout: int, cin: int, k: int, out: Dict[str, np.ndarray]) -> None:
+    out[name] = normal(seed, name, (cout, cin, k, k), (2.0 / (cin * k * k)) ** 0.5)     # He init: ReLU keeps the scale
+
+
+def rn_clip_state_dict(cfg: RPOConfig, seed: int = 0, token_rows: Iterable[int] | None = None,
+                       logit_scale: float = math.log(100.0), check: bool = True) -> Dict[str, np.ndarray]:
+    """fp32 numpy state dict of a CLIP ResNet (cfg.is_rn) with the reference key names (clip/model.py:10-150, 243-300):
+    `load_state_dict(strict=True)` into the reference's CLIP(..., vision_layers=<tuple>, ...) succeeds.  Text tower as
+    clip_state_dict (same streams, same bits); every visual tensor from its own Philox stream.  Residual-branch BN
+    gammas are drawn around 0.5 and the others around 1, so activations stay O(1) through the 16 .. 33 blocks.
+    check: run the tower once on the CPU (fp32, one image) and assert that the activation RMS after the stem and after
+    each stage lies in [0.05, 20]; the figures are printed."""
+    assert cfg.is_rn
+    sd = _text_tower(cfg, seed, token_rows, logit_scale)
+    w = cfg.rn_width
+    _conv(seed, "visual.conv1.weight", w // 2, 3, 3, sd)
+    _bn(seed, "visual.bn1.", w // 2, 1.0, sd)
+    _conv(seed, "visual.conv2.weight", w // 2, w // 2, 3, sd)
+    _bn(seed, "visual.bn2.", w // 2, 1.0, sd)
+    _conv(seed, "visual.conv3.weight", w, w // 2, 3, sd)
+    _bn(seed, "visual.bn3.", w, 1.0, sd)
+    from .config import rn_plan
+    for b in rn_plan(cfg):
+        p, cin, pl = f"visual.{b['name']}.", b["cin"], b["planes"]
+        _conv(seed, p + "conv1.weight", pl, cin, 1, sd)
+        _bn(seed, p + "bn1.", pl, 1.0, sd)
+        _conv(seed, p + "conv2.weight", pl, pl, 3, sd)
+        _bn(seed, p + "bn2.", pl, 1.0, sd)
+        _conv(seed, p + "conv3.weight", 4 * pl, pl, 1, sd)
+        _bn(seed, p + "bn3.", 4 * pl, 0.5, sd)
+        if b["down"]:
+            _conv(seed, p + "downsample.0.weight", 4 * pl, cin, 1, sd)
+            _bn(seed, p + "downsample.1.", 4 * pl, 1.0, sd)
+    C, T = cfg.d_v, cfg.n_frozen
+    a = "visual.attnpool."
+    sd[a + "positional_embedding"] = normal(seed, a + "positional_embedding", (T, C), C ** -0.5)
+    std = C ** -0.5                                                   # clip/model.py:289-294
+    for nm in ("q_proj", "k_proj", "v_proj"):
+        sd[a + nm + ".weight"] = normal(seed, a + nm + ".weight", (C, C), std)
+        sd[a + nm + ".bias"] = normal(seed, a + nm + ".bias", (C,), 0.02)
+    sd[a + "c_proj.weight"] = normal(seed, a + "c_proj.weight", (cfg.embed, C), std)
+    sd[a + "c_proj.bias"] = normal(seed, a + "c_proj.bias", (cfg.embed,), 0.02)
+    if check:
+        import torch
+        img = torch.from_numpy(images(cfg, 1, seed=seed + 17))
+        stats = {}
+        rn_tower_reference(sd, cfg, img, torch.float32, stats)
+        print("rn_clip_state_dict activation RMS: " + ", ".join(f"{k} {v:.3f}" for k, v in stats.items()))
+        bad = {k: v for k, v in stats.items() if not 0.05 <= v <= 20.0}
+        assert not bad, f"activation RMS outside [0.05, 20]: {bad}"
+    return sd
+
+
+def rn_tower_reference(sd: Dict[str, np.ndarray], cfg: RPOConfig, image, dtype, stats: Optional[dict] = None):
+    """A functional torch restatement of ModifiedResNet.forward (clip/model.py:10-152) in eval mode, NCHW, in `dtype` on
+    the image's device: the init check above, the float64 CPU reference of the tests and the bench tool's comparator.
+    Not on the product path.  stats: if given, receives the activation RMS after the stem and each stage."""
+    import torch
+    import torch.nn.functional as F
+    dev = image.device
+    t = lambda k: torch.as_tensor(np.asarray(sd[k]), device=dev).to(dtype)
+
+    def cbr(x, conv, bn, relu=True, pad=0):
+        y = F.conv2d(x, t(conv), padding=pad)
+        y = F.batch_norm(y, t(bn + "running_mean"), t(bn + "running_var"), t(bn + "weight"), t(bn + "bias"), False, 0.0,
+                         1e-5)
+        return F.relu(y) if relu else y
+
+    x = image.to(dtype)
+    x = F.relu(F.batch_norm(F.conv2d(x, t("visual.conv1.weight"), stride=2, padding=1), t("visual.bn1.running_mean"),
+                            t("visual.bn1.running_var"), t("visual.bn1.weight"), t("visual.bn1.bias"), False, 0.0, 1e-5))
+    x = cbr(x, "visual.conv2.weight", "visual.bn2.", pad=1)
+    x = cbr(x, "visual.conv3.weight", "visual.bn3.", pad=1)
+    x = F.avg_pool2d(x, 2)
+    if stats is not None:
+        stats["stem"] = float(x.float().pow(2).mean().sqrt())
+    from .config import rn_plan
+    for b in rn_plan(cfg):
+        p = f"visual.{b['name']}."
+        out = cbr(x, p + "conv1.weight", p + "bn1.")
+        out = cbr(out, p + "conv2.weight", p + "bn2.", pad=1)
+        if b["stride"] > 1:
+            out = F.avg_pool2d(out, b["stride"])
+        out = cbr(out, p + "conv3.weight", p + "bn3.", relu=False)
+        idn = x
+        if b["down"]:
+            xd = F.avg_pool2d(x, b["stride"]) if b["stride"] > 1 else x
+            idn = cbr(xd, p + "downsample.0.weight", p + "downsample.1.", relu=False)
+        x = F.relu(out + idn)
+        if stats is not None:
+            stats[b["name"].split(".")[0]] = float(x.float().pow(2).mean().sqrt())
+    a = "visual.attnpool."
+    B, C, H, W = x.shape
+    x = x.reshape(B, C, H * W).permute(2, 0, 1)
+    x = torch.cat([x.mean(dim=0, keepdim=True), x], dim=0) + t(a + "positional_embedding")[:, None, :]
+    x, _ = F.multi_head_attention_forward(
+        query=x[:1], key=x, value=x, embed_dim_to_check=C, num_heads=C // 64, q_proj_weight=t(a + "q_proj.weight"),
+        k_proj_weight=t(a + "k_proj.weight"), v_proj_weight=t(a + "v_proj.weight"), in_proj_weight=None,
+        in_proj_bias=torch.cat([t(a + "q_proj.bias"), t(a + "k_proj.bias"), t(a + "v_proj.bias")]), bias_k=None,
+        bias_v=None, add_zero_attn=False, dropout_p=0.0, out_proj_weight=t(a + "c_proj.weight"),
+        out_proj_bias=t(a + "c_proj.bias"), use_separate_proj_weight=True, training=False, need_weights=False)
+    return x[0]
+
+
 def clip_state_dict_shared(cfg: RPOConfig, seed: int, token_rows, path: str, writer: bool, barrier) -> Dict[str, np.ndarray]:
     """One generation per NODE instead of one per rank: the local writer rank generates the state dict and leaves it in
     `path` as one flat fp32 file + a JSON index (written to a temporary name and renamed, so a reader never sees a

@@ -59,6 +59,8 @@ class RPO:
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",
                  act_dtype: torch.dtype = torch.bfloat16, batch_size: int = 4, num_batches: int = 1,
                  use_graph: bool = True, sync: Optional[GradSync] = None, prompts=None, amp: bool = False):
+        from .custom_clip import refuse_rn
+        refuse_rn(cfg, "RPO")
         self.cfg = cfg
         # PREC "amp" (trainers/rpo.py:298-304): what is left of GradScaler when gradients are fp32 -- a step whose
         # gradient holds Inf / NaN is skipped on every rank (the flag is computed after the all-reduce)

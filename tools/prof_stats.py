@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel summary (count / total / avg / min / max, % of GPU kernel time) from a rocprofv3
 rocpd database (`rocprofv3 --kernel-trace -d DIR -o NAME` writes NAME_results.db).
-Usage: python tools/prof_stats.py path/to/x_results.db [top_n]"""
+Usage: python tools/prof_stats.py path/to/x_results.db [top_n] [--since SUBSTRING]
+--since: only the dispatches from the first kernel whose name contains SUBSTRING on (e.g. the first launch of a forward,
+leaving out the set-up work of the process)."""
 import re
 import sqlite3
 import sys
@@ -9,10 +11,20 @@ import sys
 
 def main():
     db = sys.argv[1]
-    top = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+    args = [a for a in sys.argv[2:]]
+    since = None
+    if "--since" in args:
+        i = args.index("--since")
+        since = args[i + 1]
+        del args[i:i + 2]
+    top = int(args[0]) if args else 40
     cur = sqlite3.connect(db).cursor()
+    where = ""
+    if since is not None:
+        t0 = cur.execute("select min(start) from kernels where name like ?", (f"%{since}%",)).fetchone()[0]
+        where = f" where start >= {int(t0)}"
     rows = cur.execute("select name, count(*), sum(end-start)/1e3, avg(end-start)/1e3, min(end-start)/1e3, "
-                       "max(end-start)/1e3 from kernels group by name order by 3 desc").fetchall()
+                       f"max(end-start)/1e3 from kernels{where} group by name order by 3 desc").fetchall()
     tot = sum(r[2] for r in rows)
     print(f"# {db}: {sum(r[1] for r in rows)} dispatches, {tot / 1e3:.3f} ms of kernel time")
     print(f"{'kernel':92s} {'calls':>6s} {'total_us':>11s} {'avg_us':>9s} {'min_us':>9s} {'max_us':>9s} {'%':>6s}")
