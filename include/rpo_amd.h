@@ -358,6 +358,18 @@ int rpo_lp_head_fwd_bwd(const float* img_f, const float* w, const float* bias, c
                         const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
                         float* g_w, float* g_bias, int B, int C, int e, float* workspace, void* stream);
 
+/* Classification evaluator (Dassl's `Classification.process`, and `compute_accuracy` of the CoOp / LP steps), accumulating
+ * on the device: pred[b] = logits[b].max()'s index as torch computes it on the CPU for fp32 -- the FIRST index of the row
+ * maximum, a row holding NaN predicts its first NaN, ties (+inf included, all -inf too) take the lowest index.
+ *   counts[0] += #(pred == label), counts[1] += B, cmat[label][pred] += 1 (row = true class)
+ * logits [B, C] fp32 with row stride ldl >= C; label int64 [B]; counts int64 [2]; cmat int32 [C * C] or NULL; pred int32
+ * [B] or NULL (overwritten, not accumulated); all device memory.  counts and cmat ACCUMULATE across calls: the caller
+ * zeroes them once and reads them back once.  A label outside [0, C) counts in the total, is never correct, writes no
+ * cmat cell and reads nothing out of bounds.  Integer sums only: every order gives the same bits.  1 <= B, C <= 65536,
+ * else RPO_E_SHAPE; counts 8-byte aligned.  One launch on `stream`, no allocation, capturable in a HIP graph. */
+int rpo_eval_accumulate(const float* logits, int64_t ldl, const int64_t* label, int B, int C, int64_t* counts,
+                        int32_t* cmat, int32_t* pred, void* stream);
+
 /* ---- CLIP ResNet image tower (clip/model.py:10-152, rpo_amd/csrc/conv.hip) ------------------------------------------
  * Activations are NHWC in the act dtype (`dtype`: RPO_F32 / RPO_BF16 / RPO_F16): row m = (b, y, x), channels contiguous.
  * Eval-mode BatchNorm is folded into weight and bias by the caller.  Every sum runs in a fixed order (same bits per call).

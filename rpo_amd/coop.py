@@ -34,6 +34,7 @@ from . import ops
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .engine import Engine, make_engine
+from .loop import LoopMixin
 from .trainer import OptimConfig, load_checkpoint_file, lr_at_epoch, write_checkpoint
 
 
@@ -117,10 +118,12 @@ class CoOpCustomCLIP:
             return eng.coop_forward_backward(image, None)
 
 
-class CoOp:
+class CoOp(LoopMixin):
     """The trainer's step (trainers/coop.py:258-281): forward -> cross-entropy -> zero_grad -> backward -> SGD step on
     `ctx`, returning {"loss", "acc"}; per-epoch LR update.  Optimiser hyper-parameters as for RPO (Dassl defaults are
     un-vendored, hence explicit: OptimConfig)."""
+
+    _reports_acc = True              # forward_backward reports "acc": run_epoch sums it on the device
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int = 16,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",
@@ -364,6 +367,8 @@ class CoCoOpCustomCLIP:
 class CoCoOp(CoOp):
     """The trainer's step (trainers/cocoop.py:255-275): loss = model(image, label) -> zero_grad -> backward -> SGD step
     on ctx and the meta-net; returns {"loss"} (no accuracy: the model returns the loss itself in training mode)."""
+
+    _reports_acc = False
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int = 4,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",

@@ -188,10 +188,14 @@ class CustomCLIP(nn.Module):
             label = label.to(device=self.engine.dev, dtype=torch.int64)
             tp, ip = self.prompt_learner()
             return _StepFunction.apply(tp, ip, self.engine, image, label)
+        return self.eval_logits(image).clone()
+
+    def eval_logits(self, image: torch.Tensor) -> torch.Tensor:
+        """The eval forward's logits as the engine's own buffer (valid until the next forward); `forward` clones it."""
         with torch.no_grad():
             # prompts may have been edited through the nn.Parameter views: a cheap version key
             ver = (self.prompt_learner.text_prompt._version, self.prompt_learner.img_prompt._version)
             if ver != getattr(self, "_seen_version", None):
                 self.engine.params_version += 1
                 self._seen_version = ver
-            return self.engine.forward_eval(image).clone()
+            return self.engine.forward_eval(image)

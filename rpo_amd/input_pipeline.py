@@ -210,6 +210,227 @@ class DeviceTransform:
         slot["done"].record(stream)
         return out
 
+    def _ksize(self, in_size: int, out_size: int) -> int:
+        key = (in_size, out_size)
+        k = self._ksize_cache.get(key)
+        if k is None:
+            k = self._ksize_cache[key] = self.lib.rpo_preprocess_ksize(in_size, out_size)
+        return k
+
+    def from_set(self, image_set: "DeviceImageSet", indices: Sequence[int],
+                 plans: Optional[Sequence[SamplePlan]] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The same transform for images of a `DeviceImageSet`: the pixels are already on the device, so only the
+        descriptors travel (a pinned slot pair of `desc_bytes` each).  `plan()` is called per image in batch order, as
+        `__call__` does, so a seeded run draws the same crops.  Spilled images of the batch are staged into the set's
+        tail behind the resident pixels and the whole batch is one `rpo_preprocess_batch` launch."""
+        B, S = len(indices), self.size
+        if not 0 < B <= self.max_batch:
+            raise ValueError(f"batch of {B} images, transform built for 1..{self.max_batch}")
+        if image_set.dev != self.dev:
+            raise ValueError(f"the image set lives on {image_set.dev}, the transform on {self.dev}")
+        if getattr(self, "dslots", None) is None:
+            self.dslots = [{"host": torch.empty(self.desc_bytes, dtype=torch.uint8).pin_memory(),
+                            "dev": torch.empty(self.desc_bytes, dtype=torch.uint8, device=self.dev),
+                            "ws": None, "done": None} for _ in range(2)]
+            self.dturn = 0
+            self._ksize_cache = {}
+        indices = [int(i) for i in indices]
+        if plans is None:
+            plans = [self.plan(*image_set.sizes[i]) for i in indices]
+        slot = self.dslots[self.dturn]
+        if slot["done"] is not None:
+            slot["done"].synchronize()          # the descriptors of two calls ago have been read
+        stream = torch.cuda.current_stream(self.dev)
+        turn = self.dturn
+        self.dturn ^= 1
+        offsets = image_set.stage_spilled(indices, turn, stream)
+        descs = (_lib.ImageDesc * B)()
+        max_rows, kmax = 1, 1
+        for b, (i, pl) in enumerate(zip(indices, plans)):
+            H, W = image_set.sizes[i]
+            top, left, ch, cw = pl.crop
+            d = descs[b]
+            d.src_offset, d.width, d.height = offsets[b], W, H
+            d.crop_x, d.crop_y, d.crop_w, d.crop_h = left, top, cw, ch
+            d.resize_w, d.resize_h = pl.resize
+            d.win_x, d.win_y = pl.window
+            d.flip = int(pl.flip)
+            max_rows = max(max_rows, ch)
+            kmax = max(kmax, self._ksize(cw, pl.resize[0]), self._ksize(ch, pl.resize[1]))
+        nbytes = ctypes.sizeof(descs)
+        ctypes.memmove(slot["host"].data_ptr(), descs, nbytes)
+        need = self.lib.rpo_preprocess_workspace_bytes(B, S, max_rows, kmax)
+        if slot["ws"] is None or slot["ws"].numel() < need:
+            slot["ws"] = torch.empty(int(need * 1.25) + 1024, dtype=torch.uint8, device=self.dev)
+        if out is None:
+            out = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.dev)
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, S, S)
+        slot["dev"][:nbytes].copy_(slot["host"][:nbytes], non_blocking=True)
+        check(self.lib.rpo_preprocess_batch(image_set.buffer.data_ptr(), image_set.buffer.numel(),
+                                            ctypes.addressof(descs), slot["dev"].data_ptr(), B, S, max_rows, kmax,
+                                            ctypes.addressof(self.mean), ctypes.addressof(self.std),
+                                            out.data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel(),
+                                            stream.cuda_stream), "rpo_preprocess_batch")
+        slot["done"] = torch.cuda.Event()
+        slot["done"].record(stream)
+        image_set.tail_read(turn, slot["done"])
+        return out
+
+
+# ---- a few-shot set that lives on the device ------------------------------------------------------------------
+
+def _align16(n: int) -> int:
+    return (n + 15) // 16 * 16
+
+
+@dataclass
+class PackingPlan:
+    """Where every image of a set goes: `offsets[i]` = byte offset in the packed buffer, or -1 for an image that
+    stays on the host ("spilled"); `resident_bytes` = the packed pixels; `tail_bytes` = one of the two staging areas
+    behind them, large enough for the spilled images of any batch of up to `max_batch` images."""
+    offsets: List[int]
+    resident_bytes: int
+    tail_bytes: int
+
+    @property
+    def spilled(self) -> List[int]:
+        return [i for i, o in enumerate(self.offsets) if o < 0]
+
+
+def plan_packing(sizes: Sequence[Tuple[int, int]], budget_bytes: Optional[int] = None,
+                 max_batch: int = 128) -> PackingPlan:
+    """Pure host function.  Images are packed in order at 16-byte aligned offsets (as the staging path packs a batch);
+    an image that would take the resident pixels beyond `budget_bytes` is spilled, later smaller ones may still fit.
+    Offsets are Python ints: a set beyond 4 GiB is addressed through `rpo_image_desc.src_offset` (64 bit)."""
+    offsets, off, spilled = [], 0, []
+    for (H, W) in sizes:
+        if H <= 0 or W <= 0:
+            raise ValueError("empty image")
+        n = _align16(int(H) * int(W) * 3)
+        if budget_bytes is not None and off + n > budget_bytes:
+            offsets.append(-1)
+            spilled.append(n)
+        else:
+            offsets.append(off)
+            off += n
+    tail = sum(sorted(spilled, reverse=True)[:max_batch])
+    return PackingPlan(offsets, off, tail)
+
+
+class DeviceImageSet:
+    """Decoded uint8 [H, W, 3] images of arbitrary sizes, uploaded once into one packed device buffer, and their
+    labels (host list + one int64 device tensor).  `DeviceTransform.from_set(set, indices)` then reads the pixels where
+    they are.  Images beyond `budget_bytes` stay on the host and are staged per batch into the buffer's tail:
+
+        buffer = [ resident pixels | tail slot 0 | tail slot 1 ]
+
+    The two tail slots alternate like the staging slots of `DeviceTransform`; a slot is refilled only after the event
+    recorded behind the kernels that read it (`tail_read`) has completed."""
+
+    CHUNK = 64 << 20                               # pinned upload chunk
+
+    def __init__(self, images: Sequence[np.ndarray], labels: Sequence[int], device, budget_bytes: Optional[int] = None,
+                 n_cls: Optional[int] = None, max_batch: int = 128):
+        if len(images) != len(labels):
+            raise ValueError(f"{len(images)} images, {len(labels)} labels")
+        for im in images:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("images must be uint8 arrays of shape [H, W, 3] (decoded RGB)")
+        self.dev = torch.device(device)
+        if self.dev.type == "cuda" and self.dev.index is None:
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        self.labels = [int(y) for y in labels]
+        self.plan = plan_packing(self.sizes, budget_bytes, max_batch)
+        if n_cls is not None:
+            self.check_labels(n_cls)
+        p = self.plan
+        self.host_images = {i: np.ascontiguousarray(images[i]) for i in p.spilled}
+        self.buffer = torch.empty(max(16, p.resident_bytes + 2 * p.tail_bytes), dtype=torch.uint8, device=self.dev)
+        self.labels_dev = torch.tensor(self.labels, dtype=torch.int64, device=self.dev)
+        self._tail = None                          # pinned host mirrors of the two tail slots + their events
+        self._upload(images)
+
+    def __len__(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def resident_bytes(self) -> int:
+        return self.plan.resident_bytes
+
+    def check_labels(self, n_cls: int) -> None:
+        """F.cross_entropy raises on an out-of-range target; the head kernels cannot: checked once per set, where
+        `parse_batch_train` checks once per batch."""
+        if not self.labels:
+            return
+        lo, hi = min(self.labels), max(self.labels)
+        if lo < 0 or hi >= n_cls:
+            raise IndexError(f"Target {hi if hi >= n_cls else lo} is out of bounds "
+                             f"(n_cls = {n_cls}; labels must be renumbered after the base/new split)")
+
+    def _upload(self, images) -> None:
+        p = self.plan
+        if p.resident_bytes == 0:
+            return
+        cap = min(self.CHUNK, p.resident_bytes)
+        cap = max(cap, max((_align16(h * w * 3) for (h, w), o in zip(self.sizes, p.offsets) if o >= 0), default=16))
+        pinned = torch.empty(cap, dtype=torch.uint8).pin_memory()
+        hv = pinned.numpy()
+        start = fill = 0                           # the chunk holds buffer[start : start + fill]
+
+        def flush():
+            nonlocal start, fill
+            if fill:
+                self.buffer[start:start + fill].copy_(pinned[:fill], non_blocking=True)
+                torch.cuda.current_stream(self.dev).synchronize()     # the chunk is reused
+            start, fill = start + fill, 0
+
+        with torch.cuda.device(self.dev):
+            for im, off in zip(images, p.offsets):
+                if off < 0:
+                    continue
+                n = im.size
+                assert off == start + fill
+                if fill + _align16(n) > cap:
+                    flush()
+                hv[fill:fill + n] = np.ascontiguousarray(im).reshape(-1)
+                fill += _align16(n)
+            flush()
+
+    def stage_spilled(self, indices: Sequence[int], turn: int, stream) -> List[int]:
+        """Byte offsets in `buffer` of the images `indices`, after copying the spilled ones among them into tail slot
+        `turn` on `stream`."""
+        p = self.plan
+        offs = [p.offsets[i] for i in indices]
+        if all(o >= 0 for o in offs):
+            return offs
+        if self._tail is None:
+            self._tail = [{"host": torch.empty(p.tail_bytes, dtype=torch.uint8).pin_memory(), "done": None}
+                          for _ in range(2)]
+        slot = self._tail[turn]
+        if slot["done"] is not None:
+            slot["done"].synchronize()
+        base = p.resident_bytes + turn * p.tail_bytes
+        hv, fill = slot["host"].numpy(), 0
+        for b, i in enumerate(indices):
+            if offs[b] >= 0:
+                continue
+            flat = self.host_images[i].reshape(-1)
+            if fill + flat.size > p.tail_bytes:
+                raise ValueError("the batch's spilled images exceed the set's staging tail: raise max_batch")
+            hv[fill:fill + flat.size] = flat
+            offs[b] = base + fill
+            fill += _align16(flat.size)
+        with torch.cuda.stream(stream):
+            self.buffer[base:base + fill].copy_(slot["host"][:fill], non_blocking=True)
+        slot["busy"] = True
+        return offs
+
+    def tail_read(self, turn: int, event) -> None:
+        """`event` completes behind the kernels that read what `stage_spilled` put into tail slot `turn`."""
+        if self._tail is not None and self._tail[turn].pop("busy", False):
+            self._tail[turn]["done"] = event
+
 
 def build_transform(cfg: InputConfig, is_train: bool, device, max_batch: int = 32, **kw) -> DeviceTransform:
     """Counterpart of Dassl's `build_transform(cfg, is_train)` for the choices the RPO configs make."""

@@ -26,6 +26,7 @@ from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .dist import GradSync
 from .engine import make_engine
+from .loop import LoopMixin
 from .trainer import OptimConfig, load_checkpoint_file, lr_at_epoch, write_checkpoint
 
 LP_PROMPT = "A photo of a {cls_name}"            # train.py:115 (cfg.TRAINER.LP.PROMPT)
@@ -98,13 +99,15 @@ class LPCustomCLIP:
             return eng.lp_forward_backward(image, None)
 
 
-class LP:
+class LP(LoopMixin):
     """The trainer (trainers/linear_prob.py:111-225): forward -> cross-entropy -> backward -> SGD step on lp_layer, returning
     {"loss", "acc"}; per-epoch LR update.  `prec` as TRAINER.LP.PREC: "fp32" = the f32 engine, "amp" = f16 storage plus
     the skip of a step whose gradient holds Inf / NaN (what is left of GradScaler when the gradients are fp32, as
     `CoOp(amp=True)`), "fp16" raises (the reference itself cannot run it).  Without `prec`, `act_dtype` and `amp` choose;
     bf16 is the explicit speed mode.  Data parallel: one sum all-reduce of the flat [W | b] gradient through `sync`
     (GradSync), grad_scale 1 / world_size in the SGD step."""
+
+    _reports_acc = True              # forward_backward reports "acc": run_epoch sums it on the device
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, optim: Optional[OptimConfig] = None,
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float32, batch_size: int = 32,

@@ -486,6 +486,20 @@ def lp_head_fwd_bwd(img_f, w, bias, text_f_n, label, scale_exp: float, z, logits
     return logits
 
 
+def eval_accumulate(logits, label, counts, cmat=None, pred=None):
+    """The classification evaluator's device half (include/rpo_amd.h rpo_eval_accumulate): counts int64 [2] (correct, total)
+    and cmat int32 [C, C] (row = true class) accumulate; pred int32 [B] is overwritten.  Enqueue only."""
+    B, Cc = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    assert label.dtype == torch.int64 and label.numel() == B and label.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
+    assert cmat is None or (cmat.dtype == torch.int32 and cmat.numel() == Cc * Cc and cmat.is_contiguous())
+    assert pred is None or (pred.dtype == torch.int32 and pred.numel() == B and pred.is_contiguous())
+    check(_lib.load().rpo_eval_accumulate(logits.data_ptr(), logits.stride(0), label.data_ptr(), B, Cc, counts.data_ptr(),
+                                          _p(cmat), _p(pred), _stream()), "rpo_eval_accumulate")
+    return counts
+
+
 def metanet_fwd(img_f, w1, b1, w2, b2, f_norm, hidden, bias):
     B, e = img_f.shape
     h, d = w1.shape[0], w2.shape[0]

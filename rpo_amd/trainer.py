@@ -1,7 +1,8 @@
 """``RPO`` trainer step with the reference's surface (trainers/rpo.py:235-357).
 
-Only the step semantics are reproduced -- Dassl's loop/data manager are out of
-scope (SURVEY.md section 2 rows 2, 14): ``forward_backward(batch)`` runs
+The step semantics are reproduced here; Dassl's epoch loops on top of them are
+``rpo_amd/loop.py`` (``run_epoch`` / ``test`` / ``train``), its data manager is out of
+scope (SURVEY.md section 2 row 2): ``forward_backward(batch)`` runs
 forward -> zero-grad -> backward -> SGD step (:306-309), returns
 ``{"loss": float}`` (:311) and updates the learning rate after the last batch
 of an epoch (:313-314).  The whole forward+backward is one captured HIP graph
@@ -23,6 +24,7 @@ from . import ops
 from .config import RPOConfig
 from .custom_clip import CustomCLIP
 from .dist import GradSync
+from .loop import LoopMixin
 from ._lib import xenv as _xenv
 
 
@@ -54,7 +56,9 @@ def lr_at_epoch(oc: OptimConfig, epoch: int) -> float:
     return oc.lr
 
 
-class RPO:
+class RPO(LoopMixin):
+    _takes_next_image = True         # run_epoch names the next batch: its patch embedding runs under this step
+
     def __init__(self, cfg: RPOConfig, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",
                  act_dtype: torch.dtype = torch.bfloat16, batch_size: int = 4, num_batches: int = 1,
@@ -501,6 +505,11 @@ class RPO:
                 return self.model(image)
             finally:
                 self.model.prompt_learner.train()
+
+    def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
+        """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
+        self._join_side()
+        return self.model.eval_logits(image)
 
     # -- checkpoints: Dassl layout <dir>/prompt_learner/{model.pth.tar-<epoch>, model-best.pth.tar} ----------
     def save_model(self, directory: str, epoch: Optional[int] = None, is_best: bool = False,

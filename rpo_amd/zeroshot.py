@@ -16,10 +16,11 @@ import torch
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .engine import Engine, make_engine
+from .loop import EvalMixin
 from . import synth
 
 
-class ZeroshotCLIP:
+class ZeroshotCLIP(EvalMixin):
     def __init__(self, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float16, max_batch: int = 100,
                  cfg: Optional[RPOConfig] = None):
@@ -33,6 +34,7 @@ class ZeroshotCLIP:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])     # one (unused) prompt row per image
         self.cfg = cfg
         self.engine = make_engine(cfg, state_dict, tokens, torch.device(device), act_dtype, max_batch)
+        self.device = self.engine.dev
         with torch.cuda.device(self.engine.dev):
             self.engine.cache_text_kv()                                       # text features: once (zsclip.py:48-53)
 
@@ -52,3 +54,7 @@ class ZeroshotCLIP:
             return eng.forward_plain(image).clone()
 
     __call__ = model_inference
+
+    def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
+        """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
+        return self.engine.forward_plain(image)
