@@ -55,7 +55,17 @@ enum {
   RPO_E_SHAPE = -2,    /* size not supported by the kernels (see each function) */
   RPO_E_DTYPE = -3,    /* dtype combination not supported */
   RPO_E_ALIGN = -4,    /* pointer / leading dimension not 16-byte aligned */
-  RPO_E_WORKSPACE = -5 /* caller-provided workspace / table bounds too small for this call */
+  RPO_E_WORKSPACE = -5, /* caller-provided workspace / table bounds too small for this call */
+  /* rpo_jpeg_probe: the file is not one the device decodes (the caller decodes it on the host instead) */
+  RPO_E_JPEG_CORRUPT = -20,     /* not a JPEG, or a header that is truncated / inconsistent */
+  RPO_E_JPEG_PROGRESSIVE = -21, /* SOF2 and the other progressive frames */
+  RPO_E_JPEG_ARITHMETIC = -22,  /* arithmetic coding */
+  RPO_E_JPEG_LOSSLESS = -23,    /* lossless / hierarchical frames */
+  RPO_E_JPEG_PRECISION = -24,   /* 12-bit samples, or 16-bit quantisation tables */
+  RPO_E_JPEG_COMPONENTS = -25,  /* not 1 or 3 components (CMYK / YCCK) */
+  RPO_E_JPEG_RGB = -26,         /* RGB-coded: Adobe APP14 transform 0, or component ids 'R','G','B' */
+  RPO_E_JPEG_SAMPLING = -27,    /* sampling other than 4:4:4, 4:2:2 (h2v1), 4:2:0 (h2v2) */
+  RPO_E_JPEG_MULTISCAN = -28    /* the first scan does not hold every component */
 };
 
 /* GEMM epilogues (fused into the MFMA kernel's store) */
@@ -451,6 +461,70 @@ int rpo_preprocess_batch(const uint8_t* src, int64_t src_bytes, const rpo_image_
                          const rpo_image_desc* desc_dev, int B, int size, int max_rows, int kmax,
                          const float* mean3, const float* std3, float* out, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ---- on-device JPEG decode ---------------------------------------------------------------------------------------
+ * Replaces Dassl's `read_image` (un-vendored; reached from the reference's dataset classes, datasets/oxford_pets.py:65-72
+ * via DatasetWrapper.__getitem__), which is Pillow's `Image.open(path).convert("RGB")`: libjpeg's baseline path with its
+ * defaults -- Huffman decode, dequantise, the "islow" integer IDCT, "fancy" (triangle) chroma upsampling, 16.16 fixed-point
+ * YCbCr -> RGB.  Output is BIT-IDENTICAL to Pillow's for every file rpo_jpeg_probe accepts: baseline sequential DCT (SOF0,
+ * SOF1 with 8-bit tables), 8-bit samples, 1 component (gray -> R = G = B) or 3 (YCbCr) at 4:4:4 / 4:2:2 / 4:2:0, any
+ * restart interval, one interleaved scan.  Everything else is refused with its own RPO_E_JPEG_* code and is the caller's to
+ * decode on the host.  The header is parsed on the host; everything from the first entropy-coded byte on runs on the device. */
+typedef struct rpo_jpeg_info {
+  int32_t width, height;
+  int32_t components;            /* 1 or 3 */
+  int32_t h_samp, v_samp;        /* luma sampling factors: 1x1 (4:4:4, gray), 2x1 (4:2:2), 2x2 (4:2:0) */
+  int32_t restart_interval;      /* MCUs per restart interval, 0 = none */
+  int32_t mcus_x, mcus_y;        /* MCU grid; an MCU is h_samp * v_samp luma blocks + 2 chroma blocks (gray: 1 block) */
+  int32_t units;                 /* independently decodable units of the scan: restart intervals (1 without DRI) */
+  int32_t reserved;
+  int64_t scan_offset;           /* first entropy-coded byte, relative to the file */
+  int64_t scan_bytes;            /* from there to the end of the file (the device stops at the first marker) */
+  int64_t table_bytes;           /* size of the table blob rpo_jpeg_tables writes (the same for every file) */
+  int64_t coef_bytes;            /* int16 coefficient blocks of this image in the workspace (128 B per block) */
+} rpo_jpeg_info;
+
+/* One image of a batch.  The caller fills file_offset / table_offset / out_offset / info; rpo_jpeg_workspace_bytes fills
+ * the rest. */
+typedef struct rpo_jpeg_desc {
+  int64_t file_offset;           /* the file's first byte in `files` */
+  int64_t file_bytes;
+  int64_t table_offset;          /* this image's table blob in `files`, 16-byte aligned */
+  int64_t out_offset;            /* where its packed RGB uint8 [height, width, 3] goes in `out` */
+  int64_t coef_offset;           /* (filled) its coefficient blocks in the workspace */
+  int32_t unit_base;             /* (filled) index of its first unit among the batch's */
+  int32_t reserved;
+  rpo_jpeg_info info;
+} rpo_jpeg_desc;
+
+/* Per-image status the decode leaves in `status` (0 = decoded).  The pixels of an image with a non-zero status are
+ * unspecified but deterministic, and inside its own height x width x 3 bytes. */
+enum {
+  RPO_JPEG_OK = 0,
+  RPO_JPEG_TRUNCATED = 1,   /* the scan ended (marker or end of file) before the header's block count was decoded */
+  RPO_JPEG_BAD_CODE = 2,    /* a bit pattern that is no code of the Huffman table, or a DC size above 11 */
+  RPO_JPEG_BAD_INDEX = 3,   /* a run that leaves the 8x8 block */
+  RPO_JPEG_NO_RESTART = 4   /* fewer restart markers than the header's restart interval implies */
+};
+
+/* HOST ONLY, no GPU work: parses the markers of `file` (never reading past nbytes) and fills *info.  Returns 0, or the
+ * RPO_E_JPEG_* code that names why the device does not decode this file. */
+int rpo_jpeg_probe(const uint8_t* file, int64_t nbytes, rpo_jpeg_info* info);
+/* HOST ONLY: writes the file's table blob (quantisation tables in natural order + derived Huffman lookup tables of the
+ * scan's components, info.table_bytes bytes) to host memory `blob`; the caller uploads it next to the file. */
+int rpo_jpeg_tables(const uint8_t* file, int64_t nbytes, void* blob, int64_t blob_bytes);
+/* HOST ONLY: lays the batch's workspace out -- fills coef_offset / unit_base of the n descriptors -- and returns the
+ * bytes of caller-owned workspace rpo_jpeg_decode_batch needs for them (0 on a bad argument). */
+size_t rpo_jpeg_workspace_bytes(rpo_jpeg_desc* descs, int n);
+/* files: device buffer (16-byte aligned, files_bytes bytes) holding the n files and their table blobs; desc_host / desc_dev:
+ * the same n descriptors in host and device memory (the host copy is validated -> RPO_E_SHAPE / RPO_E_WORKSPACE /
+ * RPO_E_ALIGN, the device copy is what the kernels read); out: device buffer of out_bytes bytes; status: int32 [n] device.
+ * n <= 65535 images of mixed sizes and modes.  Enqueues four kernels on `stream`: restart-marker scan, entropy decode (one
+ * lane per unit; every loop bound from the header, every byte read checked against the file's length), dequantise + IDCT,
+ * upsample + colour conversion.  Writes only each image's own height * width * 3 bytes of `out`. */
+int rpo_jpeg_decode_batch(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_desc* desc_host,
+                          const rpo_jpeg_desc* desc_dev, int n, uint8_t* out, int64_t out_bytes, void* workspace,
+                          size_t workspace_bytes, int32_t* status, void* stream);
 
 /* Empirical peaks of the box, used as second denominators by bench.py.
  * rpo_probe_peak_mfma: `blocks` workgroups of 4 waves each run `iters` rounds of 4 independent 32x32 MFMAs

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "librpo_hip.so")
 RPO_F32, RPO_BF16, RPO_F16 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_QGELU_BWD, EPI_PATCH, EPI_LN_BIAS, EPI_LN_BIAS_QGELU = range(8)
 E_BADARG, E_SHAPE, E_DTYPE, E_ALIGN, E_WORKSPACE = -1, -2, -3, -4, -5      # include/rpo_amd.h RPO_E_*
+(E_JPEG_CORRUPT, E_JPEG_PROGRESSIVE, E_JPEG_ARITHMETIC, E_JPEG_LOSSLESS, E_JPEG_PRECISION, E_JPEG_COMPONENTS, E_JPEG_RGB,
+ E_JPEG_SAMPLING, E_JPEG_MULTISCAN) = range(-20, -29, -1)
 
 c_i64, c_i32, c_f32, c_vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 
@@ -25,6 +27,19 @@ class ImageDesc(C.Structure):
                 ("crop_x", c_i32), ("crop_y", c_i32), ("crop_w", c_i32), ("crop_h", c_i32),
                 ("resize_w", c_i32), ("resize_h", c_i32), ("win_x", c_i32), ("win_y", c_i32),
                 ("flip", c_i32), ("reserved", c_i32)]
+
+
+class JpegInfo(C.Structure):
+    """struct rpo_jpeg_info (include/rpo_amd.h)."""
+    _fields_ = [("width", c_i32), ("height", c_i32), ("components", c_i32), ("h_samp", c_i32), ("v_samp", c_i32),
+                ("restart_interval", c_i32), ("mcus_x", c_i32), ("mcus_y", c_i32), ("units", c_i32), ("reserved", c_i32),
+                ("scan_offset", c_i64), ("scan_bytes", c_i64), ("table_bytes", c_i64), ("coef_bytes", c_i64)]
+
+
+class JpegDesc(C.Structure):
+    """struct rpo_jpeg_desc (include/rpo_amd.h)."""
+    _fields_ = [("file_offset", c_i64), ("file_bytes", c_i64), ("table_offset", c_i64), ("out_offset", c_i64),
+                ("coef_offset", c_i64), ("unit_base", c_i32), ("reserved", c_i32), ("info", JpegInfo)]
 
 
 class GemmArgs(C.Structure):
@@ -161,6 +176,10 @@ SIGNATURES = {
     "rpo_preprocess_workspace_bytes": (C.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
     "rpo_preprocess_batch": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                      C.c_size_t, c_vp]),
+    "rpo_jpeg_probe": (c_i32, [c_vp, c_i64, C.POINTER(JpegInfo)]),
+    "rpo_jpeg_tables": (c_i32, [c_vp, c_i64, c_vp, c_i64]),
+    "rpo_jpeg_workspace_bytes": (C.c_size_t, [C.POINTER(JpegDesc), c_i32]),
+    "rpo_jpeg_decode_batch": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, C.c_size_t, c_vp, c_vp]),
 }
 
 # include/rpo_amd_experimental.h: bound only from the -DRPO_EXPERIMENTAL build of the library (RPO_EXPERIMENTAL=1)

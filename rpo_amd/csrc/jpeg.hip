@@ -1,0 +1,641 @@
+// On-device baseline JPEG decode into packed RGB.  Replaces the host decode in front of the resident image
+// set: Dassl's `read_image` = Pillow's `Image.open(path).convert("RGB")` = libjpeg's baseline path with its defaults.  The
+// arithmetic restated (from its published statement: ITU T.81 + the Independent JPEG Group's documented integer paths):
+//   Huffman decode, FF 00 unstuffing, DC prediction, zig-zag -> natural order
+//   dequantise + "islow" 8x8 IDCT: 13-bit constants, columns descaled by 11 bits, rows by 18, +128, clamp
+//   "fancy" chroma upsampling: h2v1 (3a + b + 1|2) >> 2; h2v2 column sums 3 near + far, then (3t + n + 8|7) >> 4; edges
+//     replicated at the downsampled size; a chroma plane at most 2 samples wide is replicated instead
+//   YCbCr -> RGB in 16.16 fixed point
+// All integer, so results are bit-identical to Pillow's (tests/test_gpu_jpeg.py) whatever the launch geometry or the batch.
+//
+// The header is parsed on the host (parse_header below; plain C++, never reads past nbytes).  Four kernels per batch:
+//   restart_scan_kernel  per image: status = 0; byte offsets of the RSTn markers -> workspace (unit u starts behind marker u-1)
+//   entropy_kernel       one LANE per unit (image, or restart interval where DRI is present): sequential Huffman decode
+//                        into int16 coefficient blocks (128 B each, MCU order) in the workspace; up to 4096 units run one
+//                        per wave with the image's tables in LDS
+//   idct_kernel          one lane per block: dequantise + IDCT; the 64 uint8 samples overwrite the block's first 64 bytes
+//   colour_kernel        one lane per output pixel: sample fetch, upsample, colour conversion, 3 byte stores
+// What bounds the entropy kernel -- the only one that reads untrusted bytes: the block count, <= 63 AC iterations per block
+// (k strictly increases), <= 16 code lengths and <= 8 bytes per refill are all header / compile-time bounds; every byte read
+// goes through Bits::byte_at, which checks [begin, end) of the file; every table-derived index is masked.  A corrupt stream
+// therefore ends in a per-image status word and zeroed remaining blocks, never in a long or out-of-bounds run.
+#include "common.h"
+
+#include <string.h>
+
+#include <algorithm>
+
+namespace {
+
+#define HD __host__ __device__ __forceinline__
+// the coefficient workspace is written as int16 and as 4 / 16-byte words, the files are read as bytes and 8-byte words
+typedef uint32_t __attribute__((may_alias)) u32a_t;
+typedef uint64_t __attribute__((may_alias)) u64a_t;
+typedef int4 __attribute__((may_alias)) int4a_t;
+typedef int16_t __attribute__((may_alias)) i16a_t;
+
+struct HuffTab {
+  uint16_t look[512];     // 9-bit lookahead: (length << 8) | symbol, 0 = the code is longer than 9 bits
+  int32_t maxcode[18];    // [l] = largest code of length l, -1 = none
+  int32_t valoff[18];     // [l] = index of the first value of length l minus its code
+  uint8_t vals[256];
+};
+struct Tables {           // the per-image blob rpo_jpeg_tables writes: indexed by component of the scan
+  uint16_t quant[3][64];  // natural order
+  HuffTab dc[3], ac[3];
+};
+static_assert(sizeof(HuffTab) == 1424 && sizeof(Tables) == 384 + 6 * 1424 && sizeof(Tables) % 16 == 0, "blob layout");
+static_assert(sizeof(rpo_jpeg_info) == 72 && sizeof(rpo_jpeg_desc) == 120, "descriptor layout");
+
+__device__ __constant__ uint8_t ZIGZAG_D[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
+    41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38,
+    31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const uint8_t ZIGZAG_H[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
+    41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38,
+    31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+HD int zigzag(int k) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return ZIGZAG_D[k & 63];
+#else
+  return ZIGZAG_H[k & 63];
+#endif
+}
+
+HD int blocks_per_mcu(const rpo_jpeg_info& f) { return f.components == 1 ? 1 : f.h_samp * f.v_samp + 2; }
+
+// ---- the entropy-coded segment as a bit source ------------------------------------------------------------------
+// Bytes come from `base` in aligned 8-byte words; a word is loaded whole only if it lies inside [0, total) of the buffer,
+// and only bytes of [pos, end) -- this file's scan -- are ever USED.  At a marker (FF followed by anything but 00) or at
+// `end` the source feeds zero bytes and counts them: a decode that consumed one of those bits overran the data.
+struct Bits {
+  const uint8_t* base;
+  int64_t pos, end, total;
+  int64_t word_idx;
+  uint64_t word, next_word;
+  uint64_t buf;
+  int nbits, fake;
+
+  HD void init(const uint8_t* b, int64_t p, int64_t e, int64_t t) {
+    base = b; pos = p; end = e; total = t; word_idx = -2; word = 0; next_word = 0; buf = 0; nbits = 0; fake = 0;
+  }
+  HD uint64_t load_word(int64_t wi) const {   // bytes [8 wi, 8 wi + 8) of the buffer, zero beyond `total`
+    if (wi * 8 + 8 <= total) return *reinterpret_cast<const u64a_t*>(base + wi * 8);
+    uint64_t w = 0;
+    for (int i = 0; i < 8; ++i)
+      if (wi * 8 + i < total) w |= (uint64_t)base[wi * 8 + i] << (8 * i);
+    return w;
+  }
+  HD uint32_t byte_at(int64_t p) {           // p in [0, total) by the caller's pos < end <= total
+    const int64_t wi = p >> 3;
+    if (wi != word_idx) {                    // the stream advances word by word: the following word is requested now and
+      word = wi == word_idx + 1 ? next_word : load_word(wi);   // used at the next switch, its latency behind the decode
+      word_idx = wi;
+      next_word = load_word(wi + 1);
+    }
+    return (uint32_t)(word >> ((p & 7) * 8)) & 255u;
+  }
+  HD void refill() {                         // at most 8 iterations: nbits grows by 8 each
+    while (nbits <= 56) {
+      uint32_t b = 0;
+      if (fake == 0 && pos < end) {
+        b = byte_at(pos);
+        if (b == 0xFFu) {
+          const uint32_t b2 = pos + 1 < end ? byte_at(pos + 1) : 0xD9u;
+          if (b2 == 0) pos += 2;
+          else { b = 0; fake = 8; }
+        } else {
+          ++pos;
+        }
+      } else {
+        fake += 8;
+      }
+      buf |= (uint64_t)b << (56 - nbits);
+      nbits += 8;
+    }
+  }
+  HD uint32_t peek(int n) const { return (uint32_t)(buf >> (64 - n)); }      // 1 <= n <= 32
+  HD void skip(int n) { buf <<= n; nbits -= n; }
+  HD bool overrun() const { return fake > nbits; }
+};
+
+// One Huffman symbol; needs >= 16 bits in the buffer.  Returns -1 for a pattern that is no code.
+HD int huff_symbol(Bits& br, const HuffTab* t) {
+  const uint32_t e = t->look[br.peek(9)];
+  if (e) {
+    br.skip((int)(e >> 8) & 15);
+    return (int)(e & 255u);
+  }
+  const int32_t code16 = (int32_t)br.peek(16);
+  for (int l = 10; l <= 16; ++l) {
+    const int32_t code = code16 >> (16 - l);
+    if (code <= t->maxcode[l]) {
+      br.skip(l);
+      return t->vals[(code + t->valoff[l]) & 255];
+    }
+  }
+  return -1;
+}
+
+HD int extend(uint32_t v, int s) { return (int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
+
+HD void zero_block(i16a_t* blk) {
+  int4a_t* p = reinterpret_cast<int4a_t*>(blk);
+  for (int i = 0; i < 8; ++i) p[i] = int4{0, 0, 0, 0};
+}
+
+// Unit `unit` of image d: MCUs [unit * ri, +ri) (all of them without DRI), starting `start` bytes into the scan (< 0: its
+// restart marker was not found).  Returns the RPO_JPEG_* status.  Blocks behind an error are left zero.
+HD int decode_unit(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_desc& d, const Tables* tab, int16_t* coef,
+                   int unit, int start) {
+  const rpo_jpeg_info& f = d.info;
+  const int total = f.mcus_x * f.mcus_y;
+  const int ri = f.restart_interval > 0 ? f.restart_interval : total;
+  const int mcu0 = unit * ri;
+  const int nmcu = min(ri, total - mcu0);
+  const int bpm = blocks_per_mcu(f), luma = bpm == 1 ? 1 : bpm - 2;
+  int err = start < 0 ? RPO_JPEG_NO_RESTART : RPO_JPEG_OK;
+  const int64_t scan0 = d.file_offset + f.scan_offset;
+  Bits br;
+  br.init(files, scan0 + (start < 0 ? 0 : start), scan0 + f.scan_bytes, files_bytes);
+  if (start < 0 || start > f.scan_bytes) br.pos = br.end;
+  int pred[3] = {0, 0, 0};
+  for (int m = 0; m < nmcu; ++m) {
+    for (int j = 0; j < bpm; ++j) {
+      i16a_t* blk = coef + ((int64_t)(mcu0 + m) * bpm + j) * 64;
+      zero_block(blk);
+      if (err) continue;
+      const int c = j < luma ? 0 : j - luma + 1;
+      br.refill();
+      int s = huff_symbol(br, &tab->dc[c]);
+      if (s < 0 || s > 11) { err = RPO_JPEG_BAD_CODE; continue; }
+      if (s) {
+        pred[c] += extend(br.peek(s), s);
+        br.skip(s);
+      }
+      blk[0] = (int16_t)pred[c];
+      for (int k = 1; k < 64;) {             // k grows by >= 1 per iteration
+        br.refill();
+        const int rs = huff_symbol(br, &tab->ac[c]);
+        if (rs < 0) { err = RPO_JPEG_BAD_CODE; break; }
+        const int r = rs >> 4;
+        s = rs & 15;
+        if (s) {
+          k += r;
+          if (k > 63) { err = RPO_JPEG_BAD_INDEX; break; }
+          blk[zigzag(k)] = (int16_t)extend(br.peek(s), s);
+          br.skip(s);
+          ++k;
+        } else if (r == 15) {
+          k += 16;
+        } else {
+          break;
+        }
+      }
+      if (!err && br.overrun()) err = RPO_JPEG_TRUNCATED;
+    }
+  }
+  return err;
+}
+
+// ---- dequantise + IDCT ------------------------------------------------------------------------------------------
+HD void idct_1d(const int* in, int stride, int* out, int ostride, int shift) {
+  const int in0 = in[0], in1 = in[stride], in2 = in[2 * stride], in3 = in[3 * stride], in4 = in[4 * stride],
+            in5 = in[5 * stride], in6 = in[6 * stride], in7 = in[7 * stride];
+  int z1 = (in2 + in6) * 4433;
+  const int tmp2 = z1 + in6 * -15137, tmp3 = z1 + in2 * 6270;
+  const int tmp0 = (in0 + in4) * 8192, tmp1 = (in0 - in4) * 8192;
+  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  int t0 = in7, t1 = in5, t2 = in3, t3 = in1;
+  z1 = t0 + t3;
+  int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+  const int z5 = (z3 + z4) * 9633;
+  t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+  const int rnd = 1 << (shift - 1);
+  out[0] = (tmp10 + t3 + rnd) >> shift;
+  out[7 * ostride] = (tmp10 - t3 + rnd) >> shift;
+  out[ostride] = (tmp11 + t2 + rnd) >> shift;
+  out[6 * ostride] = (tmp11 - t2 + rnd) >> shift;
+  out[2 * ostride] = (tmp12 + t1 + rnd) >> shift;
+  out[5 * ostride] = (tmp12 - t1 + rnd) >> shift;
+  out[3 * ostride] = (tmp13 + t0 + rnd) >> shift;
+  out[4 * ostride] = (tmp13 - t0 + rnd) >> shift;
+}
+
+// blk: 64 int16 coefficients in natural order -> 64 uint8 samples (row-major) over its first 64 bytes
+HD void idct_block(i16a_t* blk, const uint16_t* q) {
+  int v[64], w[64];
+#pragma unroll
+  for (int i = 0; i < 64; ++i) v[i] = (int)blk[i] * (int)q[i];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) idct_1d(v + c, 8, w + c, 8, 11);       // columns
+  uint8_t* o = reinterpret_cast<uint8_t*>(blk);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    int row[8];
+    idct_1d(w + 8 * r, 1, row, 1, 18);                               // rows
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      lo |= (uint32_t)min(max(row[i] + 128, 0), 255) << (8 * i);
+      hi |= (uint32_t)min(max(row[i + 4] + 128, 0), 255) << (8 * i);
+    }
+    reinterpret_cast<u32a_t*>(o)[2 * r] = lo;
+    reinterpret_cast<u32a_t*>(o)[2 * r + 1] = hi;
+  }
+}
+
+// ---- upsample + colour conversion -------------------------------------------------------------------------------
+// sample (x, y) of component c; blocks are in MCU order, 128 bytes apart, samples in the first 64
+HD int sample_at(const uint8_t* coef, const rpo_jpeg_info& f, int c, int x, int y) {
+  const int bx = x >> 3, by = y >> 3;
+  int64_t blk;
+  if (f.components == 1) {
+    blk = (int64_t)by * f.mcus_x + bx;
+  } else {
+    const int hv = f.h_samp * f.v_samp;
+    if (c == 0)
+      blk = ((int64_t)(by / f.v_samp) * f.mcus_x + bx / f.h_samp) * (hv + 2) + (by % f.v_samp) * f.h_samp + bx % f.h_samp;
+    else
+      blk = ((int64_t)by * f.mcus_x + bx) * (hv + 2) + hv + c - 1;
+  }
+  return coef[blk * 128 + (y & 7) * 8 + (x & 7)];
+}
+
+HD int chroma_at(const uint8_t* coef, const rpo_jpeg_info& f, int c, int x, int y) {
+  if (f.h_samp == 1) return sample_at(coef, f, c, x, y);
+  const int cw = (f.width + 1) >> 1;
+  if (cw <= 2) return sample_at(coef, f, c, x >> 1, f.v_samp == 2 ? y >> 1 : y);
+  const int cx = x >> 1, odd = x & 1;
+  const int nx = odd ? min(cx + 1, cw - 1) : max(cx - 1, 0);
+  if (f.v_samp == 1)
+    return (3 * sample_at(coef, f, c, cx, y) + sample_at(coef, f, c, nx, y) + 1 + odd) >> 2;
+  const int ch = (f.height + 1) >> 1;
+  const int cy = y >> 1, fy = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
+  const int t = 3 * sample_at(coef, f, c, cx, cy) + sample_at(coef, f, c, cx, fy);
+  const int n = 3 * sample_at(coef, f, c, nx, cy) + sample_at(coef, f, c, nx, fy);
+  return (3 * t + n + 8 - odd) >> 4;
+}
+
+HD void pixel_rgb(const uint8_t* coef, const rpo_jpeg_info& f, int x, int y, uint8_t* out) {
+  const int Y = sample_at(coef, f, 0, x, y);
+  if (f.components == 1) {
+    out[0] = out[1] = out[2] = (uint8_t)Y;
+    return;
+  }
+  const int cb = chroma_at(coef, f, 1, x, y) - 128, cr = chroma_at(coef, f, 2, x, y) - 128;
+  const int r = Y + ((91881 * cr + 32768) >> 16);
+  const int g = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+  const int b = Y + ((116130 * cb + 32768) >> 16);
+  out[0] = (uint8_t)min(max(r, 0), 255);
+  out[1] = (uint8_t)min(max(g, 0), 255);
+  out[2] = (uint8_t)min(max(b, 0), 255);
+}
+
+// ---- kernels ----------------------------------------------------------------------------------------------------
+constexpr int SCAN_THREADS = 256;
+
+__global__ __launch_bounds__(SCAN_THREADS) void restart_scan_kernel(const uint8_t* __restrict__ files,
+                                                                    const rpo_jpeg_desc* __restrict__ desc, int32_t* rst,
+                                                                    int32_t* status) {
+  __shared__ int counts[SCAN_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const rpo_jpeg_desc d = desc[b];
+  const int units = d.info.units;
+  int32_t* mine = rst + d.unit_base;
+  if (tid == 0) status[b] = RPO_JPEG_OK;
+  for (int u = tid; u < units; u += SCAN_THREADS) mine[u] = u == 0 ? 0 : -1;
+  if (units <= 1) return;                                  // uniform per block
+  __syncthreads();
+  const uint8_t* p = files + d.file_offset + d.info.scan_offset;
+  const int64_t n = d.info.scan_bytes;                     // pairs (i, i + 1) with i + 1 < n
+  const int64_t chunk = (n + SCAN_THREADS - 1) / SCAN_THREADS;
+  const int64_t lo = tid * chunk, hi = min(lo + chunk, n - 1);
+  int cnt = 0;
+  for (int64_t i = lo; i < hi; ++i) cnt += (p[i] == 0xFF && (p[i + 1] & 0xF8) == 0xD0);
+  counts[tid] = cnt;
+  __syncthreads();
+  for (int off = 1; off < SCAN_THREADS; off <<= 1) {       // inclusive scan
+    const int v = tid >= off ? counts[tid - off] : 0;
+    __syncthreads();
+    counts[tid] += v;
+    __syncthreads();
+  }
+  int ord = counts[tid] - cnt;                             // markers before this thread's chunk
+  for (int64_t i = lo; i < hi; ++i) {
+    if (p[i] == 0xFF && (p[i + 1] & 0xF8) == 0xD0) {
+      if (ord + 1 < units) mine[ord + 1] = (int32_t)(i + 2);
+      ++ord;
+    }
+  }
+}
+
+// `lanes` active lanes per 64-lane block.  Few units (<= 4096, the usual case: one per image) -> ONE_PER_BLOCK: one unit per
+// wave, no divergence, and the wave first copies its image's table blob into LDS, so the table look-up on the decode's
+// dependency chain is an LDS read instead of a global one.  More units -> up to 64 per wave, tables read from global memory.
+template <bool ONE_PER_BLOCK>
+__global__ __launch_bounds__(64) void entropy_kernel(const uint8_t* __restrict__ files, int64_t files_bytes,
+                                                     const rpo_jpeg_desc* __restrict__ desc, int n, int total_units, int lanes,
+                                                     char* ws, int32_t* status) {
+  __shared__ int4 lds_tab[ONE_PER_BLOCK ? sizeof(Tables) / 16 : 1];
+  if (!ONE_PER_BLOCK && (int)threadIdx.x >= lanes) return;
+  const int u = ONE_PER_BLOCK ? (int)blockIdx.x : blockIdx.x * lanes + threadIdx.x;
+  if (u >= total_units) return;                            // block-uniform when ONE_PER_BLOCK
+  int lo = 0, hi = n - 1;                                  // last image with unit_base <= u; <= 16 steps (n <= 65535)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid].unit_base <= u) lo = mid; else hi = mid - 1;
+  }
+  const rpo_jpeg_desc d = desc[lo];
+  const int unit = u - d.unit_base;
+  const Tables* tab = reinterpret_cast<const Tables*>(files + d.table_offset);
+  if (ONE_PER_BLOCK) {
+    const int4* src = reinterpret_cast<const int4*>(tab);
+    for (int i = threadIdx.x; i < (int)(sizeof(Tables) / 16); i += 64) lds_tab[i] = src[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    tab = reinterpret_cast<const Tables*>(lds_tab);
+  }
+  if (unit >= d.info.units) return;
+  const int32_t* rst = reinterpret_cast<const int32_t*>(ws);
+  const int err = decode_unit(files, files_bytes, d, tab, reinterpret_cast<int16_t*>(ws + d.coef_offset), unit, rst[u]);
+  if (err) atomicMax(status + lo, err);
+}
+
+__global__ __launch_bounds__(256) void idct_kernel(const uint8_t* __restrict__ files, const rpo_jpeg_desc* __restrict__ desc,
+                                                   char* ws) {
+  const int b = blockIdx.y;
+  const rpo_jpeg_desc d = desc[b];
+  const int bpm = blocks_per_mcu(d.info), luma = bpm == 1 ? 1 : bpm - 2;
+  const int nblk = d.info.mcus_x * d.info.mcus_y * bpm;
+  const Tables* tab = reinterpret_cast<const Tables*>(files + d.table_offset);
+  int16_t* coef = reinterpret_cast<int16_t*>(ws + d.coef_offset);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nblk; i += gridDim.x * blockDim.x) {
+    const int j = i % bpm;
+    idct_block(coef + (int64_t)i * 64, tab->quant[j < luma ? 0 : j - luma + 1]);
+  }
+}
+
+__global__ __launch_bounds__(256) void colour_kernel(const rpo_jpeg_desc* __restrict__ desc, const char* ws, uint8_t* out) {
+  const int b = blockIdx.y;
+  const rpo_jpeg_desc d = desc[b];
+  const uint8_t* coef = reinterpret_cast<const uint8_t*>(ws + d.coef_offset);
+  uint8_t* o = out + d.out_offset;
+  const int W = d.info.width, npix = W * d.info.height;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+    uint8_t rgb[3];
+    pixel_rgb(coef, d.info, i % W, i / W, rgb);
+    o[(int64_t)i * 3] = rgb[0]; o[(int64_t)i * 3 + 1] = rgb[1]; o[(int64_t)i * 3 + 2] = rgb[2];
+  }
+}
+
+// ---- host: header parsing ---------------------------------------------------------------------------------------
+struct RawHuff { bool set; uint8_t bits[17]; uint8_t vals[256]; int count; };
+struct Parsed {
+  rpo_jpeg_info info;
+  uint8_t qtab[4][64];      // zig-zag order, as in the file
+  bool qset[4];
+  RawHuff huff[2][4];
+  int comp_q[3], comp_dc[3], comp_ac[3];
+};
+
+int parse_header(const uint8_t* p, int64_t n, Parsed& P) {
+  memset(&P, 0, sizeof(P));
+  if (n < 4 || p[0] != 0xFF || p[1] != 0xD8) return RPO_E_JPEG_CORRUPT;
+  int64_t pos = 2;
+  bool have_frame = false, jfif = false;
+  int adobe = -1, nc = 0;
+  uint8_t cid[4] = {0}, ch[4] = {0}, cv[4] = {0}, cq[4] = {0};
+  for (;;) {
+    if (pos + 2 > n || p[pos] != 0xFF) return RPO_E_JPEG_CORRUPT;
+    const int m = p[pos + 1];
+    pos += 2;
+    if (m == 0xFF) { pos -= 1; continue; }                 // fill byte
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   // standalone markers
+    if (m == 0xD9 || m == 0xD8) return RPO_E_JPEG_CORRUPT;
+    if (pos + 2 > n) return RPO_E_JPEG_CORRUPT;
+    const int L = (p[pos] << 8) | p[pos + 1];
+    if (L < 2 || pos + L > n) return RPO_E_JPEG_CORRUPT;
+    const uint8_t* seg = p + pos + 2;
+    const int sl = L - 2;
+    pos += L;
+    if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) return RPO_E_JPEG_PROGRESSIVE;
+    if (m == 0xC9 || m == 0xCB || m == 0xCD || m == 0xCF || m == 0xCC) return RPO_E_JPEG_ARITHMETIC;
+    if (m == 0xC3 || m == 0xC5 || m == 0xC7) return RPO_E_JPEG_LOSSLESS;
+    if (m == 0xC0 || m == 0xC1) {
+      if (have_frame || sl < 6) return RPO_E_JPEG_CORRUPT;
+      if (seg[0] != 8) return RPO_E_JPEG_PRECISION;
+      P.info.height = (seg[1] << 8) | seg[2];
+      P.info.width = (seg[3] << 8) | seg[4];
+      nc = seg[5];
+      if (sl != 6 + 3 * nc || P.info.height == 0 || P.info.width == 0) return RPO_E_JPEG_CORRUPT;
+      if (nc != 1 && nc != 3) return RPO_E_JPEG_COMPONENTS;
+      for (int i = 0; i < nc; ++i) {
+        cid[i] = seg[6 + 3 * i]; ch[i] = seg[7 + 3 * i] >> 4; cv[i] = seg[7 + 3 * i] & 15; cq[i] = seg[8 + 3 * i];
+        if (cq[i] > 3 || ch[i] == 0 || cv[i] == 0) return RPO_E_JPEG_CORRUPT;
+      }
+      P.info.components = nc;
+      have_frame = true;
+    } else if (m == 0xDB) {
+      for (int q = 0; q < sl;) {
+        const int pq = seg[q] >> 4, tq = seg[q] & 15;
+        if (tq > 3) return RPO_E_JPEG_CORRUPT;
+        if (pq) return RPO_E_JPEG_PRECISION;
+        if (q + 65 > sl) return RPO_E_JPEG_CORRUPT;
+        memcpy(P.qtab[tq], seg + q + 1, 64);
+        P.qset[tq] = true;
+        q += 65;
+      }
+    } else if (m == 0xC4) {
+      for (int q = 0; q < sl;) {
+        if (q + 17 > sl) return RPO_E_JPEG_CORRUPT;
+        const int tc = seg[q] >> 4, th = seg[q] & 15;
+        if (tc > 1 || th > 3) return RPO_E_JPEG_CORRUPT;
+        RawHuff& h = P.huff[tc][th];
+        int cnt = 0;
+        h.bits[0] = 0;
+        for (int i = 1; i <= 16; ++i) { h.bits[i] = seg[q + i]; cnt += h.bits[i]; }
+        if (cnt > 256 || q + 17 + cnt > sl) return RPO_E_JPEG_CORRUPT;
+        int code = 0;                                       // the lengths must describe a prefix code
+        for (int l = 1; l <= 16; ++l) {
+          code += h.bits[l];
+          if (code > (1 << l)) return RPO_E_JPEG_CORRUPT;
+          code <<= 1;
+        }
+        memcpy(h.vals, seg + q + 17, cnt);
+        h.count = cnt;
+        h.set = true;
+        q += 17 + cnt;
+      }
+    } else if (m == 0xDD) {
+      if (sl != 2) return RPO_E_JPEG_CORRUPT;
+      P.info.restart_interval = (seg[0] << 8) | seg[1];
+    } else if (m == 0xE0) {
+      if (sl >= 5 && memcmp(seg, "JFIF\0", 5) == 0) jfif = true;
+    } else if (m == 0xEE) {
+      if (sl >= 12 && memcmp(seg, "Adobe", 5) == 0) adobe = seg[11];
+    } else if (m == 0xDA) {
+      if (!have_frame) return RPO_E_JPEG_CORRUPT;
+      const int ns = sl > 0 ? seg[0] : 0;
+      if (sl != 4 + 2 * ns) return RPO_E_JPEG_CORRUPT;
+      if (ns != nc) return RPO_E_JPEG_MULTISCAN;
+      P.info.h_samp = P.info.v_samp = 1;
+      if (nc == 3) {
+        const bool rgb_ids = cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B';
+        if (!jfif && (adobe == 0 || (adobe < 0 && rgb_ids))) return RPO_E_JPEG_RGB;
+        if (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1) return RPO_E_JPEG_SAMPLING;
+        if (!((ch[0] == 1 && cv[0] == 1) || (ch[0] == 2 && cv[0] == 1) || (ch[0] == 2 && cv[0] == 2)))
+          return RPO_E_JPEG_SAMPLING;
+        P.info.h_samp = ch[0];
+        P.info.v_samp = cv[0];
+      }
+      for (int i = 0; i < ns; ++i) {
+        if (seg[1 + 2 * i] != cid[i]) return RPO_E_JPEG_MULTISCAN;
+        const int td = seg[2 + 2 * i] >> 4, ta = seg[2 + 2 * i] & 15;
+        if (td > 3 || ta > 3 || !P.qset[cq[i]] || !P.huff[0][td].set || !P.huff[1][ta].set) return RPO_E_JPEG_CORRUPT;
+        P.comp_q[i] = cq[i]; P.comp_dc[i] = td; P.comp_ac[i] = ta;
+      }
+      rpo_jpeg_info& f = P.info;
+      f.mcus_x = (f.width + 8 * f.h_samp - 1) / (8 * f.h_samp);
+      f.mcus_y = (f.height + 8 * f.v_samp - 1) / (8 * f.v_samp);
+      const int total = f.mcus_x * f.mcus_y;
+      f.units = f.restart_interval ? (total + f.restart_interval - 1) / f.restart_interval : 1;
+      f.scan_offset = pos;
+      f.scan_bytes = n - pos;
+      f.table_bytes = sizeof(Tables);
+      f.coef_bytes = (int64_t)total * blocks_per_mcu(f) * 128;
+      return 0;
+    }
+    // every other segment (APPn, COM, DNL, ...) is skipped
+  }
+}
+
+void derive(const RawHuff& h, HuffTab& t) {
+  memset(&t, 0, sizeof(t));
+  memcpy(t.vals, h.vals, h.count);
+  int code = 0, p = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int nb = h.bits[l];
+    t.maxcode[l] = nb ? code + nb - 1 : -1;
+    t.valoff[l] = p - code;
+    if (l <= 9)
+      for (int i = 0; i < nb; ++i)
+        for (int k = 0; k < (1 << (9 - l)); ++k)
+          t.look[((code + i) << (9 - l)) + k] = (uint16_t)((l << 8) | h.vals[p + i]);
+    code = (code + nb) << 1;
+    p += nb;
+  }
+  t.maxcode[0] = t.maxcode[17] = -1;
+}
+
+bool info_consistent(const rpo_jpeg_info& f) {
+  if (f.width < 1 || f.width > 65535 || f.height < 1 || f.height > 65535) return false;
+  if (f.components == 1) { if (f.h_samp != 1 || f.v_samp != 1) return false; }
+  else if (f.components == 3) {
+    if (!((f.h_samp == 1 && f.v_samp == 1) || (f.h_samp == 2 && f.v_samp == 1) || (f.h_samp == 2 && f.v_samp == 2))) return false;
+  } else return false;
+  if (f.mcus_x != (f.width + 8 * f.h_samp - 1) / (8 * f.h_samp) || f.mcus_y != (f.height + 8 * f.v_samp - 1) / (8 * f.v_samp))
+    return false;
+  const int total = f.mcus_x * f.mcus_y;
+  if (f.restart_interval < 0 || f.restart_interval > 65535) return false;
+  if (f.units != (f.restart_interval ? (total + f.restart_interval - 1) / f.restart_interval : 1)) return false;
+  if (f.table_bytes != (int64_t)sizeof(Tables) || f.coef_bytes != (int64_t)total * blocks_per_mcu(f) * 128) return false;
+  if (f.scan_offset < 0 || f.scan_bytes < 0 || f.scan_bytes > 0x7fffffff) return false;
+  return true;
+}
+
+constexpr int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+extern "C" int rpo_jpeg_probe(const uint8_t* file, int64_t nbytes, rpo_jpeg_info* info) {
+  if (!file || !info || nbytes <= 0) return RPO_E_BADARG;
+  Parsed P;
+  const int rc = parse_header(file, nbytes, P);
+  *info = P.info;
+  return rc;
+}
+
+extern "C" int rpo_jpeg_tables(const uint8_t* file, int64_t nbytes, void* blob, int64_t blob_bytes) {
+  if (!file || !blob || nbytes <= 0) return RPO_E_BADARG;
+  if (blob_bytes < (int64_t)sizeof(Tables)) return RPO_E_WORKSPACE;
+  Parsed P;
+  const int rc = parse_header(file, nbytes, P);
+  if (rc) return rc;
+  Tables* T = static_cast<Tables*>(blob);
+  memset(T, 0, sizeof(Tables));
+  for (int c = 0; c < P.info.components; ++c) {
+    for (int k = 0; k < 64; ++k) T->quant[c][ZIGZAG_H[k]] = P.qtab[P.comp_q[c]][k];
+    derive(P.huff[0][P.comp_dc[c]], T->dc[c]);
+    derive(P.huff[1][P.comp_ac[c]], T->ac[c]);
+  }
+  return 0;
+}
+
+extern "C" size_t rpo_jpeg_workspace_bytes(rpo_jpeg_desc* descs, int n) {
+  if (!descs || n <= 0 || n > 65535) return 0;
+  int64_t units = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!info_consistent(descs[i].info) || units + descs[i].info.units > 0x7fffffff) return 0;
+    descs[i].unit_base = (int32_t)units;
+    units += descs[i].info.units;
+  }
+  int64_t off = align_up(units * 4, 256);
+  for (int i = 0; i < n; ++i) {
+    descs[i].coef_offset = off;
+    off += descs[i].info.coef_bytes;
+  }
+  return (size_t)off + 16;
+}
+
+extern "C" int rpo_jpeg_decode_batch(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_desc* desc_host,
+                                     const rpo_jpeg_desc* desc_dev, int n, uint8_t* out, int64_t out_bytes, void* workspace,
+                                     size_t workspace_bytes, int32_t* status, void* stream) {
+  if (!files || !desc_host || !desc_dev || !out || !workspace || !status || n <= 0 || files_bytes <= 0 || out_bytes <= 0)
+    return RPO_E_BADARG;
+  if (n > 65535) return RPO_E_SHAPE;
+  if (reinterpret_cast<uintptr_t>(files) % 16 || reinterpret_cast<uintptr_t>(workspace) % 16) return RPO_E_ALIGN;
+  int64_t units = 0, max_blocks = 1, max_pix = 1;
+  for (int i = 0; i < n; ++i) {           // the descriptors are the only untrusted input of the launch: validate the host copy
+    const rpo_jpeg_desc& d = desc_host[i];
+    const rpo_jpeg_info& f = d.info;
+    if (!info_consistent(f)) return RPO_E_SHAPE;
+    if (d.file_offset < 0 || d.file_bytes <= 0 || d.file_offset + d.file_bytes > files_bytes ||
+        f.scan_offset + f.scan_bytes > d.file_bytes)
+      return RPO_E_SHAPE;
+    if (d.table_offset < 0 || d.table_offset + f.table_bytes > files_bytes) return RPO_E_SHAPE;
+    if (d.table_offset % 16) return RPO_E_ALIGN;
+    if (d.out_offset < 0 || d.out_offset + (int64_t)f.width * f.height * 3 > out_bytes) return RPO_E_SHAPE;
+    if (d.unit_base != units) return RPO_E_WORKSPACE;
+    units += f.units;
+    if (units > 0x7fffffff) return RPO_E_SHAPE;
+    max_blocks = std::max<int64_t>(max_blocks, f.coef_bytes / 128);
+    max_pix = std::max<int64_t>(max_pix, (int64_t)f.width * f.height);
+  }
+  int64_t off = align_up(units * 4, 256);
+  for (int i = 0; i < n; ++i) {
+    if (desc_host[i].coef_offset != off) return RPO_E_WORKSPACE;
+    off += desc_host[i].info.coef_bytes;
+  }
+  if ((size_t)off + 16 > workspace_bytes) return RPO_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(workspace);
+  hipLaunchKernelGGL(restart_scan_kernel, dim3(n), dim3(SCAN_THREADS), 0, s, files, desc_dev, reinterpret_cast<int32_t*>(ws),
+                     status);
+  const int lanes = (int)std::min<int64_t>(64, (units + 4095) / 4096);
+  if (lanes == 1)
+    hipLaunchKernelGGL(entropy_kernel<true>, dim3((unsigned)units), dim3(64), 0, s, files, files_bytes, desc_dev, n,
+                       (int)units, lanes, ws, status);
+  else
+    hipLaunchKernelGGL(entropy_kernel<false>, dim3((unsigned)((units + lanes - 1) / lanes)), dim3(64), 0, s, files,
+                       files_bytes, desc_dev, n, (int)units, lanes, ws, status);
+  hipLaunchKernelGGL(idct_kernel, dim3((unsigned)std::min<int64_t>((max_blocks + 255) / 256, 64), n), dim3(256), 0, s, files,
+                     desc_dev, ws);
+  hipLaunchKernelGGL(colour_kernel, dim3((unsigned)std::min<int64_t>((max_pix + 255) / 256, 256), n), dim3(256), 0, s, desc_dev,
+                     ws, out);
+  return rpo_launch_status();
+}

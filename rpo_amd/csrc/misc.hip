@@ -676,6 +676,15 @@ extern "C" const char* rpo_error_string(int code) {
     case RPO_E_DTYPE: return "rpo: dtype combination not supported";
     case RPO_E_ALIGN: return "rpo: pointer or leading dimension not sufficiently aligned";
     case RPO_E_WORKSPACE: return "rpo: workspace or table bound too small for this call";
+    case RPO_E_JPEG_CORRUPT: return "rpo: jpeg: not a JPEG file, or a truncated / inconsistent header";
+    case RPO_E_JPEG_PROGRESSIVE: return "rpo: jpeg: progressive frame (decode on the host)";
+    case RPO_E_JPEG_ARITHMETIC: return "rpo: jpeg: arithmetic coding (decode on the host)";
+    case RPO_E_JPEG_LOSSLESS: return "rpo: jpeg: lossless or hierarchical frame (decode on the host)";
+    case RPO_E_JPEG_PRECISION: return "rpo: jpeg: 12-bit samples or 16-bit quantisation tables (decode on the host)";
+    case RPO_E_JPEG_COMPONENTS: return "rpo: jpeg: neither 1 nor 3 components, e.g. CMYK (decode on the host)";
+    case RPO_E_JPEG_RGB: return "rpo: jpeg: RGB-coded file, no YCbCr transform (decode on the host)";
+    case RPO_E_JPEG_SAMPLING: return "rpo: jpeg: chroma sampling other than 4:4:4 / 4:2:2 / 4:2:0 (decode on the host)";
+    case RPO_E_JPEG_MULTISCAN: return "rpo: jpeg: components spread over several scans (decode on the host)";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "rpo: unknown error";
   }
 }

@@ -431,6 +431,88 @@ class DeviceImageSet:
         if self._tail is not None and self._tail[turn].pop("busy", False):
             self._tail[turn]["done"] = event
 
+    @classmethod
+    def from_jpeg(cls, files: Sequence, labels: Sequence[int], device, budget_bytes: Optional[int] = None,
+                  n_cls: Optional[int] = None, max_batch: int = 128, fallback: Optional[Callable] = None,
+                  chunk_images: int = 1024) -> "DeviceImageSet":
+        """The same set from JPEG files (`bytes`, or paths that are read here) without a host decode: Dassl's `read_image`
+        (Pillow's `Image.open(path).convert("RGB")`) runs on the device (rpo_amd/jpeg.py), bit-identical to it.  Sizes
+        come from the headers, so the packing plan is the one `DeviceImageSet(decoded)` computes.  Resident images are
+        uploaded compressed and decoded straight into their offsets of `buffer`; spilled ones are decoded on the device
+        in chunks and read back into `host_images`.  A file the device decoder refuses (progressive, CMYK, ...) goes
+        through `fallback(bytes) -> uint8 [H, W, 3]` (default: Pillow, if importable) and is uploaded as pixels.
+        `n_device` / `n_fallback` count the two routes; the set is otherwise indistinguishable from one built from
+        decoded arrays."""
+        from .jpeg import JpegCorrupt, JpegDecoder, JpegRefused, probe
+        if len(files) != len(labels):
+            raise ValueError(f"{len(files)} files, {len(labels)} labels")
+        datas, names = [], []
+        for i, f in enumerate(files):
+            if isinstance(f, (bytes, bytearray, memoryview)):
+                datas.append(bytes(f))
+                names.append(f"file {i}")
+            else:
+                with open(f, "rb") as fh:
+                    datas.append(fh.read())
+                names.append(str(f))
+        infos, decoded = [], {}
+        for i, data in enumerate(datas):
+            try:
+                infos.append(probe(data))
+            except JpegRefused as e:
+                infos.append(None)
+                if fallback is None:
+                    try:
+                        import io
+                        from PIL import Image
+                    except ImportError:
+                        raise JpegRefused(e.code, f"{names[i]}: {e.reason}; no fallback decoder was given and Pillow is "
+                                                  "not importable") from e
+                    fallback = lambda b: np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))   # noqa: E731
+                im = np.ascontiguousarray(fallback(data))
+                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                    raise ValueError(f"{names[i]}: fallback must return a uint8 array of shape [H, W, 3]")
+                decoded[i] = im
+        self = cls.__new__(cls)
+        self.dev = torch.device(device)
+        if self.dev.type == "cuda" and self.dev.index is None:
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.sizes = [(int(decoded[i].shape[0]), int(decoded[i].shape[1])) if info is None
+                      else (int(info.height), int(info.width)) for i, info in enumerate(infos)]
+        self.labels = [int(y) for y in labels]
+        self.plan = plan_packing(self.sizes, budget_bytes, max_batch)
+        if n_cls is not None:
+            self.check_labels(n_cls)
+        p = self.plan
+        self.n_fallback = len(decoded)
+        self.n_device = len(datas) - self.n_fallback
+        self.buffer = torch.empty(max(16, p.resident_bytes + 2 * p.tail_bytes), dtype=torch.uint8, device=self.dev)
+        self.labels_dev = torch.tensor(self.labels, dtype=torch.int64, device=self.dev)
+        self._tail = None
+        self.host_images = {i: decoded[i] for i in p.spilled if i in decoded}
+        dec = JpegDecoder(self.dev, chunk_images)
+        with torch.cuda.device(self.dev):
+            for i, im in decoded.items():           # refused files that are resident: uploaded as pixels, as in _upload
+                if p.offsets[i] >= 0:
+                    self.buffer[p.offsets[i]:p.offsets[i] + im.size].copy_(torch.from_numpy(im.reshape(-1)))
+            res = [i for i, info in enumerate(infos) if info is not None and p.offsets[i] >= 0]
+            st = dec.decode_into([datas[i] for i in res], self.buffer, [p.offsets[i] for i in res], [infos[i] for i in res],
+                                 raise_corrupt=False)
+            for k in np.flatnonzero(st):
+                raise JpegCorrupt(res[k], int(st[k]))          # the index in `files`, not in the resident subset
+            spill = [i for i, info in enumerate(infos) if info is not None and p.offsets[i] < 0]
+            for lo in range(0, len(spill), chunk_images):
+                part = spill[lo:lo + chunk_images]
+                try:
+                    buf, offs, _ = dec.decode([datas[i] for i in part])
+                except JpegCorrupt as e:
+                    raise JpegCorrupt(part[e.index], e.status) from None
+                flat = buf.cpu().numpy()            # one read-back per chunk
+                for i, o in zip(part, offs):
+                    H, W = self.sizes[i]
+                    self.host_images[i] = flat[o:o + H * W * 3].reshape(H, W, 3).copy()
+        return self
+
 
 def build_transform(cfg: InputConfig, is_train: bool, device, max_batch: int = 32, **kw) -> DeviceTransform:
     """Counterpart of Dassl's `build_transform(cfg, is_train)` for the choices the RPO configs make."""
