@@ -186,6 +186,12 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// Block bid of nwg runs on XCD bid % 8: its place in an order that gives every XCD one contiguous run of the nwg places
+__device__ __forceinline__ int xcd_run(const int bid, const int nwg) {
+  const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
+  return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
+}
+
 // Workgroup id -> tile origin.  XCD-aware bijective remap (guide T1): XCD x = bid % 8 gets a contiguous run of
 // tiles; grouped order: consecutive ids sweep GM m-tiles of one n-tile, then the next n-tile, so the workgroups
 // resident on one XCD form a compact super-tile whose A and W panels fit its 4 MiB L2.
@@ -195,11 +201,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 template <int BM, int BN, int GM = RPO_GM>
 __device__ __forceinline__ void tile_origin(const GemmParams& p, int& m0, int& n0, const int bid, const int nwg) {
   const int tiles_n = (p.N + BN - 1) / BN;      // BM, BN are powers of two or constants: shifts / mul-shift
-  int wg;
-  {
-    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-    wg = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-  }
+  const int wg = xcd_run(bid, nwg);
   const int tiles_m = (p.M + BM - 1) / BM;
   const int per_group = GM * tiles_n;
   // these divisions sit in front of the first DMA of every workgroup: a float reciprocal + one correction step
@@ -911,6 +913,7 @@ __global__ __launch_bounds__(CfgPP::THREADS) void gemm_pp_kernel(const GemmParam
 }
 
 #include "gemm_w4.inc"
+#include "gemm_w4_rows.inc"
 #include "gemm_w4g.inc"
 #include "gemm_w4k.inc"
 #include "gemm_mlp.inc"
@@ -945,6 +948,11 @@ template <typename TIn, typename TOut, int EPI>
 constexpr bool big_ok_v = sizeof(TIn) == 2 && sizeof(TOut) == 2 &&
                           (EPI == RPO_EPI_BIAS || EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_LN_BIAS || EPI == RPO_EPI_LN_BIAS_QGELU);
 
+// 32-bit byte offsets inside the operand matrices (buffer loads of the one-wave-per-SIMD kernels)
+static inline bool fits32(const GemmParams& p) {
+  return (int64_t)p.M * p.lda * 2 < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
+}
+
 // Shape heuristic (measured on MI355X, tools/bench_gemm.py): see the Cfg comments.  Returns the tile_config value that
 // forces the kernel this call runs (> 0; launch() switches on it, rpo_gemm_nt_plan() reports it) or the RPO_E_* the call
 // refuses with.  Nothing is dereferenced.
@@ -954,10 +962,9 @@ int choose(const GemmParams& p) {
   // row units allow it (gemm_w4k.inc).  Its row statistics are over 96 columns, the generic epilogues' over 64: the
   // caller says which it expects (rpo_gemm_args.ln_group) and gets an error instead of the other layout.
   if constexpr (w4k_ok_v<TIn, TOut, EPI>) {
-    W4KPlan kplan;
-    const bool fits32 = (int64_t)p.M * p.lda * 2 < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
+    W4RowsPlan kplan;
     const int kgrp = w4k_plan(p, &kplan);                           // 0, or the geometry's statistics group (96 / 64)
-    const bool k_ok = p.split_k == 1 && fits32 && kgrp != 0 && aligned16(p.C) && p.ldc % 4 == 0 &&
+    const bool k_ok = p.split_k == 1 && fits32(p) && kgrp != 0 && aligned16(p.C) && p.ldc % 4 == 0 &&
                       (p.ln_stats == nullptr || p.ln_group == kgrp);
     if (k_ok && (p.force_cfg == 11 || p.force_cfg == 0)) return 11;
     if (p.force_cfg == 11 || (p.ln_stats != nullptr && p.ln_group != LN_GROUP)) return RPO_E_SHAPE;
@@ -982,13 +989,12 @@ int choose(const GemmParams& p) {
     // one-wave-per-SIMD kernel (gemm_w4.inc): 32-bit byte offsets inside the operand matrices, at least two 64-deep
     // k-tiles.  Bit-identical to the ping-pong kernel (tile_config 7) and the lock-step 256x256 one (3) and faster
     // than both (in-proj at B=32: 28.1 vs 34.3 / 29.5 us on one box), so it is what the heuristic picks.
-    const bool fits32 = (int64_t)p.M * p.lda * 2 < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
     constexpr bool epi_ln = EPI == RPO_EPI_LN_BIAS || EPI == RPO_EPI_LN_BIAS_QGELU;
-    const bool w4_ok = ok && fits32 && p.K >= 2 * CfgW4::BK && (!epi_ln || p.K <= 16 * p.ln_group);
+    const bool w4_ok = ok && fits32(p) && p.K >= 2 * CfgW4::BK && (!epi_ln || p.K <= 16 * p.ln_group);
     const bool wants_big = p.force_cfg == 0 && p.M >= 2048 && p.N >= 1536 && fills;
     // 224x384 tiles when they cover the output in exactly one round and 256x256 tiles do not (c_fc at B = 32)
     {
-      W4GPlan gplan;
+      W4RowsPlan gplan;
       const bool g_ok = w4_ok && w4g_plan(p, &gplan) != 0;
       const bool big_shape = p.force_cfg == 0 && p.M >= 2048 && p.N >= 1536;
       // ... or whole rounds of row-unit tiles (64 / 128 images: 2 / 4 rounds; 256x256 tiles would need 2.6 / 5.3)
@@ -1092,20 +1098,26 @@ extern "C" __attribute__((visibility("default"))) int rpo_debug_set_timeline(uns
 }
 #endif
 
+// What rpo_gemm_stats_group and rpo_gemm_hilo_ok both ask first.  < 0: bad arguments; 0: rpo_gemm_nt would not run the
+// one-round split-k kernel for these shapes / dtypes / row units; else the statistics group (= tile width) of the
+// geometry it would run
+static int w4k_group_query(const rpo_gemm_args* a) {
+  if (a == nullptr || a->M <= 0 || a->N <= 0 || a->K <= 0) return RPO_E_BADARG;
+  const bool in16 = a->in_dtype == RPO_BF16 || a->in_dtype == RPO_F16;
+  if (a->epilogue != RPO_EPI_BIAS_RESID || !in16 || a->out_dtype != RPO_F32 || a->split_k > 1) return 0;
+  GemmParams p{};
+  p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw;
+  p.seg_rows0 = a->seg_rows0; p.seg_rows1 = a->seg_rows1; p.seg1_row0 = a->seg1_row0;
+  W4RowsPlan q;
+  return fits32(p) ? w4k_plan(p, &q) : 0;
+}
+
 // Which partial-statistics layout a BIAS_RESID producer would write for these shapes / dtypes / row units when the choice
 // is left to the library: 96 when the one-round 224x96 kernel applies, else 64.  Looks at M, N, K, lda, ldw, the dtypes,
 // split_k and the row-unit hint only; nothing is dereferenced.
 extern "C" int rpo_gemm_stats_group(const rpo_gemm_args* a) {
-  if (a == nullptr || a->M <= 0 || a->N <= 0 || a->K <= 0) return RPO_E_BADARG;
-  const bool in16 = a->in_dtype == RPO_BF16 || a->in_dtype == RPO_F16;
-  if (a->epilogue != RPO_EPI_BIAS_RESID || !in16 || a->out_dtype != RPO_F32 || a->split_k > 1) return LN_GROUP;
-  GemmParams p{};
-  p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw;
-  p.seg_rows0 = a->seg_rows0; p.seg_rows1 = a->seg_rows1; p.seg1_row0 = a->seg1_row0;
-  W4KPlan q;
-  const bool fits32 = (int64_t)p.M * p.lda * 2 < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
-  const int kgrp = fits32 ? w4k_plan(p, &q) : 0;
-  return kgrp != 0 ? kgrp : LN_GROUP;
+  const int kgrp = w4k_group_query(a);
+  return kgrp < 0 ? kgrp : kgrp != 0 ? kgrp : LN_GROUP;
 }
 
 // Argument checks of rpo_gemm_nt and the kernel-side parameter block (shared with rpo_gemm_nt_pair)
@@ -1183,18 +1195,10 @@ static int gemm_prepare(const rpo_gemm_args* a, GemmParams& p) {
 }
 
 extern "C" int rpo_gemm_hilo_ok(const rpo_gemm_args* a) {
-  if (a == nullptr || a->M <= 0 || a->N <= 0 || a->K <= 0) return 0;
-  const bool in16 = a->in_dtype == RPO_BF16 || a->in_dtype == RPO_F16;
-  if (a->epilogue != RPO_EPI_BIAS_RESID || !in16 || a->out_dtype != RPO_F32 || a->split_k > 1 ||
-      (a->tile_config != 0 && a->tile_config != 11)) return 0;
-  GemmParams p{};
-  p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw;
-  p.seg_rows0 = a->seg_rows0; p.seg_rows1 = a->seg_rows1; p.seg1_row0 = a->seg1_row0;
-  W4KPlan q;
-  const bool fits32 = (int64_t)p.M * p.lda * 2 < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
-  const int kgrp = fits32 ? w4k_plan(p, &q) : 0;
+  const int kgrp = w4k_group_query(a);
+  if (kgrp <= 0 || (a->tile_config != 0 && a->tile_config != 11)) return 0;
   const int want = a->ln_group == 0 ? LN_GROUP : a->ln_group;
-  return kgrp != 0 && a->ldc % 4 == 0 && want == kgrp ? 1 : 0;
+  return a->ldc % 4 == 0 && want == kgrp ? 1 : 0;
 }
 
 // rpo_gemm_nt, or with plan_only its verdict (rpo_gemm_nt_plan): one path through the checks and the kernel choice
@@ -1239,11 +1243,8 @@ extern "C" int rpo_mlp_fused(const rpo_gemm_args* fc, const rpo_gemm_args* proj,
     return RPO_E_SHAPE;
   if (pf.split_k != 1 || pp.split_k != 1 || pf.force_cfg != 0 || pp.force_cfg != 0 || pf.M != pp.M || pp.K != pf.N ||
       proj->A != fc->C || pp.lda != pf.ldc) return RPO_E_SHAPE;
-  W4GPlan g;
-  W4KPlan k;
-  const bool fits32 = (int64_t)pf.M * pf.lda * 2 < (1ll << 31) && (int64_t)pf.N * pf.ldw * 2 < (1ll << 31) &&
-                      (int64_t)pp.M * pp.lda * 2 < (1ll << 31) && (int64_t)pp.N * pp.ldw * 2 < (1ll << 31);
-  if (!fits32 || w4g_plan(pf, &g) != 1 || !g.from_units || w4k_plan(pp, &k) != CfgW4K::BN || k.geo != CfgW4K::TM) return RPO_E_SHAPE;
+  W4RowsPlan g, k;
+  if (!fits32(pf) || !fits32(pp) || w4g_plan(pf, &g) != 1 || !g.from_units || w4k_plan(pp, &k) != CfgW4K::BN || k.geo != CfgW4K::TM) return RPO_E_SHAPE;
   if (g.rows0 != k.rows0 || g.rows1 != k.rows1 || g.seg1_base != k.seg1_base || g.tiles_m != k.tiles_m || g.tiles_n != 8 ||
       k.tiles_n != 8 || g.tiles_m * 8 > rpo_cu_count()) return RPO_E_SHAPE;
   if (pf.K < 2 * CfgW4G::BK || pf.N % 8 != 0 || pf.ldc % 8 != 0 || !aligned16(pf.C) || !aligned16(pp.C) || pp.ldc % 4 != 0 ||

@@ -26,13 +26,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const GemmParams pf, 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // this wave's stores of g (and u) are in the L2
   __syncthreads();                                                       // ... everybody's; c_fc's LDS staging is dead
   if (threadIdx.x == 0) {
-    int tile_m;
-    {
-      const int nwg = gridDim.x, bid = blockIdx.x;
-      const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-      const int wg = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-      tile_m = wg / tn_fc;
-    }
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int tile_m = xcd_run(bid, nwg) / tn_fc;                      // the row unit, as in the two bodies
     if (safe) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const GemmParams pf, 
 }
 
 template <typename T, int EPI_FC>
-int launch_mlp_fused(const GemmParams& pf, const GemmParams& pp, const W4GPlan& g, unsigned int* counters, int safe, hipStream_t s) {
+int launch_mlp_fused(const GemmParams& pf, const GemmParams& pp, const W4RowsPlan& g, unsigned int* counters, int safe, hipStream_t s) {
   static rpo_lds_mask_t lds_ok{0};
   auto kern = mlp_fused_kernel<T, EPI_FC>;
   constexpr int bytes = CfgW4G::SMEM > CfgW4K::SMEM ? CfgW4G::SMEM : CfgW4K::SMEM;

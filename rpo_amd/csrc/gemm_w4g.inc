@@ -11,7 +11,7 @@
 //   * per 16-deep k-step 10 fragment reads feed 21 MFMAs (0.48 reads per MFMA, as the 256x256 kernel), 19 DMA pieces
 //     per 64-deep k-tile and wave = one per 4.4 MFMAs;
 //   * LDS: 2 slots x (224 + 384) rows x 128 B = 152 KiB.
-// k-loop: generated (tools/gen_gemm_w4g.py -> gemm_w4g_asm.inc), same structure and hazard arguments as gemm_w4.inc:
+// k-loop: generated (tools/gen_gemm_w4.py -> gemm_w4g_asm.inc), same structure and hazard arguments as gemm_w4.inc:
 // p0 / p1 fetch the W pieces of tile t+1, p2 front-loads its reads, lgkmcnt(0) + vmcnt(0) + barrier, p3 reads tile
 // t+1 and fetches the A pieces of tile t+2 into the slot tile t just left.
 //
@@ -23,7 +23,7 @@
 // else would.
 #include "gemm_w4g_asm.inc"
 
-// Two geometries of the same kernel (k-loops: W4G_LOOP / W4G_LOOP_9X2 of gemm_w4g_asm.inc):
+// Two geometries of the same kernel (k-loops: W4G_LOOP_7X3 / W4G_LOOP_9X2 of gemm_w4g_asm.inc):
 //   7 x 3: tile 224 x 384, a wave 224 x 96 -- ViT-B/16: 197 + K <= 224 rows per image, 3072 = 8 x 384
 //   9 x 2: tile 288 x 256, a wave 288 x 64 -- ViT-L/14: 257 + K <= 288 rows per image, 4096 = 16 x 256 (16 images: 256 tiles)
 template <int TM_, int TN_>
@@ -57,8 +57,7 @@ __device__ __forceinline__ void gemm_w4g_body(const GemmParams p, const int rows
   int tile_m, tile_n;
   {
     const int nwg = gridDim.x, bid = blockIdx.x;
-    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-    const int wg = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
+    const int wg = xcd_run(bid, nwg);
     tile_m = wg / tiles_n;
     tile_n = wg - tile_m * tiles_n;
   }
@@ -129,50 +128,7 @@ __device__ __forceinline__ void gemm_w4g_body(const GemmParams p, const int rows
   uint32_t pf_touch = 0;
   if constexpr (!(EPI == RPO_EPI_LN_BIAS && CF::TM == 7)) pf_touch = prefetch_touch(p);
   RPO_STAMP(2);
-#define W4G_TAIL_OPERANDS                                                                                             \
-        [offw] "v"(offw), [aw] "v"(aw0), [ax] "v"(ax0), [srda] "s"(srda), [srdw] "s"(srdw), [ldsw] "s"(lds_w),           \
-        [nloop] "s"(nloop), [rsw] "s"(rsw)
-  if constexpr (CF::TM == 7) {
-#define W4G_OPERANDS                                                                                                  \
-      : "+v"(acc[0][0]), "+v"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[0][4]), "+a"(acc[0][5]),            \
-        "+a"(acc[0][6]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+a"(acc[1][2]), "+a"(acc[1][3]), "+a"(acc[1][4]),            \
-        "+a"(acc[1][5]), "+a"(acc[1][6]), "+v"(acc[2][0]), "+a"(acc[2][1]), "+a"(acc[2][2]), "+a"(acc[2][3]),            \
-        "+a"(acc[2][4]), "+a"(acc[2][5]), "+a"(acc[2][6])                                                               \
-      : [offa0] "v"(offa[0]), [offa1] "v"(offa[1]), [offa2] "v"(offa[2]), [offa3] "v"(offa[3]), [offa4] "v"(offa[4]),    \
-        [offa5] "v"(offa[5]), [offa6] "v"(offa[6]), W4G_TAIL_OPERANDS                                                   \
-      : W4G_CLOBBERS
-    if constexpr (!__is_same(TOut, f16_t)) {
-#define W4G_OP "v_mfma_f32_32x32x16_bf16"
-      asm volatile(W4G_LOOP W4G_OPERANDS);
-#undef W4G_OP
-    } else {
-#define W4G_OP "v_mfma_f32_32x32x16_f16"
-      asm volatile(W4G_LOOP W4G_OPERANDS);
-#undef W4G_OP
-    }
-#undef W4G_OPERANDS
-  } else {
-    static_assert(CF::TM == 7 || (CF::TM == 9 && CF::TN == 2), "no generated k-loop for this geometry");
-#define W4G_OPERANDS                                                                                                  \
-      : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[0][4]), "+a"(acc[0][5]),            \
-        "+a"(acc[0][6]), "+a"(acc[0][7]), "+a"(acc[0][8]), "+a"(acc[1][0]), "+a"(acc[1][1]), "+a"(acc[1][2]),            \
-        "+a"(acc[1][3]), "+a"(acc[1][4]), "+a"(acc[1][5]), "+a"(acc[1][6]), "+v"(acc[1][7]), "+v"(acc[1][8])             \
-      : [offa0] "v"(offa[0]), [offa1] "v"(offa[1]), [offa2] "v"(offa[2]), [offa3] "v"(offa[3]), [offa4] "v"(offa[4]),    \
-        [offa5] "v"(offa[5]), [offa6] "v"(offa[6]), [offa7] "v"(offa[CF::TM > 7 ? 7 : 0]),                              \
-        [offa8] "v"(offa[CF::TM > 8 ? 8 : 0]), W4G_TAIL_OPERANDS                                                        \
-      : W4G_CLOBBERS_9X2
-    if constexpr (!__is_same(TOut, f16_t)) {
-#define W4G_OP "v_mfma_f32_32x32x16_bf16"
-      asm volatile(W4G_LOOP_9X2 W4G_OPERANDS);
-#undef W4G_OP
-    } else {
-#define W4G_OP "v_mfma_f32_32x32x16_f16"
-      asm volatile(W4G_LOOP_9X2 W4G_OPERANDS);
-#undef W4G_OP
-    }
-#undef W4G_OPERANDS
-  }
-#undef W4G_TAIL_OPERANDS
+  W4G_KLOOP(CF, (__is_same(TOut, f16_t)));                         // gemm_w4g_asm.inc: loop and operand list of this geometry
   RPO_STAMP(60);
   asm volatile("" :: "v"(pf_touch));
 
@@ -361,54 +317,28 @@ __global__ __launch_bounds__(256, 1) void gemm_w4g_kernel(const GemmParams p, co
 // Tiling of the 224x384 kernel for an [M, N] output, or false if it does not apply: N a multiple of 384, the tiles fit
 // ONE round of the 256 CUs and fill most of it.  With the caller's row-unit hint (rpo_gemm_args.seg_*) one tile = one
 // unit; otherwise contiguous tiles of equal height.
-// one workgroup per CU and round: the tile count must fill (most of) a whole number of rounds of the 256 CUs -- one round
-// at 32 images, two at 64, four at 128
-static inline bool w4_rounds_ok(int tiles) {
-  const int rounds = (tiles + 255) / 256;
-#ifndef RPO_W4_MINFILL
-#define RPO_W4_MINFILL 81
-#endif
-  return rounds >= 1 && rounds <= 8 && tiles * 100 >= rounds * 256 * RPO_W4_MINFILL;
-}
-struct W4GPlan { int rows0, rows1, seg1_base, tiles_m, tiles_n; bool from_units; };
 template <typename CF>
-static inline bool w4g_plan_t(const GemmParams& p, W4GPlan* q) {
+static inline bool w4g_plan_t(const GemmParams& p, W4RowsPlan* q) {
   if (p.N % CF::BN != 0 || (int64_t)p.M * p.ldc * 2 >= (int64_t(1) << 31)) return false;   // 32-bit store offsets
-  const int tn = p.N / CF::BN;
-  if (p.seg_rows0 > 0 && p.seg_rows0 + p.seg_rows1 <= CF::BM && p.seg1_row0 % p.seg_rows0 == 0) {
-    const int units = p.seg1_row0 / p.seg_rows0;
-    if (p.M - p.seg1_row0 == units * p.seg_rows1 && w4_rounds_ok(units * tn)) {
-      *q = W4GPlan{p.seg_rows0, p.seg_rows1, p.seg1_row0, units, tn, true};
-      return true;
-    }
-  }
-  const int tm = (p.M + CF::BM - 1) / CF::BM;
+  if (w4_unit_plan<CF>(p, q)) return true;
+  const int tn = p.N / CF::BN, tm = (p.M + CF::BM - 1) / CF::BM;
   if (!w4_rounds_ok(tm * tn)) return false;
-  *q = W4GPlan{(p.M + tm - 1) / tm, 0, p.M, tm, tn, false};
+  *q = W4RowsPlan{(p.M + tm - 1) / tm, 0, p.M, tm, tn, false, CF::TM};
   return true;
 }
 // 0: no geometry applies; 1: 224 x 384 tiles; 2: 288 x 256 tiles
-static inline int w4g_plan(const GemmParams& p, W4GPlan* q) {
+static inline int w4g_plan(const GemmParams& p, W4RowsPlan* q) {
   if (w4g_plan_t<CfgW4G>(p, q)) return 1;
   if (w4g_plan_t<CfgW4GL>(p, q)) return 2;
   return 0;
 }
 
-template <typename TOut, int EPI, typename CF>
-int launch_w4g_t(const GemmParams& p, const W4GPlan& q, hipStream_t s) {
-  static rpo_lds_mask_t lds_ok{0};
-  auto kern = gemm_w4g_kernel<TOut, EPI, CF>;
-  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), CF::SMEM, &lds_ok)) return rc;
-  hipLaunchKernelGGL(kern, dim3(q.tiles_m * q.tiles_n, 1), dim3(CF::THREADS), CF::SMEM, s, p, q.rows0, q.rows1,
-                     q.seg1_base, q.tiles_n);
-  return rpo_launch_status();
-}
 template <typename TOut, int EPI>
 int launch_w4g(const GemmParams& p, hipStream_t s) {
-  W4GPlan q;
+  W4RowsPlan q;
   switch (w4g_plan(p, &q)) {
-    case 1: return launch_w4g_t<TOut, EPI, CfgW4G>(p, q, s);
-    case 2: return launch_w4g_t<TOut, EPI, CfgW4GL>(p, q, s);
+    case 1: return launch_w4_rows<gemm_w4g_kernel<TOut, EPI, CfgW4G>, CfgW4G>(p, q, s);
+    case 2: return launch_w4_rows<gemm_w4g_kernel<TOut, EPI, CfgW4GL>, CfgW4GL>(p, q, s);
     default: return RPO_E_SHAPE;
   }
 }

@@ -10,7 +10,7 @@
 // (7 x 3 MFMA tiles, 336 registers), so here every wave holds the whole tile and the waves split the CONTRACTION:
 // wave w multiplies k-step w (16 of the 64 k's) of every k-tile.  Nothing staged in LDS is read twice -- LDS is only
 // the landing zone of the DMA -- so per wave and k-tile the loop is 10 DMA pieces, 10 fragment reads, 21 MFMAs
-// (tools/gen_gemm_w4k.py -> gemm_w4k_asm.inc).  The four partial tiles are summed in a fixed order by the epilogue
+// (tools/gen_gemm_w4.py -> gemm_w4k_asm.inc).  The four partial tiles are summed in a fixed order by the epilogue
 // (through LDS, 32 rows at a time), which then does what the BIAS_RESID epilogue of the other kernels does: bias +
 // residual -> fp32 C, the 16-bit copy (out2) and the partial LayerNorm statistics of the row -- over the tile's 96
 // columns (rpo_gemm_args.ln_group = 96).
@@ -18,7 +18,7 @@
 // Results: deterministic; NOT bit-identical to the other tile shapes (four-way split of the k sum).
 #include "gemm_w4k_asm.inc"
 
-// Three geometries (k-loops: W4K_LOOP / W4K_LOOP_9X2 / W4K_LOOP_8X3 of gemm_w4k_asm.inc):
+// Three geometries (k-loops: W4K_LOOP_7X3 / W4K_LOOP_9X2 / W4K_LOOP_8X3 of gemm_w4k_asm.inc):
 //   7 x 3, ring of 4: tile 224 x 96 -- ViT-B/16: 197 + K <= 224 rows per image, 768 = 8 x 96, statistics over 96 columns
 //   8 x 3, ring of 3: tile 256 x 96 -- ViT-B/16 with 225 .. 256 rows per image (K = 48: 245); 384 accumulator registers
 //                     (256 AGPR + 128 VGPR), its unrolled body entered like the 9 x 2 one
@@ -59,8 +59,7 @@ __device__ __forceinline__ void gemm_w4k_body(const GemmParams p, const int rows
   int tile_m, tile_n;
   {
     const int nwg = gridDim.x, bid = blockIdx.x;
-    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-    const int wg = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
+    const int wg = xcd_run(bid, nwg);
     tile_m = wg / tiles_n;
     tile_n = wg - tile_m * tiles_n;
   }
@@ -144,71 +143,7 @@ __device__ __forceinline__ void gemm_w4k_body(const GemmParams p, const int rows
   }
 #endif
   RPO_STAMP(2);
-#define W4K_TAIL_OPERANDS                                                                                             \
-        [offw] "v"(offw), [aw] "v"(aw0), [ax] "v"(ax0), [srda] "s"(srda), [srdw] "s"(srdw), [ldsw] "s"(lds_w),           \
-        [nloop] "s"(nloop), [rsw] "s"(rsw)
-  if constexpr (CF::TM == 7) {
-#define W4K_OPERANDS                                                                                                  \
-      : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[0][4]), "+a"(acc[0][5]),            \
-        "+a"(acc[0][6]), "+a"(acc[1][0]), "+a"(acc[1][1]), "+a"(acc[1][2]), "+a"(acc[1][3]), "+a"(acc[1][4]),            \
-        "+a"(acc[1][5]), "+a"(acc[1][6]), "+a"(acc[2][0]), "+a"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[2][3]),            \
-        "+v"(acc[2][4]), "+v"(acc[2][5]), "+v"(acc[2][6])                                                               \
-      : [offa0] "v"(offa[0]), [offa1] "v"(offa[1]), [offa2] "v"(offa[2]), [offa3] "v"(offa[3]), [offa4] "v"(offa[4]),    \
-        [offa5] "v"(offa[5]), [offa6] "v"(offa[6]), W4K_TAIL_OPERANDS                                                   \
-      : W4K_CLOBBERS
-    if constexpr (!__is_same(TAct, f16_t)) {
-#define W4K_OP "v_mfma_f32_32x32x16_bf16"
-      asm volatile(W4K_LOOP W4K_OPERANDS);
-#undef W4K_OP
-    } else {
-#define W4K_OP "v_mfma_f32_32x32x16_f16"
-      asm volatile(W4K_LOOP W4K_OPERANDS);
-#undef W4K_OP
-    }
-#undef W4K_OPERANDS
-  } else if constexpr (CF::TM == 8) {
-    static_assert(CF::TN == 3 && CF::RING == 3, "no generated k-loop for this geometry");
-#define W4K_OPERANDS                                                                                                  \
-      : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[0][4]), "+a"(acc[0][5]),            \
-        "+a"(acc[0][6]), "+a"(acc[0][7]), "+a"(acc[1][0]), "+a"(acc[1][1]), "+a"(acc[1][2]), "+a"(acc[1][3]),            \
-        "+a"(acc[1][4]), "+a"(acc[1][5]), "+a"(acc[1][6]), "+a"(acc[1][7]), "+v"(acc[2][0]), "+v"(acc[2][1]),            \
-        "+v"(acc[2][2]), "+v"(acc[2][3]), "+v"(acc[2][4]), "+v"(acc[2][5]), "+v"(acc[2][6]), "+v"(acc[2][7])             \
-      : [offa0] "v"(offa[0]), [offa1] "v"(offa[1]), [offa2] "v"(offa[2]), [offa3] "v"(offa[3]), [offa4] "v"(offa[4]),    \
-        [offa5] "v"(offa[5]), [offa6] "v"(offa[6]), [offa7] "v"(offa[CF::TM > 7 ? 7 : 0]), [entry] "s"(entry),          \
-        W4K_TAIL_OPERANDS                                                                                               \
-      : W4K_CLOBBERS_8X3
-    if constexpr (!__is_same(TAct, f16_t)) {
-#define W4K_OP "v_mfma_f32_32x32x16_bf16"
-      asm volatile(W4K_LOOP_8X3 W4K_OPERANDS);
-#undef W4K_OP
-    } else {
-#define W4K_OP "v_mfma_f32_32x32x16_f16"
-      asm volatile(W4K_LOOP_8X3 W4K_OPERANDS);
-#undef W4K_OP
-    }
-#undef W4K_OPERANDS
-  } else {
-    static_assert(CF::TM == 7 || (CF::TM == 9 && CF::TN == 2 && CF::RING == 3), "no generated k-loop for this geometry");
-#define W4K_OPERANDS                                                                                                  \
-      : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[0][4]), "+a"(acc[0][5]),            \
-        "+a"(acc[0][6]), "+a"(acc[0][7]), "+a"(acc[0][8]), "+a"(acc[1][0]), "+a"(acc[1][1]), "+a"(acc[1][2]),            \
-        "+a"(acc[1][3]), "+a"(acc[1][4]), "+a"(acc[1][5]), "+a"(acc[1][6]), "+v"(acc[1][7]), "+v"(acc[1][8])             \
-      : [offa0] "v"(offa[0]), [offa1] "v"(offa[1]), [offa2] "v"(offa[2]), [offa3] "v"(offa[3]), [offa4] "v"(offa[4]),    \
-        [offa5] "v"(offa[5]), [offa6] "v"(offa[6]), [offa7] "v"(offa[CF::TM > 7 ? 7 : 0]),                              \
-        [offa8] "v"(offa[CF::TM > 8 ? 8 : 0]), [entry] "s"(entry), W4K_TAIL_OPERANDS                                    \
-      : W4K_CLOBBERS_9X2
-    if constexpr (!__is_same(TAct, f16_t)) {
-#define W4K_OP "v_mfma_f32_32x32x16_bf16"
-      asm volatile(W4K_LOOP_9X2 W4K_OPERANDS);
-#undef W4K_OP
-    } else {
-#define W4K_OP "v_mfma_f32_32x32x16_f16"
-      asm volatile(W4K_LOOP_9X2 W4K_OPERANDS);
-#undef W4K_OP
-    }
-#undef W4K_OPERANDS
-  }
-#undef W4K_TAIL_OPERANDS
+  W4K_KLOOP(CF, (__is_same(TAct, f16_t)));                         // gemm_w4k_asm.inc: loop and operand list of this geometry
   RPO_STAMP(60);
   asm volatile("" :: "v"(pf_touch), "v"(rs_touch));
 
@@ -362,24 +297,18 @@ __global__ __launch_bounds__(256, 1) void gemm_w4k_kernel(const GemmParams p, co
 
 // Applies when the caller's row units (rpo_gemm_args.seg_*) give whole rounds of tiles: BIAS_RESID, 16-bit A / W, fp32 C,
 // N a multiple of the tile width, an admitted number of k-tiles, and statistics (if any) over tile-width column groups.
-struct W4KPlan { int rows0, rows1, seg1_base, tiles_m, tiles_n, geo; };
 template <typename CF>
-static inline bool w4k_plan_t(const GemmParams& p, W4KPlan* q) {
-  if (p.N % CF::BN != 0 || p.K % CF::BK != 0) return false;
+static inline bool w4k_plan_t(const GemmParams& p, W4RowsPlan* q) {
+  if (p.K % CF::BK != 0) return false;
   const int nk = p.K / CF::BK;
   if (nk < CF::RING) return false;
   if constexpr (CF::RING == 4) { if (nk % 4 != 0) return false; }          // loop entered at position 0 only
-  else { if (nk % 6 != 0 && nk % 6 != 4) return false; }                   // entry positions 3 / 5 (tools/gen_gemm_w4k.py)
-  const int tn = p.N / CF::BN;
-  if (p.seg_rows0 <= 0 || p.seg_rows0 + p.seg_rows1 > CF::BM || p.seg1_row0 % p.seg_rows0 != 0) return false;
-  const int units = p.seg1_row0 / p.seg_rows0;
-  if (p.M - p.seg1_row0 != units * p.seg_rows1 || !w4_rounds_ok(units * tn)) return false;
-  *q = W4KPlan{p.seg_rows0, p.seg_rows1, p.seg1_row0, units, tn, CF::TM};
-  return true;
+  else { if (nk % 6 != 0 && nk % 6 != 4) return false; }                   // entry positions 3 / 5 (tools/gen_gemm_w4.py)
+  return w4_unit_plan<CF>(p, q);
 }
 // 0: no geometry applies; else the statistics group width (= tile width) of the geometry that does: 96 or 64
 // (q->geo = its TM: 7, 8 or 9)
-static inline int w4k_plan(const GemmParams& p, W4KPlan* q) {
+static inline int w4k_plan(const GemmParams& p, W4RowsPlan* q) {
   if (w4k_plan_t<CfgW4K>(p, q)) return CfgW4K::BN;
 #ifndef RPO_W4K_NO_8X3
   if (w4k_plan_t<CfgW4K8>(p, q)) return CfgW4K8::BN;
@@ -388,23 +317,14 @@ static inline int w4k_plan(const GemmParams& p, W4KPlan* q) {
   return 0;
 }
 
-template <typename TAct, typename CF>
-int launch_w4k_t(const GemmParams& p, const W4KPlan& q, hipStream_t s) {
-  static rpo_lds_mask_t lds_ok{0};
-  auto kern = gemm_w4k_kernel<TAct, CF>;
-  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), CF::SMEM, &lds_ok)) return rc;
-  hipLaunchKernelGGL(kern, dim3(q.tiles_m * q.tiles_n, 1), dim3(CF::THREADS), CF::SMEM, s, p, q.rows0, q.rows1,
-                     q.seg1_base, q.tiles_n);
-  return rpo_launch_status();
-}
 template <typename TAct>
 int launch_w4k(const GemmParams& p, hipStream_t s) {
-  W4KPlan q;
+  W4RowsPlan q;
   if (w4k_plan(p, &q) == 0) return RPO_E_SHAPE;
   switch (q.geo) {
-    case CfgW4K::TM: return launch_w4k_t<TAct, CfgW4K>(p, q, s);
-    case CfgW4K8::TM: return launch_w4k_t<TAct, CfgW4K8>(p, q, s);
-    case CfgW4KL::TM: return launch_w4k_t<TAct, CfgW4KL>(p, q, s);
+    case CfgW4K::TM: return launch_w4_rows<gemm_w4k_kernel<TAct, CfgW4K>, CfgW4K>(p, q, s);
+    case CfgW4K8::TM: return launch_w4_rows<gemm_w4k_kernel<TAct, CfgW4K8>, CfgW4K8>(p, q, s);
+    case CfgW4KL::TM: return launch_w4_rows<gemm_w4k_kernel<TAct, CfgW4KL>, CfgW4KL>(p, q, s);
     default: return RPO_E_SHAPE;
   }
 }
