@@ -255,11 +255,32 @@ int rpo_img_embed_norm_rows(float* x_pre, int64_t ldx, const float* cls, const f
                             const float* b1, void* h, int64_t ldh, int h_dtype, int B, int N, int Kp, int d,
                             float eps, int row0, int row1, void* stream);
 
+/* (ABI 8 addition) The same with one prompt set per GROUP of images: set g = img_prompt + g * prompt_stride ([Kp, d] each,
+ * prompt_stride in floats, >= Kp * d and a multiple of 4), and image b takes its prompt rows from set b / images_per_group
+ * -- several RPO runs (trainers/rpo.py:201-204 once per run) sharing one pass over the frozen image tower.  Row by row the
+ * bits of rpo_img_embed_norm_rows called with that set's prompt; images_per_group = B is that call.
+ * B % images_per_group != 0, or overlapping sets (prompt_stride < Kp * d): RPO_E_SHAPE; a prompt_stride that is not a
+ * multiple of 4 floats: RPO_E_ALIGN (with one set the stride is not looked at). */
+int rpo_img_embed_norm_grouped(float* x_pre, int64_t ldx, const float* cls, const float* pos0, const float* img_prompt,
+                               const float* g_pre, const float* b_pre, float* x0, int64_t ldx0, const float* g1,
+                               const float* b1, void* h, int64_t ldh, int h_dtype, int B, int N, int Kp, int d,
+                               float eps, int row0, int row1, int images_per_group, int64_t prompt_stride, void* stream);
+
 /* dst[g*rows + i, :] = src[i, :]  (text prompts written into every class, trainers/rpo.py:176-177) */
 int rpo_broadcast_rows(const float* src, float* dst, int64_t ld, int groups, int rows, int d, void* stream);
 
 /* out[i, :] = sum_g src[g*rows + i, :] in fixed order g = 0..groups-1 (autograd of .repeat()) */
 int rpo_reduce_groups(const float* src, int64_t ld, float* out, int groups, int rows, int d, void* stream);
+
+/* (ABI 8 additions) Both for `sets` prompt sets in one launch each (several RPO runs in one step):
+ *   dst[(s*groups + g)*rows + i, :] = src[s * src_set_stride + i * d ...]  set s of src: [rows, d] at s * src_set_stride
+ *   out[s * out_set_stride + i * d ...] = sum_g src[(s*groups + g)*rows + i, :]
+ * (strides in floats: the sets may be rows of a wider parameter / gradient buffer) with g in the order (and on the kernel) rpo_reduce_groups uses for `groups`: per set the bits of the plain calls on the
+ * set's slices.  sets = 1 is the plain call. */
+int rpo_broadcast_rows_sets(const float* src, int64_t src_set_stride, float* dst, int64_t ld, int sets, int groups, int rows,
+                            int d, void* stream);
+int rpo_reduce_groups_sets(const float* src, int64_t ld, float* out, int64_t out_set_stride, int sets, int groups, int rows,
+                           int d, void* stream);
 
 /* Read-only masked attention of the image tower, all heads (head_dim 64), all B images.
  * q, k, v: act-dtype matrices in the row layout above with leading dimension ld (typically
@@ -311,6 +332,19 @@ int rpo_text_attn_bwd(const void* q, int64_t ldq, const void* kc, const void* vc
                       const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
                       const int32_t* len, int n_cls, int rows, int Lmax, int H, float scale, void* stream);
 
+/* (ABI 8 additions) The causal = 0 forward and its backward for n_cls VIRTUAL classes on a SHARED cache of n_kv real
+ * classes (n_cls a multiple of n_kv, else RPO_E_SHAPE): virtual class v has its own `rows` query rows (q / out / da / dq:
+ * [n_cls * rows, ld*]) and reads len[v % n_kv] and the cache rows (v % n_kv) * Lmax ... of kc, vc [n_kv * Lmax, ldkv];
+ * len: int32 [n_kv].  S prompt sets of one class set are n_cls = S * n_kv virtual classes: the cache is read, never
+ * replicated (one copy is ~1.9 GB in 16-bit at 1000 classes).  Same kernels and kernel choice as the plain calls; the bits
+ * are those of the plain calls on a cache and `len` replicated n_cls / n_kv times.  n_kv = n_cls is the plain call. */
+int rpo_text_attn_fwd_shared(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
+                             void* out, int64_t ldo, int dtype, const int32_t* len, int n_cls, int n_kv, int rows,
+                             int Lmax, int H, float scale, void* stream);
+int rpo_text_attn_bwd_shared(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
+                             const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
+                             const int32_t* len, int n_cls, int n_kv, int rows, int Lmax, int H, float scale, void* stream);
+
 /* Dense backward of the text tower's causal attention: dq, dk, dv for ALL rows of every class (q, k, v, their
  * gradients: [n_cls * Lmax, ld / ldd], class c = rows c*Lmax .. c*Lmax + len[c]; row t reads keys [0, min(t + 1, len[c]))
  * as rpo_text_attn_fwd with causal = 1), given d_out = dL/d(attention output).  Replaces autograd of
@@ -350,6 +384,20 @@ int rpo_head_fwd_bwd(const float* img_f, const float* text_f, const int64_t* lab
 int rpo_head_fwd_bwd_act(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
                          float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_f_act,
                          void* d_text_f_act, int act_dtype, int B, int C, int K, int e, float* workspace, void* stream);
+
+/* (ABI 8 additions) S independent heads in the launches of one (the group is a grid dimension: the launch count does not
+ * grow with S): img_f [S*B, K, e], text_f [S*C, K, e], label [S*B] (or NULL: eval, logits only), logits [S*B, C], loss [S],
+ * gradients like the inputs.  Group s pairs images [s B, (s+1) B) with text features [s C, (s+1) C) ONLY; loss[s] is the
+ * mean over its own B images, and an out-of-range target poisons the loss and gradients of its own group alone.  Both
+ * class-count regimes of rpo_head_fwd_bwd (chosen from B, C, e as there).  Per group the bits of rpo_head_fwd_bwd[_act]
+ * on the group's slices.  workspace: at least S * rpo_head_workspace_floats(B, C, K, e) floats.  1 <= S <= 1024. */
+int rpo_head_fwd_bwd_grouped(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                             float* logits, float* loss, float* d_img_f, float* d_text_f,
+                             int S, int B, int C, int K, int e, float* workspace, void* stream);
+int rpo_head_fwd_bwd_grouped_act(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                                 float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_f_act,
+                                 void* d_text_f_act, int act_dtype, int S, int B, int C, int K, int e, float* workspace,
+                                 void* stream);
 
 /* Linear-probe head, cross-entropy and the gradient of the probe layer (trainers/linear_prob.py:61-95, :151-184):
  *   z      = img_f . w^T + bias                 (lp_layer = nn.Linear(e, e) on the UN-normalised image feature, :89-90)
@@ -409,7 +457,8 @@ int rpo_attnpool_attn(const float* q, int64_t ldq, const void* kv, void* out, in
 
 /* torch.optim.SGD (dampening 0, no nesterov) on n fp32 scalars (trainers/rpo.py:274,309):
  *   g' = grad_scale * g + wd * p;  buf = first ? g' : momentum * buf + g';  p -= lr * buf
- * grad_scale = 1 / world_size after a sum all-reduce. */
+ * grad_scale = 1 / world_size after a sum all-reduce.  Elementwise: one call over the flat [S, K*d_t + K*d_v] buffers of S
+ * runs that share the rate is S calls on the rows, bit for bit. */
 int rpo_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd,
                  float grad_scale, int first_step, void* stream);
 

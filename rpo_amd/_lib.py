@@ -131,9 +131,13 @@ SIGNATURES = {
                                    c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_img_embed_norm_rows": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32,
                                         c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp]),
+    "rpo_img_embed_norm_grouped": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                           c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_i32, c_i64, c_vp]),
     "rpo_img_assemble": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "rpo_broadcast_rows": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "rpo_reduce_groups": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "rpo_broadcast_rows_sets": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rpo_reduce_groups_sets": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "rpo_attn_readonly_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
                                       c_f32, c_vp]),
     "rpo_attn_readonly_fwd_rows": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
@@ -146,6 +150,10 @@ SIGNATURES = {
                                   c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_text_attn_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp,
                                   c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "rpo_text_attn_fwd_shared": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32,
+                                         c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "rpo_text_attn_bwd_shared": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp,
+                                         c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_text_attn_bwd_dense": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp,
                                         c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_metanet_fwd": (c_i32, [c_vp] * 8 + [c_i32] * 4 + [c_vp]),
@@ -155,6 +163,10 @@ SIGNATURES = {
                                  c_vp, c_vp]),
     "rpo_head_fwd_bwd_act": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_i32, c_vp, c_vp]),
+    "rpo_head_fwd_bwd_grouped": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                         c_vp, c_vp]),
+    "rpo_head_fwd_bwd_grouped_act": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                             c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rpo_lp_head_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "rpo_lp_head_fwd_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                     c_vp, c_vp]),

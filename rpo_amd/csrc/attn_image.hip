@@ -1536,14 +1536,15 @@ template <typename T, bool BWD, int NKT>
 __global__ __launch_bounds__(64) void text_attn_wave_kernel(const T* q, int64_t ldq, const T* kc, const T* vc, int64_t ldkv,
                                                             const T* da, int64_t ldda, T* out, int64_t ldo,
                                                             const int32_t* __restrict__ len, int rows, int Lmax, int H,
-                                                            float scale) {
+                                                            float scale, int n_kv) {
   const int lane = threadIdx.x, half = lane >> 5, l31 = lane & 31;
   const int c = blockIdx.x / H, h = blockIdx.x % H;
-  const int L = min(len[c], Lmax);
+  const int ckv = c % n_kv;                // the cached class this (virtual) class reads: c itself when n_kv = n_cls
+  const int L = min(len[ckv], Lmax);
   RowFrag<T> kf[NKT], vf[NKT];
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {          // keys >= L: the last key again (scores masked, p = 0 exactly)
-    const int64_t base = ((int64_t)c * Lmax + max(min(32 * t + l31, L - 1), 0)) * ldkv + h * 64;
+    const int64_t base = ((int64_t)ckv * Lmax + max(min(32 * t + l31, L - 1), 0)) * ldkv + h * 64;
     kf[t].load(kc + base, half);
     vf[t].load(vc + base, half);
   }
@@ -1631,12 +1632,12 @@ __global__ __launch_bounds__(64) void text_attn_wave_kernel(const T* q, int64_t 
 
 template <typename T, bool BWD>
 int launch_text_wave(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv, const void* da, int64_t ldda,
-                     void* out, int64_t ldo, const int32_t* len, int n_cls, int rows, int Lmax, int H, float scale,
+                     void* out, int64_t ldo, const int32_t* len, int n_cls, int n_kv, int rows, int Lmax, int H, float scale,
                      hipStream_t s) {
 #define RPO_TW(NKT)                                                                                                   \
   hipLaunchKernelGGL((text_attn_wave_kernel<T, BWD, NKT>), dim3(n_cls * H), dim3(64), 0, s, static_cast<const T*>(q), \
                      ldq, static_cast<const T*>(kc), static_cast<const T*>(vc), ldkv, static_cast<const T*>(da), ldda, \
-                     static_cast<T*>(out), ldo, len, rows, Lmax, H, scale)
+                     static_cast<T*>(out), ldo, len, rows, Lmax, H, scale, n_kv)
   if (Lmax <= 32) RPO_TW(1);
   else if (Lmax <= 64) RPO_TW(2);
   else RPO_TW(3);
@@ -1650,16 +1651,16 @@ int launch_text_wave(const void* q, int64_t ldq, const void* kc, const void* vc,
 // 16-bit storage, rows <= 64 prompt queries per class, Lmax <= 96 keys, 16-byte aligned rows: the one-wave kernel above;
 // RPO_E_SHAPE otherwise (the caller, attn_text.hip, then runs its VALU kernel).  bwd: `da` = d(attention output), `out` = dq.
 int rpo_text_attn_wave(int bwd, const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv, const void* da,
-                       int64_t ldda, void* out, int64_t ldo, int dtype, const int32_t* len, int n_cls, int rows, int Lmax,
-                       int H, float scale, hipStream_t s) {
+                       int64_t ldda, void* out, int64_t ldo, int dtype, const int32_t* len, int n_cls, int n_kv, int rows,
+                       int Lmax, int H, float scale, hipStream_t s) {
   if ((dtype != RPO_BF16 && dtype != RPO_F16) || rows > 64 || Lmax > 96) return RPO_E_SHAPE;
   if (!aligned16(q) || (ldq * 2) % 16 != 0 || (reinterpret_cast<uintptr_t>(out) & 7u) || (ldo * 2) % 8 != 0) return RPO_E_SHAPE;
   if (bwd && (!aligned16(da) || (ldda * 2) % 16 != 0)) return RPO_E_SHAPE;
   if (dtype == RPO_BF16)
-    return bwd ? launch_text_wave<bf16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, rows, Lmax, H, scale, s)
-               : launch_text_wave<bf16_t, false>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, rows, Lmax, H, scale, s);
-  return bwd ? launch_text_wave<f16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, rows, Lmax, H, scale, s)
-             : launch_text_wave<f16_t, false>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, rows, Lmax, H, scale, s);
+    return bwd ? launch_text_wave<bf16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, n_kv, rows, Lmax, H, scale, s)
+               : launch_text_wave<bf16_t, false>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, n_kv, rows, Lmax, H, scale, s);
+  return bwd ? launch_text_wave<f16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, n_kv, rows, Lmax, H, scale, s)
+             : launch_text_wave<f16_t, false>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, n_kv, rows, Lmax, H, scale, s);
 }
 
 extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const void* v, int64_t ld, void* out,

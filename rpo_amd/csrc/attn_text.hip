@@ -22,13 +22,15 @@ __global__ __launch_bounds__(256) void text_attn_kernel(const T* __restrict__ q,
                                                         const T* __restrict__ kc, const T* __restrict__ vc,
                                                         int64_t ldkv, const T* __restrict__ da, int64_t ldda,
                                                         T* out, int64_t ldo, const int32_t* __restrict__ len,
-                                                        int rows, int Lmax, int H, int causal, float scale) {
+                                                        int rows, int Lmax, int H, int causal, float scale,
+                                                        int n_kv) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* Kf = reinterpret_cast<float*>(smem);
   float* Vf = Kf + Lmax * 65;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = blockIdx.x / H, h = blockIdx.x % H;
-  const int L = min(len[c], Lmax);
+  const int ckv = c % n_kv;                     // the cached class this (virtual) class reads: c itself when n_kv = n_cls
+  const int L = min(len[ckv], Lmax);
   // stage K and V head slices as fp32 [L][65]; 16-B global loads, all issued before the LDS writes
   constexpr int EPC = 16 / sizeof(T);          // elements per 16-B chunk
   constexpr int CPR = 64 / EPC;                // chunks per key row
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(256) void text_attn_kernel(const T* __restrict__ q,
     const int id = tid + it * 256;
     const int j = id / CPR, cch = id % CPR;
     if (j < L) {
-      const int64_t off = ((int64_t)c * Lmax + j) * ldkv + h * 64 + cch * EPC;
+      const int64_t off = ((int64_t)ckv * Lmax + j) * ldkv + h * 64 + cch * EPC;
       kv[it] = *reinterpret_cast<const uint4*>(kc + off);
       vv[it] = *reinterpret_cast<const uint4*>(vc + off);
     }
@@ -223,22 +225,24 @@ int launch_dense(const void* q, const void* k, const void* v, int64_t ld, const 
 template <typename T, bool BWD>
 int launch(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv, const void* da,
            int64_t ldda, void* out, int64_t ldo, const int32_t* len, int n_cls, int rows, int Lmax, int H,
-           int causal, float scale, hipStream_t s) {
+           int causal, float scale, int n_kv, hipStream_t s) {
   static rpo_lds_mask_t lds_ok{0};
   auto kern = text_attn_kernel<T, BWD>;
   const int bytes = 2 * Lmax * 65 * 4;
   if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), 2 * 128 * 65 * 4, &lds_ok)) return rc;
   hipLaunchKernelGGL(kern, dim3(n_cls * H, (rows + RPO_TEXT_ROWS_PER_WG - 1) / RPO_TEXT_ROWS_PER_WG), dim3(256), bytes, s, static_cast<const T*>(q), ldq,
                      static_cast<const T*>(kc), static_cast<const T*>(vc), ldkv, static_cast<const T*>(da), ldda,
-                     static_cast<T*>(out), ldo, len, rows, Lmax, H, causal, scale);
+                     static_cast<T*>(out), ldo, len, rows, Lmax, H, causal, scale, n_kv);
   return rpo_launch_status();
 }
 
 }  // namespace
 
-extern "C" int rpo_text_attn_fwd(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
-                                 void* out, int64_t ldo, int dtype, const int32_t* len, int n_cls, int rows,
-                                 int Lmax, int H, int causal, float scale, void* stream) {
+// n_kv < n_cls: the n_cls classes are VIRTUAL -- class v reads len[v % n_kv] and the cache rows of class v % n_kv
+// (rpo_text_attn_fwd_shared / _bwd_shared: several prompt sets against one cache); n_kv = n_cls is the plain call.
+static int text_attn_fwd_impl(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv, void* out,
+                              int64_t ldo, int dtype, const int32_t* len, int n_cls, int n_kv, int rows, int Lmax, int H,
+                              int causal, float scale, void* stream) {
   if (!q || !kc || !vc || !out || !len || n_cls <= 0 || rows <= 0 || Lmax <= 0 || H <= 0) return RPO_E_BADARG;
   if (Lmax > 128) return RPO_E_SHAPE;
   {
@@ -248,23 +252,22 @@ extern "C" int rpo_text_attn_fwd(const void* q, int64_t ldq, const void* kc, con
   hipStream_t s = static_cast<hipStream_t>(stream);
 #ifndef RPO_TEXT_ATTN_VALU
   if (!causal) {
-    const int rc = rpo_text_attn_wave(0, q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, dtype, len, n_cls, rows, Lmax, H, scale, s);
+    const int rc = rpo_text_attn_wave(0, q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, dtype, len, n_cls, n_kv, rows, Lmax, H, scale, s);
     if (rc != RPO_E_SHAPE) return rc;
   }
 #endif
   if (dtype == RPO_F16)
-    return launch<f16_t, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, s);
+    return launch<f16_t, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, n_kv, s);
   if (dtype == RPO_BF16)
-    return launch<bf16_t, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, s);
+    return launch<bf16_t, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, n_kv, s);
   if (dtype == RPO_F32)
-    return launch<float, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, s);
+    return launch<float, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, n_kv, s);
   return RPO_E_DTYPE;
 }
 
-extern "C" int rpo_text_attn_bwd(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
-                                 const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
-                                 const int32_t* len, int n_cls, int rows, int Lmax, int H, float scale,
-                                 void* stream) {
+static int text_attn_bwd_impl(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv, const void* da,
+                              int64_t ldda, void* dq, int64_t lddq, int dtype, const int32_t* len, int n_cls, int n_kv,
+                              int rows, int Lmax, int H, float scale, void* stream) {
   if (!q || !kc || !vc || !da || !dq || !len || n_cls <= 0 || rows <= 0 || Lmax <= 0 || H <= 0) return RPO_E_BADARG;
   if (Lmax > 128) return RPO_E_SHAPE;
   {
@@ -274,17 +277,47 @@ extern "C" int rpo_text_attn_bwd(const void* q, int64_t ldq, const void* kc, con
   hipStream_t s = static_cast<hipStream_t>(stream);
 #ifndef RPO_TEXT_ATTN_VALU
   {
-    const int rc = rpo_text_attn_wave(1, q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, dtype, len, n_cls, rows, Lmax, H, scale, s);
+    const int rc = rpo_text_attn_wave(1, q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, dtype, len, n_cls, n_kv, rows, Lmax, H, scale, s);
     if (rc != RPO_E_SHAPE) return rc;
   }
 #endif
   if (dtype == RPO_F16)
-    return launch<f16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, s);
+    return launch<f16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
   if (dtype == RPO_BF16)
-    return launch<bf16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, s);
+    return launch<bf16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
   if (dtype == RPO_F32)
-    return launch<float, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, s);
+    return launch<float, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
   return RPO_E_DTYPE;
+}
+
+extern "C" int rpo_text_attn_fwd(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
+                                 void* out, int64_t ldo, int dtype, const int32_t* len, int n_cls, int rows,
+                                 int Lmax, int H, int causal, float scale, void* stream) {
+  return text_attn_fwd_impl(q, ldq, kc, vc, ldkv, out, ldo, dtype, len, n_cls, n_cls, rows, Lmax, H, causal, scale, stream);
+}
+
+extern "C" int rpo_text_attn_bwd(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
+                                 const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
+                                 const int32_t* len, int n_cls, int rows, int Lmax, int H, float scale,
+                                 void* stream) {
+  return text_attn_bwd_impl(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, dtype, len, n_cls, n_cls, rows, Lmax, H, scale, stream);
+}
+
+extern "C" int rpo_text_attn_fwd_shared(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
+                                        void* out, int64_t ldo, int dtype, const int32_t* len, int n_cls, int n_kv,
+                                        int rows, int Lmax, int H, float scale, void* stream) {
+  if (n_kv <= 0) return RPO_E_BADARG;
+  if (n_cls % n_kv != 0) return RPO_E_SHAPE;
+  return text_attn_fwd_impl(q, ldq, kc, vc, ldkv, out, ldo, dtype, len, n_cls, n_kv, rows, Lmax, H, 0, scale, stream);
+}
+
+extern "C" int rpo_text_attn_bwd_shared(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
+                                        const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
+                                        const int32_t* len, int n_cls, int n_kv, int rows, int Lmax, int H, float scale,
+                                        void* stream) {
+  if (n_kv <= 0) return RPO_E_BADARG;
+  if (n_cls % n_kv != 0) return RPO_E_SHAPE;
+  return text_attn_bwd_impl(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, dtype, len, n_cls, n_kv, rows, Lmax, H, scale, stream);
 }
 
 extern "C" int rpo_text_attn_bwd_dense(const void* q, const void* k, const void* v, int64_t ld, const void* d_out,

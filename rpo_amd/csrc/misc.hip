@@ -79,15 +79,18 @@ __global__ void assemble_kernel(float* x, int64_t ldx, const float* __restrict__
   }
 }
 
-__global__ void broadcast_rows_kernel(const float* __restrict__ src, float* dst, int64_t ld, int rows, int d) {
-  const int r = blockIdx.x;                 // g*rows + i
-  const float* s = src + (int64_t)(r % rows) * d;
+__global__ void broadcast_rows_kernel(const float* __restrict__ src, float* dst, int64_t ld, int rows, int d,
+                                      int set_rows, int64_t src_stride) {
+  const int r = blockIdx.x;                 // (s*groups + g)*rows + i; set_rows = groups * rows (one set: s = 0)
+  const float* s = src + (int64_t)(r / set_rows) * src_stride + (int64_t)(r % rows) * d;
   float* o = dst + (int64_t)r * ld;
   for (int i = threadIdx.x; i < d; i += blockDim.x) o[i] = s[i];
 }
 
 __global__ void reduce_groups_kernel(const float* __restrict__ src, int64_t ld, float* out, int groups, int rows,
-                                     int d) {
+                                     int d, int64_t out_stride) {
+  src += (int64_t)blockIdx.y * groups * rows * ld;                  // blockIdx.y: the set (rpo_reduce_groups_sets)
+  out += (int64_t)blockIdx.y * out_stride;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= rows * d) return;
   const int i = idx / d, c = idx % d;
@@ -102,8 +105,10 @@ __global__ void reduce_groups_kernel(const float* __restrict__ src, int64_t ld, 
 // sums groups j, j + 8, ... in ascending order), then adds the 8 partial sums in thread-row order through LDS: a fixed
 // summation order (deterministic), 8 x the loads in flight and 8 x the workgroups.
 __global__ __launch_bounds__(256) void reduce_groups_wide_kernel(const float* __restrict__ src, int64_t ld, float* out,
-                                                                 int groups, int rows, int d) {
+                                                                 int groups, int rows, int d, int64_t out_stride) {
   __shared__ float part[8][32];
+  src += (int64_t)blockIdx.y * groups * rows * ld;                  // blockIdx.y: the set (rpo_reduce_groups_sets)
+  out += (int64_t)blockIdx.y * out_stride;
   const int cols = (d + 31) / 32;
   const int i = blockIdx.x / cols, c = (blockIdx.x % cols) * 32 + (threadIdx.x & 31), j = threadIdx.x >> 5;
   float s = 0.f;
@@ -192,11 +197,30 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 // normalisation launch, no unit-vector copies.  The inverse norms the backward needs are left in ni / nt by the blocks of
 // class 0 / image 0.  (A version with one block per image that looped over all C * K text rows took 150 us: 120 dependent
 // load -> reduce rounds per wave on 32 CUs.)
+// Several independent heads in one launch (rpo_head_fwd_bwd_grouped): group s pairs images [s B, (s + 1) B) with text
+// features [s C, (s + 1) C) only.  Every kernel below takes the group from a grid dimension and moves its pointers by the
+// group's strides (elements) before doing exactly what it does for a single head; a single head is group 0 of 1.
+struct HeadGroups {
+  int64_t img;      // B * K * e   (img_f, d_img_f, their act copies)
+  int64_t txt;      // C * K * e   (text_f, d_text_f, their act copies)
+  int64_t bc;       // B * C       (logits)
+  int64_t lab;      // B           (label)
+  int64_t ws;       // workspace floats per group (rpo_head_workspace_floats)
+};
+template <typename T> __device__ __forceinline__ T* head_shift(T* p, int64_t off) { return p == nullptr ? p : p + off; }
+__device__ __forceinline__ void* head_shift16(void* p, int64_t off) {            // act copies: 2-byte elements
+  return p == nullptr ? p : static_cast<void*>(static_cast<uint16_t*>(p) + off);
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restrict__ f_img, const float* __restrict__ f_txt,
                                                           float* ni, float* nt, float* logits, int C, int K, int e,
-                                                          float mul) {
+                                                          float mul, HeadGroups hg) {
   __shared__ float red[4];
+  {
+    const int64_t s = blockIdx.z;
+    f_img += s * hg.img; f_txt += s * hg.txt; ni += s * hg.ws; nt += s * hg.ws; logits += s * hg.bc;
+  }
   const int c = blockIdx.x, b = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float acc = 0.f;
@@ -243,8 +267,13 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
 // per image: loss_b = logsumexp - logit[label]; dl[b,c] = (softmax - onehot) * gmul
 __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ logits,
                                                       const int64_t* __restrict__ label, float* dl,
-                                                      float* loss_b, int C, float gmul, float* dlT, int B) {
+                                                      float* loss_b, int C, float gmul, float* dlT, int B,
+                                                      HeadGroups hg) {
   __shared__ float red[4];
+  {
+    const int64_t s = blockIdx.y;
+    logits += s * hg.bc; label += s * hg.lab; dl += s * hg.ws; loss_b += s * hg.ws; dlT = head_shift(dlT, s * hg.ws);
+  }
   const int b = blockIdx.x;
   const float* z = logits + (int64_t)b * C;
   float m = -INFINITY;
@@ -286,9 +315,16 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                                                        int B, int C, int K, int e, const float* loss_b, float* loss,
                                                        const float* __restrict__ logits,
                                                        const int64_t* __restrict__ label, float gmul,
-                                                       void* d_img_a, void* d_text_a, int act_dtype) {
+                                                       void* d_img_a, void* d_text_a, int act_dtype, HeadGroups hg) {
   extern __shared__ __attribute__((aligned(16))) char head_smem[];
   __shared__ float red[4];
+  {
+    const int64_t s = blockIdx.y;
+    dl += s * hg.ws; ni += s * hg.ws; nt += s * hg.ws; loss_b += s * hg.ws;
+    f_img += s * hg.img; f_txt += s * hg.txt; d_img_f += s * hg.img; d_text_f += s * hg.txt;
+    d_img_a = head_shift16(d_img_a, s * hg.img); d_text_a = head_shift16(d_text_a, s * hg.txt);
+    logits += s * hg.bc; label = head_shift(label, s * hg.lab); loss = head_shift(loss, s);
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool img = (int)blockIdx.x < B * K;
   const int row = img ? blockIdx.x : blockIdx.x - B * K;            // g*K + i
@@ -396,8 +432,13 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 __device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 __global__ __launch_bounds__(64) void head_pairs_kernel(const float* __restrict__ f_img, const float* __restrict__ f_txt,
-                                                        float* ni, float* nt, float* part, int B, int C, int K, int e) {
+                                                        float* ni, float* nt, float* part, int B, int C, int K, int e,
+                                                        HeadGroups hg) {
   __shared__ float s_ix[32];
+  {
+    const int64_t s = blockIdx.z;
+    f_img += s * hg.img; f_txt += s * hg.txt; ni += s * hg.ws; nt += s * hg.ws; part += s * hg.ws;
+  }
   const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
   const int c0 = blockIdx.x * 32, i = blockIdx.y;
   const int c = min(c0 + l31, C - 1);
@@ -446,7 +487,9 @@ __global__ __launch_bounds__(64) void head_pairs_kernel(const float* __restrict_
   }
 }
 
-__global__ __launch_bounds__(256) void head_sum_kernel(const float* __restrict__ part, float* logits, int BC, int K, float mul) {
+__global__ __launch_bounds__(256) void head_sum_kernel(const float* __restrict__ part, float* logits, int BC, int K, float mul,
+                                                      HeadGroups hg) {
+  part += (int64_t)blockIdx.y * hg.ws; logits += (int64_t)blockIdx.y * hg.bc;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= BC) return;
   float s = 0.f;
@@ -458,8 +501,12 @@ __global__ __launch_bounds__(256) void head_sum_kernel(const float* __restrict__
 // mean loss
 __global__ __launch_bounds__(256) void head_rowdots_kernel(const float* __restrict__ dl, const float* __restrict__ part,
                                                            float* s_t, float* s_x, int B, int C, int K,
-                                                           const float* loss_b, float* loss) {
+                                                           const float* loss_b, float* loss, HeadGroups hg) {
   __shared__ float red[4];
+  {
+    const int64_t s = blockIdx.y;
+    dl += s * hg.ws; part += s * hg.ws; s_t += s * hg.ws; s_x += s * hg.ws; loss_b += s * hg.ws; loss = head_shift(loss, s);
+  }
   const int ct = (C + 255) / 256;
   if (loss != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {    // mean CE over the batch, fixed summation order
     float s = 0.f;
@@ -494,8 +541,15 @@ __global__ __launch_bounds__(64) void head_bwd_text_kernel(const float* __restri
                                                            const float* __restrict__ ni, const float* __restrict__ f_txt,
                                                            const float* __restrict__ nt, const float* __restrict__ s_t,
                                                            float* d_text_f, void* d_text_a, int act_dtype, int B, int C,
-                                                           int K, int e, int etiles_per_block) {
+                                                           int K, int e, int etiles_per_block, int ez,
+                                                           HeadGroups hg) {
   const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
+  const int bz = blockIdx.z % ez;                                   // blockIdx.z = group * ez + e-tile group
+  {
+    const int64_t s = blockIdx.z / ez;
+    dl += s * hg.ws; ni += s * hg.ws; nt += s * hg.ws; s_t += s * hg.ws;
+    f_img += s * hg.img; f_txt += s * hg.txt; d_text_f += s * hg.txt; d_text_a = head_shift16(d_text_a, s * hg.txt);
+  }
   const int c0 = blockIdx.x * 32, i = blockIdx.y;
   const int c = min(c0 + l31, C - 1);
   float itv[16], cf[16];                                            // per accumulator row: 1 / |t|, <h, dh> / |t|^2
@@ -517,7 +571,7 @@ __global__ __launch_bounds__(64) void head_bwd_text_kernel(const float* __restri
   };
   float a0[16];
   weights(0, a0);
-  for (int et = blockIdx.z * etiles_per_block; et < min((int)(blockIdx.z + 1) * etiles_per_block, e >> 5); ++et) {
+  for (int et = bz * etiles_per_block; et < min((bz + 1) * etiles_per_block, e >> 5); ++et) {
     const int col = et * 32 + l31;
     f32x16_t d;
     float tq[16], xv[16];                                           // the rows' own values (epilogue), requested up front
@@ -556,10 +610,15 @@ constexpr int HEAD_IMG_WAVES = 8;
 __global__ __launch_bounds__(64 * HEAD_IMG_WAVES) void head_bwd_img_kernel(
     const float* __restrict__ dlT, const float* __restrict__ f_img, const float* __restrict__ ni,
     const float* __restrict__ f_txt, const float* __restrict__ nt, const float* __restrict__ s_x, float* d_img_f,
-    void* d_img_a, int act_dtype, int B, int C, int K, int e) {
+    void* d_img_a, int act_dtype, int B, int C, int K, int e, int btiles, HeadGroups hg) {
   __shared__ float s_part[HEAD_IMG_WAVES][16][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
-  const int i = blockIdx.x, col = blockIdx.y * 32 + l31, b0 = blockIdx.z * 32;
+  {
+    const int64_t s = blockIdx.z / btiles;                          // blockIdx.z = group * btiles + 32-image tile
+    dlT += s * hg.ws; ni += s * hg.ws; nt += s * hg.ws; s_x += s * hg.ws;
+    f_img += s * hg.img; f_txt += s * hg.txt; d_img_f += s * hg.img; d_img_a = head_shift16(d_img_a, s * hg.img);
+  }
+  const int i = blockIdx.x, col = blockIdx.y * 32 + l31, b0 = (blockIdx.z % btiles) * 32;
   const int b = min(b0 + l31, B - 1);
   f32x16_t d;
 #pragma unroll
@@ -737,21 +796,34 @@ extern "C" int rpo_img_assemble(float* x, int64_t ldx, const float* cls, const f
 
 extern "C" int rpo_broadcast_rows(const float* src, float* dst, int64_t ld, int groups, int rows, int d,
                                   void* stream) {
-  if (!src || !dst || groups <= 0 || rows <= 0 || d <= 0) return RPO_E_BADARG;
-  hipLaunchKernelGGL(broadcast_rows_kernel, dim3(groups * rows), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     src, dst, ld, rows, d);
+  return rpo_broadcast_rows_sets(src, (int64_t)rows * d, dst, ld, 1, groups, rows, d, stream);
+}
+
+extern "C" int rpo_broadcast_rows_sets(const float* src, int64_t src_set_stride, float* dst, int64_t ld, int sets,
+                                       int groups, int rows, int d, void* stream) {
+  if (!src || !dst || sets <= 0 || groups <= 0 || rows <= 0 || d <= 0 || src_set_stride < 0) return RPO_E_BADARG;
+  if ((int64_t)sets * groups * rows >= (1ll << 31)) return RPO_E_SHAPE;
+  hipLaunchKernelGGL(broadcast_rows_kernel, dim3(sets * groups * rows), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     src, dst, ld, rows, d, groups * rows, src_set_stride);
   return rpo_launch_status();
 }
 
 extern "C" int rpo_reduce_groups(const float* src, int64_t ld, float* out, int groups, int rows, int d,
                                  void* stream) {
-  if (!src || !out || groups <= 0 || rows <= 0 || d <= 0) return RPO_E_BADARG;
+  return rpo_reduce_groups_sets(src, ld, out, (int64_t)rows * d, 1, groups, rows, d, stream);
+}
+
+extern "C" int rpo_reduce_groups_sets(const float* src, int64_t ld, float* out, int64_t out_set_stride, int sets,
+                                      int groups, int rows, int d, void* stream) {
+  if (!src || !out || sets <= 0 || groups <= 0 || rows <= 0 || d <= 0) return RPO_E_BADARG;
+  if (sets > 1 && out_set_stride < (int64_t)rows * d) return RPO_E_SHAPE;
+  if (sets > 65535) return RPO_E_SHAPE;
   if (groups >= 64)          // (below: the one-thread-per-element kernel, whose order the Oxford-Pets goldens were validated with)
-    hipLaunchKernelGGL(reduce_groups_wide_kernel, dim3(rows * ((d + 31) / 32)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), src, ld, out, groups, rows, d);
+    hipLaunchKernelGGL(reduce_groups_wide_kernel, dim3(rows * ((d + 31) / 32), sets), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), src, ld, out, groups, rows, d, out_set_stride);
   else
-    hipLaunchKernelGGL(reduce_groups_kernel, dim3((rows * d + 255) / 256), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), src, ld, out, groups, rows, d);
+    hipLaunchKernelGGL(reduce_groups_kernel, dim3((rows * d + 255) / 256, sets), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), src, ld, out, groups, rows, d, out_set_stride);
   return rpo_launch_status();
 }
 
@@ -759,22 +831,18 @@ extern "C" int64_t rpo_head_workspace_floats(int B, int C, int K, int e) {
   return (int64_t)(B + C) * K * e + (int64_t)(B + C) * K + (int64_t)B * C + B;
 }
 
-extern "C" int rpo_head_fwd_bwd(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
-                                float* logits, float* loss, float* d_img_f, float* d_text_f, int B, int C, int K,
-                                int e, float* ws, void* stream) {
-  return rpo_head_fwd_bwd_act(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32,
-                              B, C, K, e, ws, stream);
-}
-
-extern "C" int rpo_head_fwd_bwd_act(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
-                                    float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_act,
-                                    void* d_text_act, int act_dtype, int B, int C, int K, int e, float* ws,
-                                    void* stream) {
-  if (!img_f || !text_f || !logits || !ws || B <= 0 || C <= 0 || K <= 0 || e <= 0) return RPO_E_BADARG;
+// S independent heads (S = 1: the plain call); group s works in workspace [s * wsg, (s + 1) * wsg), wsg =
+// rpo_head_workspace_floats(B, C, K, e), laid out as a single head's.
+static int head_impl(const float* img_f, const float* text_f, const int64_t* label, float scale_exp, float* logits,
+                     float* loss, float* d_img_f, float* d_text_f, void* d_img_act, void* d_text_act, int act_dtype, int S,
+                     int B, int C, int K, int e, float* ws, void* stream) {
+  if (!img_f || !text_f || !logits || !ws || S <= 0 || B <= 0 || C <= 0 || K <= 0 || e <= 0) return RPO_E_BADARG;
   if ((d_img_act || d_text_act) && act_dtype != RPO_BF16 && act_dtype != RPO_F16) return RPO_E_DTYPE;
   if (label && (!loss || !d_img_f || !d_text_f)) return RPO_E_BADARG;
-  if (e > 1024) return RPO_E_SHAPE;
+  if (e > 1024 || S > 1024 || (int64_t)((B + 31) / 32) * S > 65535) return RPO_E_SHAPE;   // (grid.z of the image backward)
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint32_t G = (uint32_t)S;
+  const HeadGroups hg{(int64_t)B * K * e, (int64_t)C * K * e, (int64_t)B * C, (int64_t)B, rpo_head_workspace_floats(B, C, K, e)};
   float* ni = ws;
   float* nt = ni + (int64_t)B * K;
   float* dl = nt + (int64_t)C * K;
@@ -794,41 +862,73 @@ extern "C" int rpo_head_fwd_bwd_act(const float* img_f, const float* text_f, con
                          (s_x + (int64_t)B * K) - ws <= rpo_head_workspace_floats(B, C, K, e) && (int64_t)B * C < (1ll << 31);
 #endif
   if (mfma_head) {
-    hipLaunchKernelGGL(head_pairs_kernel, dim3((C + 31) / 32, K), dim3(64), 0, s, img_f, text_f, ni, nt, part, B, C, K, e);
-    hipLaunchKernelGGL(head_sum_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, part, logits, B * C, K, mul);
+    hipLaunchKernelGGL(head_pairs_kernel, dim3((C + 31) / 32, K, G), dim3(64), 0, s, img_f, text_f, ni, nt, part, B, C, K, e, hg);
+    hipLaunchKernelGGL(head_sum_kernel, dim3((B * C + 255) / 256, G), dim3(256), 0, s, part, logits, B * C, K, mul, hg);
     if (!label) return rpo_launch_status();
-    hipLaunchKernelGGL(head_ce_kernel, dim3(B), dim3(256), 0, s, logits, label, dl, lb, C, gmul, dlT, B);
-    hipLaunchKernelGGL(head_rowdots_kernel, dim3(K * ((C + 255) / 256) + B * K), dim3(256), 0, s, dl, part, s_t, s_x, B, C, K,
-                       lb, loss);
+    hipLaunchKernelGGL(head_ce_kernel, dim3(B, G), dim3(256), 0, s, logits, label, dl, lb, C, gmul, dlT, B, hg);
+    hipLaunchKernelGGL(head_rowdots_kernel, dim3(K * ((C + 255) / 256) + B * K, G), dim3(256), 0, s, dl, part, s_t, s_x, B, C, K,
+                       lb, loss, hg);
 #ifndef RPO_HEAD_TEXT_EZ
 #define RPO_HEAD_TEXT_EZ 4
 #endif
     const int etiles = e / 32, ez = etiles >= RPO_HEAD_TEXT_EZ ? RPO_HEAD_TEXT_EZ : 1;
-    hipLaunchKernelGGL(head_bwd_text_kernel, dim3((C + 31) / 32, K, ez), dim3(64), 0, s, dl, img_f, ni, text_f, nt, s_t,
-                       d_text_f, d_text_act, act_dtype, B, C, K, e, (etiles + ez - 1) / ez);
-    hipLaunchKernelGGL(head_bwd_img_kernel, dim3(K, etiles, (B + 31) / 32), dim3(64 * HEAD_IMG_WAVES), 0, s, dlT, img_f, ni, text_f, nt, s_x,
-                       d_img_f, d_img_act, act_dtype, B, C, K, e);
+    const int btiles = (B + 31) / 32;
+    hipLaunchKernelGGL(head_bwd_text_kernel, dim3((C + 31) / 32, K, ez * G), dim3(64), 0, s, dl, img_f, ni, text_f, nt, s_t,
+                       d_text_f, d_text_act, act_dtype, B, C, K, e, (etiles + ez - 1) / ez, ez, hg);
+    hipLaunchKernelGGL(head_bwd_img_kernel, dim3(K, etiles, btiles * G), dim3(64 * HEAD_IMG_WAVES), 0, s, dlT, img_f, ni, text_f, nt, s_x,
+                       d_img_f, d_img_act, act_dtype, B, C, K, e, btiles, hg);
     return rpo_launch_status();
   }
+  if (B > 65535) return RPO_E_SHAPE;
   if (e % 256 == 0 && aligned16(img_f) && aligned16(text_f))
-    hipLaunchKernelGGL(head_logits_kernel<true>, dim3(C, B), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul);
+    hipLaunchKernelGGL(head_logits_kernel<true>, dim3(C, B, G), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul, hg);
   else
-    hipLaunchKernelGGL(head_logits_kernel<false>, dim3(C, B), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul);
+    hipLaunchKernelGGL(head_logits_kernel<false>, dim3(C, B, G), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul, hg);
   if (!label) return rpo_launch_status();
   // Small class sets (the few-shot base / new splits; 19 for Oxford-Pets base): two launches per training step, the
   // cross-entropy is recomputed inside the backward blocks.  Larger ones (ImageNet: 500 / 1000 classes) get their own
   // cross-entropy launch and a dl array.
   const int nmax = B > C ? B : C;
   if (C <= 128 && B <= 2048) {
-    hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(B * K + C * K), dim3(256), (size_t)(nmax + 3 * B) * sizeof(float), s,
-                       dl, img_f, ni, text_f, nt, d_img_f, d_text_f, B, C, K, e, lb, loss, logits, label, gmul, d_img_act, d_text_act, act_dtype);
+    hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(B * K + C * K, G), dim3(256), (size_t)(nmax + 3 * B) * sizeof(float), s,
+                       dl, img_f, ni, text_f, nt, d_img_f, d_text_f, B, C, K, e, lb, loss, logits, label, gmul, d_img_act, d_text_act, act_dtype, hg);
     return rpo_launch_status();
   }
   if ((size_t)nmax * sizeof(float) > 64 * 1024) return RPO_E_SHAPE;
-  hipLaunchKernelGGL(head_ce_kernel, dim3(B), dim3(256), 0, s, logits, label, dl, lb, C, gmul, static_cast<float*>(nullptr), 0);
-  hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(B * K + C * K), dim3(256), (size_t)nmax * sizeof(float), s, dl, img_f,
-                     ni, text_f, nt, d_img_f, d_text_f, B, C, K, e, lb, loss, logits, label, gmul, d_img_act, d_text_act, act_dtype);
+  hipLaunchKernelGGL(head_ce_kernel, dim3(B, G), dim3(256), 0, s, logits, label, dl, lb, C, gmul, static_cast<float*>(nullptr), 0, hg);
+  hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(B * K + C * K, G), dim3(256), (size_t)nmax * sizeof(float), s, dl, img_f,
+                     ni, text_f, nt, d_img_f, d_text_f, B, C, K, e, lb, loss, logits, label, gmul, d_img_act, d_text_act, act_dtype, hg);
   return rpo_launch_status();
+}
+
+extern "C" int rpo_head_fwd_bwd(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                                float* logits, float* loss, float* d_img_f, float* d_text_f, int B, int C, int K,
+                                int e, float* ws, void* stream) {
+  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32, 1, B, C, K, e,
+                   ws, stream);
+}
+
+extern "C" int rpo_head_fwd_bwd_act(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                                    float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_act,
+                                    void* d_text_act, int act_dtype, int B, int C, int K, int e, float* ws,
+                                    void* stream) {
+  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, 1, B,
+                   C, K, e, ws, stream);
+}
+
+extern "C" int rpo_head_fwd_bwd_grouped(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                                        float* logits, float* loss, float* d_img_f, float* d_text_f, int S, int B, int C,
+                                        int K, int e, float* ws, void* stream) {
+  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32, S, B, C, K, e,
+                   ws, stream);
+}
+
+extern "C" int rpo_head_fwd_bwd_grouped_act(const float* img_f, const float* text_f, const int64_t* label,
+                                            float scale_exp, float* logits, float* loss, float* d_img_f, float* d_text_f,
+                                            void* d_img_act, void* d_text_act, int act_dtype, int S, int B, int C, int K,
+                                            int e, float* ws, void* stream) {
+  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, S, B,
+                   C, K, e, ws, stream);
 }
 
 // ---- CoCoOp's meta-net (trainers/cocoop.py:93-97, :137-143) -----------------------------------------------------------

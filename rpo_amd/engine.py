@@ -33,6 +33,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_LN_BIAS, EPI_LN
 from .config import RPOConfig
 from .engine_coop import CoopEngineMixin
 from .engine_lp import LpEngineMixin
+from .engine_multi import MultiEngineMixin
 from .engine_rn import RnEngineMixin
 
 import contextlib
@@ -69,7 +70,7 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
+class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under
@@ -117,10 +118,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
         # against 69 without, profiles/r06_trace_ncls1000.txt); the row-unit kernel forms it in its block loop.  It takes
         # row units that tile the rows in whole rounds of the CUs: u rows each with 225 <= u <= 288 and (rows / u) x
         # (4 d_t / 256) a multiple of 256 -- 250 at 24 000 rows.  No such u: the heuristic's choice stays.
-        Rt_, tn = cfg.n_cls * cfg.K, (4 * cfg.d_t) // 256
-        u = next((u for u in range(288, 224, -1) if Rt_ % u == 0 and ((Rt_ // u) * tn) % 256 == 0), 0)
-        self._text_fc_units = (dict(row_units=(u, 0, Rt_)) if (u and Rt_ >= 2048 and act_dtype != torch.float32
-                                                                 and os.environ.get("RPO_NO_TEXT_UNITS") != "1") else {})
+        self._text_fc_units = self._text_fc_units_for(cfg.n_cls * cfg.K)            # (engine_multi.py)
         tokens = np.asarray(tokens, dtype=np.int64)
         assert tokens.shape == (cfg.n_cls, cfg.context)
         self.len_np = tokens.argmax(-1) + 1             # trainers/rpo.py:137
@@ -429,7 +427,8 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
     def _text_forward_(self, train: bool) -> None:
         cfg = self.cfg
         n, K, dt, H, Rt = cfg.n_cls, cfg.K, cfg.d_t, cfg.heads_t, self.Rt
-        ops.broadcast_rows(self.text_prompt, self.xt[0], n)          # trainers/rpo.py:176-177
+        if self._multi: self._m_text_embed(n)                        # (engine_multi.py: S prompt sets, one launch)
+        else: ops.broadcast_rows(self.text_prompt, self.xt[0], n)    # trainers/rpo.py:176-177
         fold, st, last = self.fold_ln and os.environ.get("RPO_NO_TEXT_FOLD") != "1", self.ln_stats_t, len(self.txt) - 1
         pf = self._pf_chains
         nxt_q = lambda l: ((self.txt[l + 1].w_in_ln if fold else self.txt[l + 1].w_in)[:dt] if (pf and l < last) else None)
@@ -444,8 +443,9 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
                 ops.layernorm_fwd(self.xt[l], blk.ln1_w, blk.ln1_b, self.ht)
                 self._gemm(self.ht, blk.w_in[:dt], self.qt[l], EPI_BIAS, bias=blk.b_in[:dt],
                             prefetch=blk.w_out if pf else None)
-            ops.text_attn_fwd(self.qt[l], kv[:, :dt], kv[:, dt:], self.att_t, self.len_i32, n, K, self.Lmax, H,
-                              causal=False, scale=SCALE)
+            if self._multi: self._m_text_attn(l, None, None)         # (S * n virtual classes on the ONE cache)
+            else: ops.text_attn_fwd(self.qt[l], kv[:, :dt], kv[:, dt:], self.att_t, self.len_i32, n, K, self.Lmax, H,
+                                    causal=False, scale=SCALE)
             prod = dict(out2=self.ht, ln_stats=st) if fold else {}
             self._gemm(self.att_t, blk.w_out, self.xtm[l], EPI_BIAS_RESID, bias=blk.b_out, resid=self.xt[l], **prod,
                         prefetch=(blk.w_fc_ln if fold else blk.w_fc) if pf else None, **self._tt("out"))
@@ -482,6 +482,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
         the next batch, RPO.step_async(next_image=...)), the prompt rows [B*N, B*(N+K)) on the prompts."""
         cfg = self.cfg
         R = B * (cfg.n_frozen + cfg.K)
+        if self._multi: return self._m_img_embed(B, R, rows)        # (image b reads prompt set b // (B / S))
         ops.img_embed_norm(self.x_pre[:R], self.cls, self.pos, self.img_prompt, self.ln_pre[0], self.ln_pre[1], self.x[0][:R],
                            self.vis[0].ln1_w, self.vis[0].ln1_b, self.h[:R], B, cfg.n_frozen, cfg.K, rows=rows)
 
@@ -802,6 +803,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
 
     def _image_backward_finish(self, B: int) -> None:
         """sum over the batch (.repeat, rpo.py:204)"""
+        if self._multi: return self._m_img_reduce(B)                # (each run's own B / S images)
         ops.reduce_groups(self.dxb_v[:B * self.cfg.K], self.g_img, B)
 
     def _text_backward(self) -> None:
@@ -822,6 +824,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
                           None if self.act == torch.float32 else dxc)
 
         dx = self._text_chain()
+        if self._multi: return self._m_text_reduce(dx, n)
         ops.reduce_groups(dx, self.g_text, n)            # same prompt row written into every class
 
     def _text_chain(self) -> torch.Tensor:
@@ -833,6 +836,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin):
 
         def attn_bwd(l, da, dq):
             kv = self.kv_t[l]
+            if self._multi: return self._m_text_attn(l, da, dq)
             ops.text_attn_bwd(self.qt[l], kv[:, :dt], kv[:, dt:], da, dq, self.len_i32, n, K, self.Lmax, H, SCALE)
 
         return self._rows_backward(self.txt, self.xt[:-1], self.xtm, self.ut, self.dxa_t, self.dxb_t, self.dxc_t, self.du_t,

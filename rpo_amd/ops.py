@@ -329,6 +329,22 @@ def img_embed_norm(x_pre, cls, pos0, img_prompt, g_pre, b_pre, x0, g1, b1, h, B:
     return h
 
 
+def img_embed_norm_grouped(x_pre, cls, pos0, img_prompt, g_pre, b_pre, x0, g1, b1, h, B: int, N: int, Kp: int,
+                           images_per_group: int, eps: float = LN_EPS, rows: Optional[tuple] = None):
+    """`img_embed_norm` with one prompt set per group of images: img_prompt [B / images_per_group, Kp, d] (the sets may be
+    strided: a column block of a wider parameter buffer) and image b reads set b / images_per_group
+    (rpo_img_embed_norm_grouped)."""
+    r0, r1 = (0, B * (N + Kp)) if rows is None else rows
+    assert tuple(img_prompt.shape) == (B // images_per_group, Kp, x_pre.shape[1]) and img_prompt[0].is_contiguous()
+    check(_lib.load().rpo_img_embed_norm_grouped(x_pre.data_ptr(), _ld(x_pre), cls.data_ptr(), pos0.data_ptr(),
+                                                 img_prompt.data_ptr(), g_pre.data_ptr(), b_pre.data_ptr(), x0.data_ptr(),
+                                                 _ld(x0), g1.data_ptr(), b1.data_ptr(), h.data_ptr(), _ld(h),
+                                                 dtype_code(h.dtype), B, N, Kp, x_pre.shape[1], eps, r0, r1,
+                                                 images_per_group, img_prompt.stride(0), _stream()),
+          "rpo_img_embed_norm_grouped")
+    return h
+
+
 def img_assemble(x: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, img_prompt: torch.Tensor, B: int, N: int,
                  Kp: int) -> torch.Tensor:
     check(_lib.load().rpo_img_assemble(x.data_ptr(), _ld(x), cls.data_ptr(), pos.data_ptr(), img_prompt.data_ptr(),
@@ -349,6 +365,26 @@ def reduce_groups(src: torch.Tensor, out: torch.Tensor, groups: int) -> torch.Te
     assert out.is_contiguous()
     check(_lib.load().rpo_reduce_groups(src.data_ptr(), _ld(src), out.data_ptr(), groups, rows, d, _stream()),
           "rpo_reduce_groups")
+    return out
+
+
+def broadcast_rows_sets(src: torch.Tensor, dst: torch.Tensor, groups: int) -> torch.Tensor:
+    """dst[(s*groups + g)*rows + i] = src[s, i] for src [sets, rows, d], sets possibly strided (rpo_broadcast_rows_sets)."""
+    sets, rows, d = src.shape
+    assert src[0].is_contiguous() and dst.shape[0] >= sets * groups * rows
+    check(_lib.load().rpo_broadcast_rows_sets(src.data_ptr(), src.stride(0), dst.data_ptr(), _ld(dst), sets, groups, rows, d,
+                                              _stream()),
+          "rpo_broadcast_rows_sets")
+    return dst
+
+
+def reduce_groups_sets(src: torch.Tensor, out: torch.Tensor, groups: int) -> torch.Tensor:
+    """out[s, i] = sum_g src[(s*groups + g)*rows + i] for out [sets, rows, d], sets possibly strided (rpo_reduce_groups_sets)."""
+    sets, rows, d = out.shape
+    assert out[0].is_contiguous() and src.shape[0] >= sets * groups * rows
+    check(_lib.load().rpo_reduce_groups_sets(src.data_ptr(), _ld(src), out.data_ptr(), out.stride(0), sets, groups, rows, d,
+                                             _stream()),
+          "rpo_reduce_groups_sets")
     return out
 
 
@@ -445,6 +481,27 @@ def text_attn_bwd(q, kc, vc, da, dq, len_i32, n_cls: int, rows: int, Lmax: int, 
     return dq
 
 
+def text_attn_fwd_shared(q, kc, vc, out, len_i32, n_cls: int, n_kv: int, rows: int, Lmax: int, H: int, scale: float = 0.125):
+    """`text_attn_fwd` (causal = False) for n_cls virtual classes on the cache of n_kv real ones (rpo_text_attn_fwd_shared)."""
+    assert _ld(kc) == _ld(vc) and len_i32.dtype == torch.int32 and len_i32.numel() >= n_kv
+    assert kc.shape[0] >= n_kv * Lmax and q.shape[0] >= n_cls * rows and out.shape[0] >= n_cls * rows
+    check(_lib.load().rpo_text_attn_fwd_shared(q.data_ptr(), _ld(q), kc.data_ptr(), vc.data_ptr(), _ld(kc),
+                                               out.data_ptr(), _ld(out), dtype_code(q.dtype), len_i32.data_ptr(), n_cls,
+                                               n_kv, rows, Lmax, H, scale, _stream()), "rpo_text_attn_fwd_shared")
+    return out
+
+
+def text_attn_bwd_shared(q, kc, vc, da, dq, len_i32, n_cls: int, n_kv: int, rows: int, Lmax: int, H: int, scale: float = 0.125):
+    """`text_attn_bwd` for n_cls virtual classes on the cache of n_kv real ones (rpo_text_attn_bwd_shared)."""
+    assert _ld(kc) == _ld(vc) and len_i32.dtype == torch.int32 and len_i32.numel() >= n_kv
+    assert kc.shape[0] >= n_kv * Lmax and q.shape[0] >= n_cls * rows and da.shape[0] >= n_cls * rows and dq.shape[0] >= n_cls * rows
+    check(_lib.load().rpo_text_attn_bwd_shared(q.data_ptr(), _ld(q), kc.data_ptr(), vc.data_ptr(), _ld(kc),
+                                               da.data_ptr(), _ld(da), dq.data_ptr(), _ld(dq), dtype_code(q.dtype),
+                                               len_i32.data_ptr(), n_cls, n_kv, rows, Lmax, H, scale, _stream()),
+          "rpo_text_attn_bwd_shared")
+    return dq
+
+
 def head_workspace_floats(B: int, Cc: int, K: int, e: int) -> int:
     return int(_lib.load().rpo_head_workspace_floats(B, Cc, K, e))
 
@@ -462,6 +519,27 @@ def head_fwd_bwd(img_f, text_f, label, scale_exp: float, logits, loss, d_img_f, 
                                            logits.data_ptr(), _p(loss), _p(d_img_f), _p(d_text_f), _p(d_img_f_act),
                                            _p(d_text_f_act), _lib.RPO_F32 if act is None else dtype_code(act.dtype),
                                            B, Cc, K, e, ws.data_ptr(), _stream()), "rpo_head_fwd_bwd_act")
+    return logits
+
+
+def head_fwd_bwd_grouped(img_f, text_f, label, scale_exp: float, logits, loss, d_img_f, d_text_f, ws, S: int,
+                         d_img_f_act=None, d_text_f_act=None):
+    """S independent heads in one call (rpo_head_fwd_bwd_grouped[_act]): img_f [S*B, K, e], text_f [S*C, K, e], label [S*B]
+    or None, logits [S*B, C], loss [S]; ws: S * head_workspace_floats(B, C, K, e) floats."""
+    SB, K, e = img_f.shape
+    assert SB % S == 0 and text_f.shape[0] % S == 0
+    B, Cc = SB // S, text_f.shape[0] // S
+    assert img_f.is_contiguous() and text_f.is_contiguous() and logits.is_contiguous() and logits.numel() >= SB * Cc
+    assert label is None or (label.dtype == torch.int64 and label.numel() == SB and label.is_contiguous())
+    assert label is None or (loss.numel() >= S and loss.is_contiguous())
+    assert ws.numel() >= S * head_workspace_floats(B, Cc, K, e)
+    act = d_img_f_act if d_img_f_act is not None else d_text_f_act
+    assert act is None or (act.is_contiguous() and (d_text_f_act is None or d_text_f_act.is_contiguous()))
+    check(_lib.load().rpo_head_fwd_bwd_grouped_act(img_f.data_ptr(), text_f.data_ptr(), _p(label), scale_exp,
+                                                   logits.data_ptr(), _p(loss), _p(d_img_f), _p(d_text_f),
+                                                   _p(d_img_f_act), _p(d_text_f_act),
+                                                   _lib.RPO_F32 if act is None else dtype_code(act.dtype),
+                                                   S, B, Cc, K, e, ws.data_ptr(), _stream()), "rpo_head_fwd_bwd_grouped_act")
     return logits
 
 

@@ -1,0 +1,220 @@
+"""Host-side checks of the multi-run RPO trainer (rpo_amd/multi.py, rpo_amd/engine_multi.py) and its C ABI additions: the
+entry points are declared, exported and bound; bad arguments get the calls' own error codes with nothing launched; a
+member's checkpoint is a standalone RPO's file in both directions; `seeds=` draws RPO's prompts; the per-member batch
+order is `epoch_indices`'; everything unsupported is refused before a device is touched.  No GPU needed."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+NEW = ("rpo_img_embed_norm_grouped", "rpo_text_attn_fwd_shared", "rpo_text_attn_bwd_shared", "rpo_head_fwd_bwd_grouped",
+       "rpo_head_fwd_bwd_grouped_act", "rpo_broadcast_rows_sets", "rpo_reduce_groups_sets")
+
+
+def test_multi_entry_points_are_declared_exported_and_bound():
+    from rpo_amd import _lib, ops
+    from rpo_amd.build import build_library
+    build_library()
+    hdr = open(os.path.join(ROOT, "include", "rpo_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NEW:
+        assert re.search(rf"\b{name}\s*\(", src), f"{name} is not declared in include/rpo_amd.h"
+        assert hasattr(lib, name), f"librpo_hip.so does not export {name}"
+        assert name in _lib.SIGNATURES
+    for fn in ("img_embed_norm_grouped", "text_attn_fwd_shared", "text_attn_bwd_shared", "head_fwd_bwd_grouped",
+               "broadcast_rows_sets", "reduce_groups_sets"):
+        assert callable(getattr(ops, fn))
+    # additions to ABI 8, documented as such; the version does not move
+    assert _lib.load().rpo_version() == 8 and "#define RPO_ABI_VERSION 8" in hdr
+    assert hdr.count("(ABI 8 addition") >= 4
+
+
+def test_multi_entry_points_refuse_bad_arguments_without_launching():
+    from rpo_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 4096)()
+    p = (ctypes.addressof(buf) + 15) // 16 * 16                # 16-byte aligned host memory: never dereferenced
+    BAD, SHAPE, ALIGN, DTYPE = _lib.E_BADARG, _lib.E_SHAPE, _lib.E_ALIGN, _lib.E_DTYPE
+    # grouped embedding: B must be a whole number of groups; the sets must not overlap and stay 16-byte aligned
+    emb = lambda B, ipg, stride, prompt=p: lib.rpo_img_embed_norm_grouped(
+        p, 768, p, p, prompt, p, p, p, 768, p, p, p, 768, _lib.RPO_BF16, B, 197, 24, 768, 1e-5, 0, B * 221, ipg, stride, None)
+    assert emb(12, 5, 24 * 768) == SHAPE
+    assert emb(12, 0, 24 * 768) == BAD
+    assert emb(12, 4, 24 * 768 - 4) == SHAPE and emb(12, 4, 24 * 768 + 2) == ALIGN      # overlapping / misaligned sets
+    assert emb(0, 4, 24 * 768) == BAD and emb(12, 4, -4) == BAD
+    assert emb(12, 4, 24 * 768, None) == BAD
+    # shared-cache text attention
+    fwd = lambda n_cls, n_kv, Lmax=77, q=p, ldkv=1024: lib.rpo_text_attn_fwd_shared(
+        q, 512, p, p, ldkv, p, 512, _lib.RPO_BF16, p, n_cls, n_kv, 24, Lmax, 8, 0.125, None)
+    bwd = lambda n_cls, n_kv, Lmax=77, da=p, ldkv=1024: lib.rpo_text_attn_bwd_shared(
+        p, 512, p, p, ldkv, da, 512, p, 512, _lib.RPO_BF16, p, n_cls, n_kv, 24, Lmax, 8, 0.125, None)
+    for f in (fwd, bwd):
+        assert f(57, 0) == BAD and f(0, 19) == BAD
+        assert f(58, 19) == SHAPE                               # not a whole number of prompt sets
+        assert f(57, 19, Lmax=129) == SHAPE
+        assert f(57, 19, ldkv=1023) == ALIGN
+    assert fwd(57, 19, q=None) == BAD and bwd(57, 19, da=None) == BAD
+    assert lib.rpo_text_attn_fwd_shared(p, 512, p, p, 1024, p, 512, 7, p, 200, 100, 65, 77, 8, 0.125, None) == DTYPE
+    # grouped head
+    head = lambda S, B=4, C=19, e=512, label=p, loss=p: lib.rpo_head_fwd_bwd_grouped(
+        p, p, label, 100.0, p, loss, p, p, S, B, C, 24, e, p, None)
+    assert head(0) == BAD and head(3, B=0) == BAD and head(3, loss=None) == BAD
+    assert head(3, e=2048) == SHAPE and head(1025) == SHAPE
+    assert lib.rpo_head_fwd_bwd_grouped_act(p, p, p, 100.0, p, p, p, p, p, p, _lib.RPO_F32, 3, 4, 19, 24, 512, p, None) == DTYPE
+    # grouped sums
+    assert lib.rpo_broadcast_rows_sets(p, 24 * 512, p, 512, 0, 19, 24, 512, None) == BAD
+    assert lib.rpo_broadcast_rows_sets(None, 24 * 512, p, 512, 3, 19, 24, 512, None) == BAD
+    assert lib.rpo_reduce_groups_sets(p, 512, p, 24 * 512, 0, 19, 24, 512, None) == BAD
+    assert lib.rpo_reduce_groups_sets(p, 512, p, 24 * 512 - 1, 3, 19, 24, 512, None) == SHAPE     # overlapping outputs
+    assert lib.rpo_reduce_groups_sets(p, 512, None, 24 * 512, 3, 19, 24, 512, None) == BAD
+
+
+def _cfg(K=4, depth=1):
+    from rpo_amd.config import vit_b16
+    return vit_b16(layers_v=depth, layers_t=depth, K=K)
+
+
+def test_member_checkpoint_is_a_standalone_rpo_file_in_both_directions(tmp_path):
+    """A member's file, from fabricated tensors, through RPO's own reader; a standalone RPO's file through the multi
+    trainer's reader.  No engine: the readers are exercised on stand-in objects, as tests/test_lp_host.py does."""
+    from rpo_amd import multi
+    from rpo_amd.trainer import RPO, OptimConfig, checkpoint_dict, load_checkpoint_file, lr_at_epoch, write_checkpoint
+    cfg = _cfg()
+    nt, ni = cfg.K * cfg.d_t, cfg.K * cfg.d_v
+    oc = OptimConfig()
+    params = torch.arange(3 * (nt + ni), dtype=torch.float32).reshape(3, nt + ni) * 1e-4
+    mom = torch.linspace(-1, 1, 3 * (nt + ni)).reshape(3, nt + ni)
+    # ---- member 1 -> RPO.load_model
+    ck = multi.member_checkpoint(params[1], mom[1], cfg, 2, oc, 0.01, steps=5)
+    path = write_checkpoint(str(tmp_path / "m1"), ck, 2, is_best=True)
+    assert path == os.path.join(str(tmp_path / "m1"), "prompt_learner", "model.pth.tar-2")
+
+    class PL(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.text_prompt = torch.nn.Parameter(torch.zeros(cfg.K, cfg.d_t))
+            self.img_prompt = torch.nn.Parameter(torch.zeros(cfg.K, cfg.d_v))
+
+    tr = RPO.__new__(RPO)
+    tr.model = type("M", (), {})()
+    tr.model.prompt_learner = PL()
+    tr.engine = type("E", (), {})()
+    tr.engine.mom, tr.engine.params_version = torch.zeros(nt + ni), 0
+    tr.optim_cfg, tr._graph = oc, None
+    tr.load_model(str(tmp_path / "m1"))                                 # model-best
+    assert torch.equal(tr.model.prompt_learner.text_prompt.detach().reshape(-1), params[1, :nt])
+    assert torch.equal(tr.model.prompt_learner.img_prompt.detach().reshape(-1), params[1, nt:])
+    assert torch.equal(tr.engine.mom, mom[1]) and tr.epoch == 2 and tr._steps == 5
+    # the same keys and layout as the dict RPO.save_model builds
+    want = checkpoint_dict(tr.model.prompt_learner.state_dict(), 2, mom[1], oc, 0.01, 5, nt)
+    back = load_checkpoint_file(path)
+    assert list(back) == list(want) and list(back["state_dict"]) == list(want["state_dict"]) == ["text_prompt", "img_prompt"]
+    assert back["optimizer"]["param_groups"] == want["optimizer"]["param_groups"]
+    for i in (0, 1):
+        assert torch.equal(back["optimizer"]["state"][i]["momentum_buffer"], want["optimizer"]["state"][i]["momentum_buffer"])
+    # no step yet: no momentum state, as torch.optim.SGD
+    assert multi.member_checkpoint(params[0], mom[0], cfg, 0, oc, 1e-5, steps=0)["optimizer"]["state"] == {}
+    # ---- standalone RPO files -> RPOMulti.load_model
+    dirs = []
+    for s in range(3):
+        d = str(tmp_path / f"solo{s}")
+        write_checkpoint(d, checkpoint_dict({"text_prompt": params[s, :nt].reshape(cfg.K, cfg.d_t),
+                                             "img_prompt": params[s, nt:].reshape(cfg.K, cfg.d_v)}, 3, mom[s], oc, 0.01,
+                                            7, nt), 3)
+        dirs.append(d)
+    mt = multi.RPOMulti.__new__(multi.RPOMulti)
+    mt.cfg, mt.n_runs, mt.optim_cfg = cfg, 3, oc
+    mt.engine = type("E", (), {})()
+    mt.engine.m_params, mt.engine.m_mom = torch.zeros(3, nt + ni), torch.zeros(3, nt + ni)
+    mt.load_model(dirs, epoch=3)
+    assert torch.equal(mt.engine.m_params, params) and torch.equal(mt.engine.m_mom, mom)
+    assert mt.epoch == 3 and mt._steps == 7 and mt.lr == lr_at_epoch(oc, 3) < oc.lr
+    # the members share the schedule: files of different epochs are refused
+    write_checkpoint(dirs[2], multi.member_checkpoint(params[2], mom[2], cfg, 4, oc, 0.01, 7), 3)
+    with pytest.raises(ValueError, match="share one schedule"):
+        mt.load_model(dirs, epoch=3)
+    with pytest.raises(ValueError, match="directories for 3 members"):
+        mt.load_model(dirs[:2])
+
+
+def test_seeds_reproduce_rpo_initial_prompts():
+    """`seeds=[...]`: member s gets the prompts RPO's constructor draws under torch.manual_seed(seed_s) -- the reference's
+    own for seed 3 (the G7 fixture: the REAL PromptLearner.initialization_token), and `init_prompts` under each seed."""
+    from rpo_amd import multi, synth
+    from rpo_amd.custom_clip import init_prompts
+    g = dict(np.load(os.path.join(GOLD, "ref_init_seed3_d1_k4.npz")))
+    cfg = _cfg(K=4)
+    sd = synth.clip_state_dict(cfg, seed=0, logit_scale=float(np.log(100.0)))
+    seeds = [1, int(g["seed"]), 2]
+    got = multi.seeded_prompts(sd, cfg, seeds)
+    assert np.abs(got[1][0] - g["text_prompt"]).max() <= 1e-7 and np.abs(got[1][1] - g["img_prompt"]).max() <= 1e-7
+    for seed, (tp, ip) in zip(seeds, got):
+        torch.manual_seed(seed)
+        wt, wi = init_prompts(sd, cfg.K, cfg.d_t, cfg.d_v)
+        assert np.array_equal(tp, wt) and np.array_equal(ip, wi)
+    assert not np.array_equal(got[0][0], got[2][0])
+
+
+def test_member_batch_order_is_epoch_indices_with_the_members_generator():
+    from rpo_amd import multi
+    from rpo_amd.loop import epoch_indices
+    sizes, B = [16, 19, 17], 4
+    gens = [torch.Generator().manual_seed(100 + s) for s in range(3)]
+    got = multi.member_batches(sizes, B, gens)
+    for s in range(3):
+        g = torch.Generator().manual_seed(100 + s)
+        assert got[s] == epoch_indices(sizes[s], B, g)
+        assert torch.equal(gens[s].get_state(), g.get_state())          # left where a standalone epoch leaves it
+    # a second epoch continues each member's own stream
+    again = multi.member_batches(sizes, B, gens)
+    assert all(again[s] != got[s] for s in range(3))
+    with pytest.raises(ValueError, match="same, non-zero number of batches"):
+        multi.member_batches([16, 20], B, gens[:2])
+    with pytest.raises(ValueError, match="same, non-zero number of batches"):
+        multi.member_batches([3, 3], B, gens[:2])
+
+
+def test_unsupported_configurations_are_refused_before_any_device_work(monkeypatch):
+    import dataclasses
+    from rpo_amd import engine, multi
+    from rpo_amd.config import rn_clip
+    from rpo_amd.trainer import OptimConfig
+    touched = []
+    monkeypatch.setattr(engine, "make_engine", lambda *a, **k: touched.append(1))
+    cfg = _cfg()
+    kw = dict(n_runs=2, batch_size=4, seeds=[1, 2])
+    with pytest.raises(NotImplementedError, match="amp"):
+        multi.RPOMulti(cfg, {}, amp=True, **kw)
+    with pytest.raises(NotImplementedError, match="world_size"):
+        multi.RPOMulti(cfg, {}, world_size=2, **kw)
+    rn = rn_clip((1, 1, 1, 1), 64, 1024, K=4)
+    with pytest.raises(NotImplementedError, match="ResNet"):
+        multi.RPOMulti(rn, {}, **kw)
+    with pytest.raises(ValueError, match="per-member K"):
+        multi.RPOMulti([cfg, dataclasses.replace(cfg, K=8)], {}, **kw)
+    with pytest.raises(ValueError, match="per-member learning rate"):
+        multi.RPOMulti(cfg, {}, optim=[OptimConfig(lr=0.01), OptimConfig(lr=0.02)], **kw)
+    with pytest.raises(ValueError, match="exactly one of"):
+        multi.RPOMulti(cfg, {}, n_runs=2, batch_size=4)
+    with pytest.raises(ValueError, match="for n_runs = 2"):
+        multi.RPOMulti(cfg, {}, n_runs=2, batch_size=4, seeds=[1, 2, 3])
+    assert not touched
+
+
+def test_multi_modules_import_neither_oracle_nor_experiments():
+    import ast
+    mods = []
+    for f in ("multi.py", "engine_multi.py"):
+        for node in ast.walk(ast.parse(open(os.path.join(ROOT, "rpo_amd", f)).read())):
+            if isinstance(node, ast.Import):
+                mods += [a.name for a in node.names]
+            elif isinstance(node, ast.ImportFrom):
+                mods.append(("." * node.level) + (node.module or ""))
+    assert not any(m.split(".")[0] == "oracle" or m.lstrip(".").startswith("experimental") for m in mods), mods
