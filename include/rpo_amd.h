@@ -298,6 +298,21 @@ int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const void* v, int6
                                void* out, int64_t ldo, int dtype, int B, int H, int N, int Kp, float scale,
                                int q_first, void* stream);
 
+/* (ABI 8 addition) The prompt queries of `sets` prompt sets over SHARED frozen keys / values: the prompt-row pass of the
+ * image tower on buffers of its own, for any number of prompt sets per frozen image pass (no frozen row reads a prompt,
+ * trainers/rpo.py:154-156, so K / V of the frozen rows depend on the image alone).
+ *   q_rows, out : [sets * B * Kp, ldq / ldo] act dtype, set-major: row (s * B + b) * Kp + j is query j of set s for image b
+ *   k, v        : the frozen rows; image b reads rows (first_image[0] + b) * N ... + N, leading dimension ldkv (3 d when
+ *                 they point into the packed in-proj output of the pass just run, 2 d in a cache of its K | V columns)
+ *   first_image : int32 on the DEVICE (read by the kernel: one captured graph serves every chunk of a cached set), or
+ *                 NULL = 0
+ * One workgroup per (image, head) stages the image's K / V once and serves the query tiles of all sets.  Scores and
+ * softmax in fp32, P as in rpo_attn_readonly_fwd; per query the bits do not depend on `sets` or on the other queries of
+ * the launch.  head_dim 64, N <= 288, any sets * Kp.  Columns [H * 64, ldo) of `out` are not touched. */
+int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                        void* out, int64_t ldo, int dtype, int B, int H, int N, int Kp, int sets,
+                        const int32_t* first_image, float scale, void* stream);
+
 /* Backward of the above for the prompt rows only: dq[B*Kp, lddq] given da[B*Kp, ldda].
  * q_rows points at the first PROMPT row of q; k, v at the first frozen row.  dK/dV are not
  * produced: keys/values belong to frozen tokens.  Kp <= 128, N <= 288. */

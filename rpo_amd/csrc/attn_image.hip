@@ -1406,6 +1406,142 @@ int launch_fwd(const void* q, const void* k, const void* v, int64_t ld, void* ou
   return rpo_launch_status();
 }
 
+// ---- forward, prompt queries of SEVERAL prompt sets over one image's frozen K / V (rpo_attn_prompt_fwd) -----------------
+// The prompt rows of `sets` prompt sets, each a batch of B images x Kp queries in buffers of their own (set-major: row
+// (s B + b) Kp + j), read the frozen K / V of image first + b: rows (first + b) N ... of k / v, which lie in the live
+// packed in-proj output of the frozen pass (ldkv = 3 d) or in a cache of it (ldkv = 2 d).  One workgroup per (image, head)
+// stages that image's K / V once -- exactly as attn_fwd_kernel does: K rows padded to 144 B, V^T fragments transposed on
+// the matrix core (16-bit); row-major [NPAD][65] (f32) -- and then serves the sets * Kp queries of the image as 32-query
+// tiles, one wave each.  A lane holds ONE query (S^T = K . Q^T), so the queries of a tile may belong to different sets and
+// a query's result does not depend on which other queries share its tile: set s of a launch is bit for bit the launch of
+// that set alone.  Per query the arithmetic is attn_fwd_kernel's (online softmax in fp32, P rounded to the storage type
+// for P.V in the 16-bit modes, fp32 P on the 32x32x2 f32 MFMA in the f32 mode).
+// `first` is read on the device: a captured graph serves every chunk of a cached set.
+template <typename T, int NT>
+__global__ __launch_bounds__(512, 4) void attn_prompt_fwd_kernel(const T* __restrict__ q, int64_t ldq,
+                                                              const T* __restrict__ k, const T* __restrict__ v,
+                                                              int64_t ldkv, T* out, int64_t ldo, int B, int H, int N,
+                                                              int Kp, int sets, const int32_t* __restrict__ first,
+                                                              float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using L = AL<T, NT>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const int64_t img = (int64_t)(first != nullptr ? *first : 0) + b;
+  const T* kb = k + img * N * ldkv + h * 64;
+  const T* vb = v + img * N * ldkv + h * 64;
+  char* ks = smem;
+  char* vs = smem + L::K_BYTES;
+  const int Q = sets * Kp;                               // this image's queries, set-major
+  const int qt_end = (Q + 31) >> 5;
+  auto qrow = [&](int qt) -> int64_t {                   // (queries past Q: the last one again, computed and not stored)
+    const int vq = min(qt * 32 + l31, Q - 1);
+    const int s = vq / Kp, j = vq - s * Kp;
+    return ((int64_t)s * B + b) * Kp + j;
+  };
+  RowFrag<T> qf;
+  if constexpr (sizeof(T) == 2) qf.load(q + qrow(wave) * ldq + h * 64, half);
+  if constexpr (sizeof(T) == 2) {
+    bf16x8_t vrows[(NT + 7) / 8][4];
+#pragma unroll
+    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
+      const int key = 32 * (wave + 8 * ti) + l31;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        uint4 z = make_uint4(0, 0, 0, 0);
+        if (wave + 8 * ti < NT && key < N) z = *reinterpret_cast<const uint4*>(vb + (int64_t)key * ldkv + kk * 16 + half * 8);
+        vrows[ti][kk] = __builtin_bit_cast(bf16x8_t, z);
+      }
+    }
+    stage_rows_bf16<NT, 512>(ks, reinterpret_cast<const bf16_t*>(kb), ldkv, N, tid);
+    const bf16x8_t i0 = ident_frag<T>(0, l31, half), i1 = ident_frag<T>(1, l31, half);
+#pragma unroll
+    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
+      const int t = wave + 8 * ti;
+      if (t < NT) {
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          bf16x8_t fr[2];
+          transpose_tile<T>(vrows[ti], dt, i0, i1, fr);
+#pragma unroll
+          for (int g2 = 0; g2 < 2; ++g2)
+            *reinterpret_cast<bf16x8_t*>(vs + (((t * 2 + dt) * 2 + g2) * 64 + lane) * 16) = fr[g2];
+        }
+      }
+    }
+  } else {
+    stage_rows_f32<NT, 512>(reinterpret_cast<float*>(ks), kb, ldkv, N, tid);
+    stage_rows_f32<NT, 512>(reinterpret_cast<float*>(vs), vb, ldkv, N, tid);
+  }
+  __syncthreads();
+  for (int qt = wave; qt < qt_end; qt += 8) {
+    int l31v = l31;                                      // (keeps the K / V ds_reads inside the loop: attn_fwd_kernel)
+    asm volatile("" : "+v"(l31v));
+    const int vq = qt * 32 + l31;
+    const int64_t grow = qrow(qt);
+    if (sizeof(T) != 2 || qt != wave) qf.load(q + grow * ldq + h * 64, half);
+    float m = -INFINITY, l = 0.f;
+    f32x16_t o[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    if constexpr (sizeof(T) == 2) {
+      const int nfull = min(N >> 5, NT), rem = N - 32 * nfull;
+#pragma unroll 1
+      for (int t = 0; t < nfull; ++t) {
+        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
+        float tm = sc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
+        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+        const float alpha = move_max<T>(tm, scale, m, o);
+        l = l * alpha + exp_tile<T>(sc, m, scale);
+        contract_keys<T, NT>(vs, t, sc, o, l31v, half);
+      }
+      if (rem > 0 && nfull < NT) fwd_tile_tail<T, NT>(ks, vs, nfull, rem, qf, scale, m, l, o, l31v, half);
+    } else {
+#pragma unroll 1
+      for (int t = 0; t < NT; ++t) {
+        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
+        const float mn = fmaxf(m, mask_and_max(sc, t, N, half));     // finite from tile 0 on (N >= 1)
+        const float alpha = exp_scalar<T>(m - mn, scale);           // first tile: exp(-inf) = 0
+        l = l * alpha + exp_tile<T>(sc, mn, scale);
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+        contract_keys<T, NT>(vs, t, sc, o, l31v, half);
+        m = mn;
+      }
+    }
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    if (vq < Q) {
+      T* orow = out + grow * ldo + h * 64;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
+                        o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
+    }
+  }
+}
+
+template <typename T, int NT>
+int launch_prompt_fwd(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* out, int64_t ldo,
+                      int B, int H, int N, int Kp, int sets, const int32_t* first, float scale, hipStream_t s) {
+  static rpo_lds_mask_t lds_ok{0};
+  auto kern = attn_prompt_fwd_kernel<T, NT>;
+  constexpr int bytes = AL<T, NT>::FWD_BYTES;
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
+  hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), bytes, s, static_cast<const T*>(q), ldq, static_cast<const T*>(k),
+                     static_cast<const T*>(v), ldkv, static_cast<T*>(out), ldo, B, H, N, Kp, sets, first, scale);
+  return rpo_launch_status();
+}
+
 template <typename T, int NT>
 int launch_bwd(const void* qr, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* da,
                int64_t ldda, void* dq, int64_t lddq, int B, int H, int N, int Kp, float scale, hipStream_t s) {
@@ -1694,6 +1830,29 @@ extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const vo
   }
   if (N <= 224) return launch_fwd<float, 7>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
   return launch_fwd<float, 9>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
+}
+
+extern "C" int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                                   void* out, int64_t ldo, int dtype, int B, int H, int N, int Kp, int sets,
+                                   const int32_t* first_image, float scale, void* stream) {
+  if (!q_rows || !k || !v || !out || B <= 0 || H <= 0 || N <= 0 || Kp <= 0 || sets <= 0) return RPO_E_BADARG;
+  if (N > 288 || (int64_t)sets * Kp > (1 << 24) || (int64_t)sets * Kp * B > INT32_MAX) return RPO_E_SHAPE;
+  if (dtype != RPO_F32 && dtype != RPO_BF16 && dtype != RPO_F16) return RPO_E_DTYPE;
+  const int esz = dtype == RPO_F32 ? 4 : 2;
+  if (!aligned16(q_rows) || !aligned16(k) || !aligned16(v) || !ok_ld(ldq, esz) || !ok_ld(ldkv, esz) ||
+      reinterpret_cast<uintptr_t>(out) % (4 * esz) || (ldo * esz) % (4 * esz) ||
+      reinterpret_cast<uintptr_t>(first_image) % 4) return RPO_E_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == RPO_BF16) {
+    if (N <= 224) return launch_prompt_fwd<bf16_t, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+    return launch_prompt_fwd<bf16_t, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+  }
+  if (dtype == RPO_F16) {
+    if (N <= 224) return launch_prompt_fwd<f16_t, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+    return launch_prompt_fwd<f16_t, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+  }
+  if (N <= 224) return launch_prompt_fwd<float, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+  return launch_prompt_fwd<float, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
 }
 
 extern "C" int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v,

@@ -34,6 +34,7 @@ from .config import RPOConfig
 from .engine_coop import CoopEngineMixin
 from .engine_lp import LpEngineMixin
 from .engine_multi import MultiEngineMixin
+from .engine_prompt_rows import PromptRowsEngineMixin
 from .engine_rn import RnEngineMixin
 
 import contextlib
@@ -70,7 +71,7 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin):
+class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under

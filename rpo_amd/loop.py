@@ -85,6 +85,54 @@ class EvalMixin:
         return res
 
 
+    @torch.no_grad()
+    def _test_shared(self, image_set, S: int, sides, batch_size: int = 100, frozen=None, verbose: bool = True,
+                     per_class_result: bool = False, hook=None) -> List[dict]:
+        """`test` for S prompt sets at once on the shared frozen image rows (rpo_amd/engine_prompt_rows.py): per chunk
+        (those of `test`) one frozen pass -- none with `frozen`, a `FrozenImageKV` of this set -- and ONE prompt-row pass +
+        grouped head for all sets; every set has its own counts / confusion matrix, filled by `rpo_eval_accumulate` on
+        its slice of the logits; one read-back.  `sides()` -> (img_prompts [S, K, d_v], text_f [S * n_cls * K, e]), called
+        once with the device current.  `hook(b0, logits [S, B, n_cls])` sees each chunk's logits (the engine's buffer)."""
+        eng, n, C = self.engine, len(image_set), self.cfg.n_cls
+        if frozen is not None:
+            frozen.check(eng, image_set)
+        chunk = max(1, min(batch_size, eng.max_batch))
+        evs = [Classification(C, per_class_result) for _ in range(S)]
+        with torch.cuda.device(self.device):
+            eng.prompt_rows_setup(S, chunk)
+            img_prompts, text_f = sides()
+            counts = torch.zeros(S, 2, dtype=torch.int64, device=self.device)
+            cmat = torch.zeros(S, C * C, dtype=torch.int32, device=self.device)
+            if frozen is None:
+                tf = self._loop_transform(False, chunk)
+                size = self.cfg.image_size
+                bufs = self.__dict__.setdefault("_test_bufs", {})
+                if chunk not in bufs:
+                    bufs[chunk] = torch.zeros(chunk, 3, size, size, dtype=torch.float32, device=self.device)
+            for b0 in range(0, n, chunk):
+                B = min(chunk, n - b0)
+                if frozen is None:
+                    eng.frozen_pass(tf.from_set(image_set, range(b0, b0 + B), out=bufs[chunk][:B]))
+                    kv = eng.live_kv()
+                    kv.set_first(0, B)
+                else:
+                    kv = frozen.kv
+                    kv.set_first(b0, B)
+                logits = eng.shared_eval_logits(B, kv, img_prompts, text_f)
+                if hook is not None:
+                    hook(b0, logits)
+                for s in range(S):
+                    ops.eval_accumulate(logits[s], image_set.labels_dev[b0:b0 + B], counts[s], cmat[s])
+            counts_h, cmat_h = counts.cpu().numpy(), cmat.cpu().numpy()         # the one read-back
+        out = []
+        for s, ev in enumerate(evs):
+            ev.process_counts(counts_h[s], cmat_h[s])
+            res = ev.evaluate(verbose=verbose)
+            res["confusion_matrix"] = ev.cmat.copy()
+            out.append(res)
+        return out
+
+
 class LoopMixin(EvalMixin):
     """`run_epoch` / `test` / `train` for a trainer that has `step_async`, `batch_size`, `num_batches`, `batch_idx`,
     `epoch`, `lr`, `optim_cfg`, `cfg`, `device`, `engine` (RPO, CoOp, CoCoOp, LP).  The small `_loop_*` methods are
@@ -92,6 +140,7 @@ class LoopMixin(EvalMixin):
 
     _takes_next_image = False          # step_async(image, label, next_image=...) (RPO)
     _reports_acc = False               # forward_backward reports "acc" (CoOp, LP)
+    _takes_frozen = False              # test(..., frozen=FrozenImageKV) (RPO)
 
     def _loop_buffers(self):
         if getattr(self, "_loop_bufs", None) is None:
@@ -177,12 +226,18 @@ class LoopMixin(EvalMixin):
         return out
 
     def train(self, train_set, max_epoch: Optional[int] = None, val_set=None, directory: Optional[str] = None,
-              generator: Optional[torch.Generator] = None, test_batch_size: int = 100, verbose: bool = True) -> List[dict]:
+              generator: Optional[torch.Generator] = None, test_batch_size: int = 100, verbose: bool = True,
+              val_frozen=None) -> List[dict]:
         """Dassl's `train()`: `run_epoch` until `max_epoch` (default: the optimiser config's), and after each epoch its
         `after_epoch`: with a validation set `test(val_set)` -> `after_epoch_eval` (keeps `model-best`); without one
         the last epoch's model is saved.  Returns one record per epoch (mean loss, training accuracy where the
-        trainer reports it, validation accuracy)."""
+        trainer reports it, validation accuracy).  `val_frozen`: a `FrozenImageKV` of `val_set` -- the validation images'
+        frozen pass is then never repeated (RPO only: the other trainers' features depend on what they train)."""
         max_epoch = self.optim_cfg.max_epoch if max_epoch is None else max_epoch
+        if val_frozen is not None and not self._takes_frozen:
+            raise NotImplementedError(f"{type(self).__name__}.train: val_frozen is RPO's (its frozen image rows never read a "
+                                      "prompt); this trainer evaluates through its own image pass")
+        val_kw = {} if val_frozen is None else {"frozen": val_frozen}
         history = []
         while self.epoch < max_epoch:
             res = self.run_epoch(train_set, generator)
@@ -191,7 +246,7 @@ class LoopMixin(EvalMixin):
                 c = res["counts"].tolist()
                 rec["acc"] = 100.0 * c[0] / max(1, c[1])
             if val_set is not None:
-                rec["val_acc"] = self.test(val_set, test_batch_size, verbose=verbose)["accuracy"]
+                rec["val_acc"] = self.test(val_set, test_batch_size, verbose=verbose, **val_kw)["accuracy"]
                 if directory:
                     self.after_epoch_eval(directory, rec["val_acc"])
             elif directory and self.epoch == max_epoch:

@@ -298,6 +298,35 @@ class RPOMulti(EvalMixin):
             self._select(member)
         return super().test(image_set, batch_size, verbose, per_class_result)
 
+    # ------------------------------------------------------------------ evaluation: all members per frozen image pass
+    def _shared_sides(self):
+        eng = self.engine
+        return eng.m_img_prompt, eng.multi_text_features()
+
+    @torch.no_grad()
+    def model_inference_all(self, image: torch.Tensor) -> torch.Tensor:
+        """logits [S, B, n_cls] of every member for one batch: ONE frozen image pass, then the S * B * K prompt rows of all
+        members on its K / V (rpo_amd/engine_prompt_rows.py).  Member s's slice is what `model_inference(image, member=s)`
+        computes, up to the summation order of the GEMM plans."""
+        eng, S = self.engine, self.n_runs
+        with torch.cuda.device(self.device):
+            image = image.to(device=self.device, dtype=torch.float32).contiguous()
+            B = image.shape[0]
+            eng.prompt_rows_setup(S, B)
+            img_prompts, text_f = self._shared_sides()
+            eng.frozen_pass(image)
+            kv = eng.live_kv()
+            kv.set_first(0, B)
+            return eng.shared_eval_logits(B, kv, img_prompts, text_f).clone()
+
+    def test_all(self, image_set, batch_size: int = 100, frozen=None, verbose: bool = True, per_class_result: bool = False,
+                 hook=None) -> List[dict]:
+        """Dassl's `test()` for EVERY member in one pass over the set: per chunk one frozen image pass (none with `frozen`,
+        a `FrozenImageKV` of this set) and one prompt-row pass for all S members.  Returns, per member, the dict
+        `test(image_set, member=s)` returns."""
+        return self._test_shared(image_set, self.n_runs, self._shared_sides, batch_size, frozen, verbose, per_class_result,
+                                 hook)
+
     # ------------------------------------------------------------------ checkpoints: per member, a standalone RPO's files
     def save_model(self, directories: Sequence[str], epoch: Optional[int] = None, is_best: bool = False,
                    val_results: Optional[Sequence[Optional[float]]] = None) -> List[str]:

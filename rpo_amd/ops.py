@@ -397,6 +397,23 @@ def attn_readonly_fwd(q, k, v, out, B: int, H: int, N: int, Kp: int, scale: floa
     return out
 
 
+def attn_prompt_fwd(q_rows, k, v, out, B: int, H: int, N: int, Kp: int, sets: int, first_image=None, scale: float = 0.125,
+                    kv_images: Optional[int] = None):
+    """The prompt queries of `sets` prompt sets (q_rows / out: [sets*B*Kp, .], set-major) over the frozen K / V of images
+    first_image[0] + b (rpo_attn_prompt_fwd).  first_image: int32 device scalar or None = 0; it is read on the device, so
+    the caller vouches that first_image + B <= kv_images, the images k / v hold (default: as many as their rows give)."""
+    assert q_rows.dtype == k.dtype == v.dtype == out.dtype and _ld(k) == _ld(v)
+    assert q_rows.shape[0] >= sets * B * Kp and out.shape[0] >= sets * B * Kp
+    assert q_rows.shape[1] >= H * 64 and out.shape[1] >= H * 64 and k.shape[1] >= H * 64 and v.shape[1] >= H * 64
+    kv_images = min(k.shape[0], v.shape[0]) // N if kv_images is None else kv_images
+    assert B <= kv_images and min(k.shape[0], v.shape[0]) >= kv_images * N, "k / v hold fewer than B images of N rows"
+    assert first_image is None or (first_image.dtype == torch.int32 and first_image.is_cuda and first_image.numel() == 1)
+    check(_lib.load().rpo_attn_prompt_fwd(q_rows.data_ptr(), _ld(q_rows), k.data_ptr(), v.data_ptr(), _ld(k), out.data_ptr(),
+                                          _ld(out), dtype_code(q_rows.dtype), B, H, N, Kp, sets, _p(first_image), scale,
+                                          _stream()), "rpo_attn_prompt_fwd")
+    return out
+
+
 def attn_readonly_bwd_proj(q_rows, k, v, dx, w_out_t, dq, B: int, H: int, N: int, Kp: int, scale: float = 0.125):
     """attn_readonly_bwd with the d out-proj GEMM folded in: dx = gradient of the out-proj output (act dtype)."""
     assert q_rows.dtype == k.dtype == v.dtype == dx.dtype == w_out_t.dtype == dq.dtype

@@ -58,6 +58,7 @@ def lr_at_epoch(oc: OptimConfig, epoch: int) -> float:
 
 class RPO(LoopMixin):
     _takes_next_image = True         # run_epoch names the next batch: its patch embedding runs under this step
+    _takes_frozen = True             # test(..., frozen=...): the prompt-row pass alone on a set's cached frozen K / V
 
     def __init__(self, cfg: RPOConfig, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",
@@ -510,6 +511,24 @@ class RPO(LoopMixin):
         """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
         self._join_side()
         return self.model.eval_logits(image)
+
+    def _shared_sides(self):
+        """(img_prompts [1, K, d_v], text_f) of the current prompts for the prompt-row pass."""
+        eng, pl = self.engine, self.model.prompt_learner
+        ver = (pl.text_prompt._version, pl.img_prompt._version)       # (edits through the nn.Parameter views: eval_logits)
+        if ver != getattr(self.model, "_seen_version", None):
+            eng.params_version += 1
+            self.model._seen_version = ver
+        return eng.img_prompt.unsqueeze(0), eng.eval_text_features()
+
+    def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, frozen=None,
+             hook=None):
+        """Dassl's `test()` (loop.EvalMixin.test).  `frozen`: a `FrozenImageKV` built for this engine and set -- no image
+        pass is run at all, only the K prompt rows per image on the cached frozen K / V (rpo_amd/frozen_kv.py)."""
+        if frozen is None:
+            return super().test(image_set, batch_size, verbose, per_class_result)
+        self._join_side()
+        return self._test_shared(image_set, 1, self._shared_sides, batch_size, frozen, verbose, per_class_result, hook)[0]
 
     # -- checkpoints: Dassl layout <dir>/prompt_learner/{model.pth.tar-<epoch>, model-best.pth.tar} ----------
     def save_model(self, directory: str, epoch: Optional[int] = None, is_best: bool = False,
