@@ -530,10 +530,11 @@ int rpo_preprocess_batch(const uint8_t* src, int64_t src_bytes, const rpo_image_
  * Replaces Dassl's `read_image` (un-vendored; reached from the reference's dataset classes, datasets/oxford_pets.py:65-72
  * via DatasetWrapper.__getitem__), which is Pillow's `Image.open(path).convert("RGB")`: libjpeg's baseline path with its
  * defaults -- Huffman decode, dequantise, the "islow" integer IDCT, "fancy" (triangle) chroma upsampling, 16.16 fixed-point
- * YCbCr -> RGB.  Output is BIT-IDENTICAL to Pillow's for every file rpo_jpeg_probe accepts: baseline sequential DCT (SOF0,
- * SOF1 with 8-bit tables), 8-bit samples, 1 component (gray -> R = G = B) or 3 (YCbCr) at 4:4:4 / 4:2:2 / 4:2:0, any
- * restart interval, one interleaved scan.  Everything else is refused with its own RPO_E_JPEG_* code and is the caller's to
- * decode on the host.  The header is parsed on the host; everything from the first entropy-coded byte on runs on the device. */
+ * YCbCr -> RGB.  rpo_jpeg_probe accepts baseline sequential DCT (SOF0, SOF1 with 8-bit tables), 8-bit samples, 1 component
+ * (gray -> R = G = B) or 3 (YCbCr) at 4:4:4 / 4:2:2 / 4:2:0, any restart interval, one interleaved scan.  For those the
+ * output is BIT-IDENTICAL to Pillow's wherever the coefficient blocks are ones an encoder can produce from 8-bit samples
+ * (any quantiser); for other header-valid streams it is defined and deterministic but may differ from Pillow's.
+ * Everything else is refused with its own RPO_E_JPEG_* code and is the caller's to decode on the host.  The header is parsed on the host; everything from the first entropy-coded byte on runs on the device. */
 typedef struct rpo_jpeg_info {
   int32_t width, height;
   int32_t components;            /* 1 or 3 */
@@ -583,7 +584,7 @@ size_t rpo_jpeg_workspace_bytes(rpo_jpeg_desc* descs, int n);
 /* files: device buffer (16-byte aligned, files_bytes bytes) holding the n files and their table blobs; desc_host / desc_dev:
  * the same n descriptors in host and device memory (the host copy is validated -> RPO_E_SHAPE / RPO_E_WORKSPACE /
  * RPO_E_ALIGN, the device copy is what the kernels read); out: device buffer of out_bytes bytes; status: int32 [n] device.
- * n <= 65535 images of mixed sizes and modes.  Enqueues four kernels on `stream`: restart-marker scan, entropy decode (one
+ * n <= 65535 images of mixed sizes and modes, each of at most 2^31 - 1 pixels (RPO_E_SHAPE).  Enqueues four kernels on `stream`: restart-marker scan, entropy decode (one
  * lane per unit; every loop bound from the header, every byte read checked against the file's length), dequantise + IDCT,
  * upsample + colour conversion.  Writes only each image's own height * width * 3 bytes of `out`. */
 int rpo_jpeg_decode_batch(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_desc* desc_host,

@@ -6,7 +6,10 @@
 //   "fancy" chroma upsampling: h2v1 (3a + b + 1|2) >> 2; h2v2 column sums 3 near + far, then (3t + n + 8|7) >> 4; edges
 //     replicated at the downsampled size; a chroma plane at most 2 samples wide is replicated instead
 //   YCbCr -> RGB in 16.16 fixed point
-// All integer, so results are bit-identical to Pillow's (tests/test_gpu_jpeg.py) whatever the launch geometry or the batch.
+// All integer and all defined (sums that can leave 31 bits are formed modulo 2^32), so the result depends on neither the
+// launch geometry nor the batch.  Bit-identical to Pillow's for coefficient blocks an encoder can produce from 8-bit
+// samples, at any quantiser; for other header-valid streams it is what tests/jpeg_oracle.py computes and may differ from
+// Pillow (tests/test_gpu_jpeg.py, tests/test_jpeg_streams_host.py).
 //
 // The header is parsed on the host (parse_header below; plain C++, never reads past nbytes).  Four kernels per batch:
 //   restart_scan_kernel  per image: status = 0; byte offsets of the RSTn markers -> workspace (unit u starts behind marker u-1)
@@ -159,7 +162,7 @@ HD int decode_unit(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_des
   Bits br;
   br.init(files, scan0 + (start < 0 ? 0 : start), scan0 + f.scan_bytes, files_bytes);
   if (start < 0 || start > f.scan_bytes) br.pos = br.end;
-  int pred[3] = {0, 0, 0};
+  uint32_t pred[3] = {0, 0, 0};            // modulo 2^32: the block keeps its low 16 bits, as a JCOEF does
   for (int m = 0; m < nmcu; ++m) {
     for (int j = 0; j < bpm; ++j) {
       i16a_t* blk = coef + ((int64_t)(mcu0 + m) * bpm + j) * 64;
@@ -170,10 +173,10 @@ HD int decode_unit(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_des
       int s = huff_symbol(br, &tab->dc[c]);
       if (s < 0 || s > 11) { err = RPO_JPEG_BAD_CODE; continue; }
       if (s) {
-        pred[c] += extend(br.peek(s), s);
+        pred[c] += (uint32_t)extend(br.peek(s), s);
         br.skip(s);
       }
-      blk[0] = (int16_t)pred[c];
+      blk[0] = (int16_t)(uint16_t)pred[c];
       for (int k = 1; k < 64;) {             // k grows by >= 1 per iteration
         br.refill();
         const int rs = huff_symbol(br, &tab->ac[c]);
@@ -199,31 +202,37 @@ HD int decode_unit(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_des
 }
 
 // ---- dequantise + IDCT ------------------------------------------------------------------------------------------
+// The butterflies run in uint32_t: a coefficient stream no encoder writes (int16 coefficient x quantiser up to 255, dense)
+// takes the sums past 31 bits, which is undefined for int and wraps modulo 2^32 here.  Only the descaling shift reads the
+// sum as a signed number, so every input that stays inside 31 bits -- all an encoder produces from 8-bit samples -- gives
+// the bits it gave before, at the same instruction count (tests/jpeg_oracle.py restates the same definition).
+HD int descale(uint32_t v, int shift) { return (int)(v + (1u << (shift - 1))) >> shift; }
+
 HD void idct_1d(const int* in, int stride, int* out, int ostride, int shift) {
-  const int in0 = in[0], in1 = in[stride], in2 = in[2 * stride], in3 = in[3 * stride], in4 = in[4 * stride],
-            in5 = in[5 * stride], in6 = in[6 * stride], in7 = in[7 * stride];
-  int z1 = (in2 + in6) * 4433;
-  const int tmp2 = z1 + in6 * -15137, tmp3 = z1 + in2 * 6270;
-  const int tmp0 = (in0 + in4) * 8192, tmp1 = (in0 - in4) * 8192;
-  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-  int t0 = in7, t1 = in5, t2 = in3, t3 = in1;
+  typedef uint32_t u;
+  const u in0 = (u)in[0], in1 = (u)in[stride], in2 = (u)in[2 * stride], in3 = (u)in[3 * stride], in4 = (u)in[4 * stride],
+          in5 = (u)in[5 * stride], in6 = (u)in[6 * stride], in7 = (u)in[7 * stride];
+  u z1 = (in2 + in6) * 4433u;
+  const u tmp2 = z1 - in6 * 15137u, tmp3 = z1 + in2 * 6270u;
+  const u tmp0 = (in0 + in4) * 8192u, tmp1 = (in0 - in4) * 8192u;
+  const u tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  u t0 = in7, t1 = in5, t2 = in3, t3 = in1;
   z1 = t0 + t3;
-  int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-  const int z5 = (z3 + z4) * 9633;
-  t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
-  z1 *= -7373; z2 *= -20995;
-  z3 = z3 * -16069 + z5;
-  z4 = z4 * -3196 + z5;
+  u z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+  const u z5 = (z3 + z4) * 9633u;
+  t0 *= 2446u; t1 *= 16819u; t2 *= 25172u; t3 *= 12299u;
+  z1 = 0u - z1 * 7373u; z2 = 0u - z2 * 20995u;
+  z3 = z5 - z3 * 16069u;
+  z4 = z5 - z4 * 3196u;
   t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-  const int rnd = 1 << (shift - 1);
-  out[0] = (tmp10 + t3 + rnd) >> shift;
-  out[7 * ostride] = (tmp10 - t3 + rnd) >> shift;
-  out[ostride] = (tmp11 + t2 + rnd) >> shift;
-  out[6 * ostride] = (tmp11 - t2 + rnd) >> shift;
-  out[2 * ostride] = (tmp12 + t1 + rnd) >> shift;
-  out[5 * ostride] = (tmp12 - t1 + rnd) >> shift;
-  out[3 * ostride] = (tmp13 + t0 + rnd) >> shift;
-  out[4 * ostride] = (tmp13 - t0 + rnd) >> shift;
+  out[0] = descale(tmp10 + t3, shift);
+  out[7 * ostride] = descale(tmp10 - t3, shift);
+  out[ostride] = descale(tmp11 + t2, shift);
+  out[6 * ostride] = descale(tmp11 - t2, shift);
+  out[2 * ostride] = descale(tmp12 + t1, shift);
+  out[5 * ostride] = descale(tmp12 - t1, shift);
+  out[3 * ostride] = descale(tmp13 + t0, shift);
+  out[4 * ostride] = descale(tmp13 - t0, shift);
 }
 
 // blk: 64 int16 coefficients in natural order -> 64 uint8 samples (row-major) over its first 64 bytes
@@ -299,6 +308,8 @@ HD void pixel_rgb(const uint8_t* coef, const rpo_jpeg_info& f, int x, int y, uin
 // ---- kernels ----------------------------------------------------------------------------------------------------
 constexpr int SCAN_THREADS = 256;
 
+HD bool rst_at(const uint8_t* p, int64_t i) { return p[i] == 0xFF && (p[i + 1] & 0xF8) == 0xD0; }   // needs i + 1 < n
+
 __global__ __launch_bounds__(SCAN_THREADS) void restart_scan_kernel(const uint8_t* __restrict__ files,
                                                                     const rpo_jpeg_desc* __restrict__ desc, int32_t* rst,
                                                                     int32_t* status) {
@@ -316,7 +327,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void restart_scan_kernel(const uint8_
   const int64_t chunk = (n + SCAN_THREADS - 1) / SCAN_THREADS;
   const int64_t lo = tid * chunk, hi = min(lo + chunk, n - 1);
   int cnt = 0;
-  for (int64_t i = lo; i < hi; ++i) cnt += (p[i] == 0xFF && (p[i + 1] & 0xF8) == 0xD0);
+  for (int64_t i = lo; i < hi; ++i) cnt += rst_at(p, i);
   counts[tid] = cnt;
   __syncthreads();
   for (int off = 1; off < SCAN_THREADS; off <<= 1) {       // inclusive scan
@@ -327,7 +338,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void restart_scan_kernel(const uint8_
   }
   int ord = counts[tid] - cnt;                             // markers before this thread's chunk
   for (int64_t i = lo; i < hi; ++i) {
-    if (p[i] == 0xFF && (p[i + 1] & 0xF8) == 0xD0) {
+    if (rst_at(p, i)) {
       if (ord + 1 < units) mine[ord + 1] = (int32_t)(i + 2);
       ++ord;
     }
@@ -610,6 +621,7 @@ extern "C" int rpo_jpeg_decode_batch(const uint8_t* files, int64_t files_bytes, 
     if (d.table_offset < 0 || d.table_offset + f.table_bytes > files_bytes) return RPO_E_SHAPE;
     if (d.table_offset % 16) return RPO_E_ALIGN;
     if (d.out_offset < 0 || d.out_offset + (int64_t)f.width * f.height * 3 > out_bytes) return RPO_E_SHAPE;
+    if ((int64_t)f.width * f.height > 0x7fffffff) return RPO_E_SHAPE;   // the colour kernel counts pixels in an int
     if (d.unit_base != units) return RPO_E_WORKSPACE;
     units += f.units;
     if (units > 0x7fffffff) return RPO_E_SHAPE;

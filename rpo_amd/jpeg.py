@@ -3,9 +3,17 @@
 The reference reads its datasets through Dassl's `read_image`, i.e. Pillow's `Image.open(path).convert("RGB")`, one file at
 a time on CPU workers.  Here the header of each file is parsed on the host (C++ inside the library), the compressed bytes
 and the derived tables travel to the device, and entropy decode, IDCT, chroma upsampling and colour conversion run there
-for whole chunks of files of mixed sizes and modes -- bit-identical to Pillow for every file `probe` accepts (baseline,
-8-bit, gray or YCbCr at 4:4:4 / 4:2:2 / 4:2:0, any restart interval).  Files it refuses raise `JpegRefused` with the
-library's reason; `DeviceImageSet.from_jpeg` routes those through a host decoder.
+for whole chunks of files of mixed sizes and modes.  `probe` accepts baseline, 8-bit, gray or YCbCr at 4:4:4 / 4:2:2 /
+4:2:0, any restart interval, any table ids and segment packing.  Files it refuses raise `JpegRefused` with the library's
+reason; `DeviceImageSet.from_jpeg` routes those through a host decoder.
+
+What is tested (tests/golden/jpeg_streams.npz): the pixels are bit-identical to Pillow's for coefficient
+blocks an encoder can produce from 8-bit samples, at any quantiser (1..255) and with any valid Huffman tables.  Outside
+that domain -- header-valid streams no encoder writes: dense coefficients at dequantised amplitudes of 1020 and more, AC
+magnitudes of category 11..15, a DC predictor run past int16 -- the decode is still defined and deterministic and equals
+the numpy oracle (32-bit sums wrap), but may differ from Pillow, which clamps narrower intermediates: 0-7 of 1024 pixels at
+amplitude 1020, about a third at 4080, half and more beyond (the table in 9f).  Pillow itself refuses files wider or
+higher than 65500; the device decodes up to 65535.
 
     dec = JpegDecoder("cuda:0")
     info = dec.probe(data)                        # width / height / components / sampling ... or JpegRefused

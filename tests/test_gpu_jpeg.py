@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import jpeg_oracle as J
+import jpeg_writer as JW
 from test_gpu_loop import DEV, _make, _staging, _state, bits
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +34,16 @@ def metas():
         g = np.load(os.path.join(GOLD, name))
         out += [tuple(int(v) for v in g[f"meta{i}"]) for i in range(int(g["n"]))]
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def streams():
+    """tests/golden/jpeg_streams.npz: streams Pillow's encoder never writes (tests/jpeg_writer.py), `rgb` = Pillow's decode"""
+    return JW.load_streams(os.path.join(GOLD, "jpeg_streams.npz"))
+
+
+def in_gamut():
+    return [c for c in streams() if c["gamut"] and not c["refused"]]
 
 
 def refused_file(kind):
@@ -241,3 +252,109 @@ def test_test_on_a_from_jpeg_set_is_bit_identical():
     b = tr.test(ds, batch_size=bs)
     assert (a["total"], a["correct"], a["accuracy"]) == (b["total"], b["correct"], b["accuracy"]) and a["total"] == n
     assert np.array_equal(a["confusion_matrix"], b["confusion_matrix"])
+
+
+# ---- streams Pillow's encoder never writes (tools/make_jpeg_streams.py) ---------------------------------------------------
+
+def test_every_in_gamut_stream_in_one_call_equals_pillow():
+    """2600+ streams -- third table slots, packed / redefined tables, 16-bit codes, every size 1..18 squared in four modes,
+    restart and marker variants, the 8188-unit strip next to 1x1 images -- in ONE launch: each equals Pillow's pixels; the
+    same bits in chunks of 7 in another order."""
+    from rpo_amd.jpeg import JpegDecoder
+    cs = in_gamut()
+    assert len(cs) > 2592 + 60
+    files, shapes = [c["file"] for c in cs], [c["rgb"].shape[:2] for c in cs]
+    st, first = guarded_decode(JpegDecoder(DEV, chunk_images=4096), files, shapes)
+    assert st.shape == (len(cs),) and not st.any(), [cs[k]["tag"] for k in np.flatnonzero(st)][:5]
+    for c, im in zip(cs, first):
+        assert np.array_equal(im, c["rgb"]), (c["tag"], int((im != c["rgb"]).any(-1).sum()))
+    order = list(np.random.default_rng(3).permutation(len(cs)))
+    st, second = guarded_decode(JpegDecoder(DEV, chunk_images=7), [files[j] for j in order], [shapes[j] for j in order], guard=5)
+    assert not st.any()
+    for j, im in zip(order, second):
+        assert np.array_equal(im, first[j]), cs[j]["tag"]
+
+
+def test_the_8188_unit_strip_alone_and_among_299_small_streams():
+    """One file of 8188 restart intervals is > 4096 units with a single descriptor: several units per wave, every lane's
+    binary search ends on image 0.  Then the same file behind and in front of 299 small ones."""
+    from rpo_amd.jpeg import JpegDecoder, probe
+    cs = in_gamut()
+    strip = next(c for c in cs if "8188 units" in c["tag"])
+    assert probe(strip["file"]).units == 8188
+    dec = JpegDecoder(DEV, chunk_images=4096)
+    st, (alone,) = guarded_decode(dec, [strip["file"]], [strip["rgb"].shape[:2]])
+    assert not st.any() and np.array_equal(alone, strip["rgb"])
+    small = [c for c in cs if c["rgb"].shape[0] * c["rgb"].shape[1] <= 2048]
+    pick = [small[j] for j in np.random.default_rng(4).integers(0, len(small), 299)]
+    mixed = pick[:150] + [strip] + pick[150:]
+    st, imgs = guarded_decode(dec, [c["file"] for c in mixed], [c["rgb"].shape[:2] for c in mixed])
+    assert not st.any() and np.array_equal(imgs[150], alone)
+    for c, im in zip(mixed, imgs):
+        assert np.array_equal(im, c["rgb"]), c["tag"]
+
+
+def test_out_of_gamut_streams_are_defined_and_equal_the_oracle():
+    """Header-valid streams no encoder produces (dense coefficients at dequantised amplitudes up to 32767 x 255, AC
+    categories 11..15, a DC predictor past int16): status 0, the oracle's bits (sums modulo 2^32), the same
+    bits again.  Pillow clamps narrower intermediates there; equality with it is required only where the generator saw it."""
+    from rpo_amd.jpeg import JpegDecoder
+    cs = [c for c in streams() if not c["gamut"]]
+    assert len(cs) >= 12
+    dec = JpegDecoder(DEV)
+    files, shapes = [c["file"] for c in cs], [c["rgb"].shape[:2] for c in cs]
+    st, first = guarded_decode(dec, files, shapes)
+    assert not st.any()
+    for c, im in zip(cs, first):
+        assert np.array_equal(im, J.decode(c["file"])), c["tag"]
+        differ = int((im != c["rgb"]).any(-1).sum())
+        print(f"{differ:5d} of {im.shape[0] * im.shape[1]} pixels differ from Pillow: {c['tag']}")
+        if c["differ"] == 0:
+            assert differ == 0, c["tag"]
+    st, second = guarded_decode(dec, files, shapes)
+    assert not st.any() and all(np.array_equal(a, b) for a, b in zip(first, second))
+
+
+def test_constructed_corrupt_streams_end_in_their_exact_status():
+    """Each stream is wrong in one known place (tests/jpeg_writer.py corrupt_streams; all of them ran through the decoder's
+    code on the CPU first, tests/test_jpeg_streams_host.py); good streams sit between them and stay exact."""
+    from rpo_amd.jpeg import JpegDecoder
+    good = [c for c in in_gamut() if c["rgb"].shape[:2] == (32, 32)][:6]
+    corrupt = JW.corrupt_streams()
+    assert [s for _, _, s in corrupt] == [2, 2, 3, 1, 4]            # BAD_CODE, BAD_CODE, BAD_INDEX, TRUNCATED, NO_RESTART
+    files, want = [good[0]["file"]], [0]
+    for k, (_, data, status) in enumerate(corrupt):
+        files += [data, good[k + 1]["file"]]
+        want += [status, 0]
+    dec = JpegDecoder(DEV)
+    st, imgs = guarded_decode(dec, files, [(32, 32)] * len(files))
+    print("device status:", st.tolist())
+    assert st.tolist() == want
+    for k, c in enumerate(good):
+        assert np.array_equal(imgs[2 * k], c["rgb"]), c["tag"]
+    st2, imgs2 = guarded_decode(dec, files, [(32, 32)] * len(files))
+    assert np.array_equal(st, st2) and all(np.array_equal(a, b) for a, b in zip(imgs, imgs2))
+
+
+def test_from_jpeg_on_a_folder_of_the_streams_and_the_refused_ones(tmp_path):
+    from rpo_amd.input_pipeline import DeviceImageSet
+    cs = [c for c in streams() if c["gamut"]]
+    stand_in = np.random.default_rng(2).integers(0, 256, (9, 11, 3), dtype=np.uint8)
+    paths, images = [], []
+    for i, c in enumerate(cs):
+        paths.append(str(tmp_path / f"{i:04d}.jpg"))
+        with open(paths[-1], "wb") as f:
+            f.write(c["file"])
+        images.append(stand_in if c["refused"] else c["rgb"])
+    n_refused = sum(bool(c["refused"]) for c in cs)
+    assert n_refused == 2
+    seen = []
+
+    def fallback(data):
+        seen.append(data)
+        return stand_in
+    labels = [i % 19 for i in range(len(cs))]
+    ds = DeviceImageSet.from_jpeg(paths, labels, DEV, fallback=fallback)
+    assert (ds.n_device, ds.n_fallback) == (len(cs) - n_refused, n_refused)
+    assert seen == [c["file"] for c in cs if c["refused"]]
+    _set_equal(DeviceImageSet(images, labels, DEV), ds, images)
