@@ -65,7 +65,10 @@ enum {
   RPO_E_JPEG_COMPONENTS = -25,  /* not 1 or 3 components (CMYK / YCCK) */
   RPO_E_JPEG_RGB = -26,         /* RGB-coded: Adobe APP14 transform 0, or component ids 'R','G','B' */
   RPO_E_JPEG_SAMPLING = -27,    /* sampling other than 4:4:4, 4:2:2 (h2v1), 4:2:0 (h2v2) */
-  RPO_E_JPEG_MULTISCAN = -28    /* the first scan does not hold every component */
+  RPO_E_JPEG_MULTISCAN = -28,   /* the first scan does not hold every component */
+  /* rpo_jpeg_prog_probe only */
+  RPO_E_JPEG_SCRIPT = -29,      /* progressive scan script incomplete, inconsistent or otherwise outside the accepted rules */
+  RPO_E_JPEG_SEQUENTIAL = -30   /* a sequential (SOF0 / SOF1) frame: rpo_jpeg_probe is the one that handles it */
 };
 
 /* GEMM epilogues (fused into the MFMA kernel's store) */
@@ -590,6 +593,33 @@ size_t rpo_jpeg_workspace_bytes(rpo_jpeg_desc* descs, int n);
 int rpo_jpeg_decode_batch(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_desc* desc_host,
                           const rpo_jpeg_desc* desc_dev, int n, uint8_t* out, int64_t out_bytes, void* workspace,
                           size_t workspace_bytes, int32_t* status, void* stream);
+
+/* ---- progressive JPEG files (SOF2, Huffman coding, 8-bit samples) ------------------------------------------------
+ * The files rpo_jpeg_probe refuses with RPO_E_JPEG_PROGRESSIVE, through entry points of their own; components, sampling and
+ * colour rules are rpo_jpeg_probe's.  The scan script must be consistent and complete: DC scans have Ss = Se = 0 over any
+ * subset of the components, AC scans 1 <= Ss <= Se <= 63 and one component; Ah, Al <= 13; the first scan over a
+ * (component, coefficient) has Ah = 0, each later one Ah = the previous Al and Al = Ah - 1; a component's AC scans follow
+ * its first DC scan; at EOI (or the end of the file) every coefficient of every component has reached Al = 0; no DQT
+ * follows the first SOS.  DHT and DRI between scans hold for the scans behind them.  Anything else -> RPO_E_JPEG_SCRIPT (or
+ * the code that names the frame) and the host decodes the file.  Pixels: bit-identical to the baseline file of the same
+ * coefficient blocks, hence to Pillow's under the same condition as above.
+ * The same rpo_jpeg_info / rpo_jpeg_desc, with: units = sum over the scans of their restart intervals, restart_interval = 0
+ * (DRI is per scan), reserved = number of dependency levels (1..14; a scan's level is one more than the highest level among
+ * earlier scans sharing a component and a coefficient with it), scan_offset = first entropy-coded byte of the first scan,
+ * table_bytes = size of THIS file's plan blob. */
+/* HOST ONLY: walks every marker of `file` and the entropy-coded bytes between them, never reading past nbytes. */
+int rpo_jpeg_prog_probe(const uint8_t* file, int64_t nbytes, rpo_jpeg_info* info);
+/* HOST ONLY: writes the file's plan blob (info.table_bytes bytes): quantisation tables in natural order, one record per
+ * scan, the Huffman lookup tables as defined at each SOS, the byte offset at which every unit starts. */
+int rpo_jpeg_prog_plan(const uint8_t* file, int64_t nbytes, void* blob, int64_t blob_bytes);
+/* HOST ONLY: as rpo_jpeg_workspace_bytes, for descriptors whose infos come from rpo_jpeg_prog_probe. */
+size_t rpo_jpeg_prog_workspace_bytes(rpo_jpeg_desc* descs, int n);
+/* As rpo_jpeg_decode_batch (same arguments, same validation of the host descriptors, same status words), table_offset
+ * naming each file's plan blob.  Kernels: zero the coefficient blocks and the status words; one entropy kernel per
+ * dependency level (one lane per unit: a restart interval of a scan); then the IDCT and colour kernels of the baseline path. */
+int rpo_jpeg_prog_decode_batch(const uint8_t* files, int64_t files_bytes, const rpo_jpeg_desc* desc_host,
+                               const rpo_jpeg_desc* desc_dev, int n, uint8_t* out, int64_t out_bytes, void* workspace,
+                               size_t workspace_bytes, int32_t* status, void* stream);
 
 /* Empirical peaks of the box, used as second denominators by bench.py.
  * rpo_probe_peak_mfma: `blocks` workgroups of 4 waves each run `iters` rounds of 4 independent 32x32 MFMAs

@@ -16,7 +16,7 @@ RPO_F32, RPO_BF16, RPO_F16 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_QGELU_BWD, EPI_PATCH, EPI_LN_BIAS, EPI_LN_BIAS_QGELU = range(8)
 E_BADARG, E_SHAPE, E_DTYPE, E_ALIGN, E_WORKSPACE = -1, -2, -3, -4, -5      # include/rpo_amd.h RPO_E_*
 (E_JPEG_CORRUPT, E_JPEG_PROGRESSIVE, E_JPEG_ARITHMETIC, E_JPEG_LOSSLESS, E_JPEG_PRECISION, E_JPEG_COMPONENTS, E_JPEG_RGB,
- E_JPEG_SAMPLING, E_JPEG_MULTISCAN) = range(-20, -29, -1)
+ E_JPEG_SAMPLING, E_JPEG_MULTISCAN, E_JPEG_SCRIPT, E_JPEG_SEQUENTIAL) = range(-20, -31, -1)
 
 c_i64, c_i32, c_f32, c_vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 
@@ -194,6 +194,10 @@ SIGNATURES = {
     "rpo_jpeg_tables": (c_i32, [c_vp, c_i64, c_vp, c_i64]),
     "rpo_jpeg_workspace_bytes": (C.c_size_t, [C.POINTER(JpegDesc), c_i32]),
     "rpo_jpeg_decode_batch": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, C.c_size_t, c_vp, c_vp]),
+    "rpo_jpeg_prog_probe": (c_i32, [c_vp, c_i64, C.POINTER(JpegInfo)]),
+    "rpo_jpeg_prog_plan": (c_i32, [c_vp, c_i64, c_vp, c_i64]),
+    "rpo_jpeg_prog_workspace_bytes": (C.c_size_t, [C.POINTER(JpegDesc), c_i32]),
+    "rpo_jpeg_prog_decode_batch": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, C.c_size_t, c_vp, c_vp]),
 }
 
 # include/rpo_amd_experimental.h: bound only from the -DRPO_EXPERIMENTAL build of the library (RPO_EXPERIMENTAL=1)

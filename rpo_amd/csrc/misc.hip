@@ -744,6 +744,8 @@ extern "C" const char* rpo_error_string(int code) {
     case RPO_E_JPEG_RGB: return "rpo: jpeg: RGB-coded file, no YCbCr transform (decode on the host)";
     case RPO_E_JPEG_SAMPLING: return "rpo: jpeg: chroma sampling other than 4:4:4 / 4:2:2 / 4:2:0 (decode on the host)";
     case RPO_E_JPEG_MULTISCAN: return "rpo: jpeg: components spread over several scans (decode on the host)";
+    case RPO_E_JPEG_SCRIPT: return "rpo: jpeg: progressive scan script incomplete or inconsistent (decode on the host)";
+    case RPO_E_JPEG_SEQUENTIAL: return "rpo: jpeg: a sequential frame: rpo_jpeg_probe handles it, not rpo_jpeg_prog_probe";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "rpo: unknown error";
   }
 }

@@ -434,7 +434,7 @@ class DeviceImageSet:
     @classmethod
     def from_jpeg(cls, files: Sequence, labels: Sequence[int], device, budget_bytes: Optional[int] = None,
                   n_cls: Optional[int] = None, max_batch: int = 128, fallback: Optional[Callable] = None,
-                  chunk_images: int = 1024) -> "DeviceImageSet":
+                  chunk_images: int = 1024, progressive: bool = False) -> "DeviceImageSet":
         """The same set from JPEG files (`bytes`, or paths that are read here) without a host decode: Dassl's `read_image`
         (Pillow's `Image.open(path).convert("RGB")`) runs on the device (rpo_amd/jpeg.py), bit-identical to it.  Sizes
         come from the headers, so the packing plan is the one `DeviceImageSet(decoded)` computes.  Resident images are
@@ -442,7 +442,8 @@ class DeviceImageSet:
         in chunks and read back into `host_images`.  A file the device decoder refuses (progressive, CMYK, ...) goes
         through `fallback(bytes) -> uint8 [H, W, 3]` (default: Pillow, if importable) and is uploaded as pixels.
         `n_device` / `n_fallback` count the two routes; the set is otherwise indistinguishable from one built from
-        decoded arrays."""
+        decoded arrays.  `progressive=True` also decodes progressive files on the device (rpo_amd/jpeg.py: complete,
+        consistent Huffman scan scripts); what its probe refuses too takes the fallback with that probe's reason."""
         from .jpeg import JpegCorrupt, JpegDecoder, JpegRefused, probe
         if len(files) != len(labels):
             raise ValueError(f"{len(files)} files, {len(labels)} labels")
@@ -458,7 +459,7 @@ class DeviceImageSet:
         infos, decoded = [], {}
         for i, data in enumerate(datas):
             try:
-                infos.append(probe(data))
+                infos.append(probe(data, progressive))
             except JpegRefused as e:
                 infos.append(None)
                 if fallback is None:
@@ -490,7 +491,7 @@ class DeviceImageSet:
         self.labels_dev = torch.tensor(self.labels, dtype=torch.int64, device=self.dev)
         self._tail = None
         self.host_images = {i: decoded[i] for i in p.spilled if i in decoded}
-        dec = JpegDecoder(self.dev, chunk_images)
+        dec = JpegDecoder(self.dev, chunk_images, progressive=progressive)
         with torch.cuda.device(self.dev):
             for i, im in decoded.items():           # refused files that are resident: uploaded as pixels, as in _upload
                 if p.offsets[i] >= 0:

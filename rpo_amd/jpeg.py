@@ -7,6 +7,16 @@ for whole chunks of files of mixed sizes and modes.  `probe` accepts baseline, 8
 4:2:0, any restart interval, any table ids and segment packing.  Files it refuses raise `JpegRefused` with the library's
 reason; `DeviceImageSet.from_jpeg` routes those through a host decoder.
 
+Progressive files (SOF2, Huffman coded, 8-bit, the same components / sampling / colour rules) are decoded on the device too
+when `progressive=True` is given to `probe`, `JpegDecoder` and `DeviceImageSet.from_jpeg`; the default is off, and then they
+are refused as before.  The host walks all scans of such a file, checks that the scan script is consistent and complete
+(DESIGN.md 9f lists the rules; incomplete or inconsistent scripts, which libjpeg smooths or only warns about, stay with the
+host decoder, as do arithmetic-coded files) and uploads a per-file plan; the device zeroes the coefficient blocks, runs one
+entropy kernel per dependency level of the script (Pillow's ten-scan script has three) and then the same IDCT and colour
+kernels, so the pixels are those of the baseline file of the same coefficients.  A chunk's baseline and progressive files
+go through their two library calls into the same output buffer.  How large a share of the reference's datasets is
+progressive has not been measured by this project.
+
 What is tested (tests/golden/jpeg_streams.npz): the pixels are bit-identical to Pillow's for coefficient
 blocks an encoder can produce from 8-bit samples, at any quantiser (1..255) and with any valid Huffman tables.  Outside
 that domain -- header-valid streams no encoder writes: dense coefficients at dequantised amplitudes of 1020 and more, AC
@@ -57,11 +67,16 @@ def _align16(n: int) -> int:
     return (n + 15) // 16 * 16
 
 
-def probe(data: bytes) -> JpegInfo:
-    """Host only (no GPU): the header of one file, or `JpegRefused`."""
+def probe(data: bytes, progressive: bool = False) -> JpegInfo:
+    """Host only (no GPU): the header of one file, or `JpegRefused`.  With `progressive`, a file refused as progressive is
+    walked by `rpo_jpeg_prog_probe`; what that accepts has `info.reserved` (its number of dependency levels) > 0, what it
+    refuses raises with its reason."""
     lib = _lib.load()
     info = JpegInfo()
-    rc = lib.rpo_jpeg_probe(bytes(data), len(data), ctypes.byref(info))
+    data = bytes(data)
+    rc = lib.rpo_jpeg_probe(data, len(data), ctypes.byref(info))
+    if rc == _lib.E_JPEG_PROGRESSIVE and progressive:
+        rc = lib.rpo_jpeg_prog_probe(data, len(data), ctypes.byref(info))
     if rc != 0:
         msg = lib.rpo_error_string(int(rc))
         raise JpegRefused(int(rc), msg.decode() if msg else str(rc))
@@ -72,20 +87,20 @@ class JpegDecoder:
     """Chunked batch decode.  Two pinned staging slots alternate, as in `DeviceTransform`: chunk t+1 is packed on the host
     while chunk t is in flight; a slot is reused only after the event recorded behind its kernels has completed."""
 
-    def __init__(self, device, chunk_images: int = 1024, chunk_bytes: int = 256 << 20):
+    def __init__(self, device, chunk_images: int = 1024, chunk_bytes: int = 256 << 20, progressive: bool = False):
         if not 0 < chunk_images <= 65535:
             raise ValueError("chunk_images must be in 1..65535")
         self.dev = torch.device(device)
         if self.dev.type == "cuda" and self.dev.index is None:
             self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.chunk_images, self.chunk_bytes = int(chunk_images), int(chunk_bytes)
+        self.chunk_images, self.chunk_bytes, self.progressive = int(chunk_images), int(chunk_bytes), bool(progressive)
         self.lib = _lib.load()
         self.slots = [{"host": None, "dev": None, "done": None} for _ in range(2)]
         self.turn = 0
         self.ws = None
 
     def probe(self, data: bytes) -> JpegInfo:
-        return probe(data)
+        return probe(data, self.progressive)
 
     # ---- one chunk ---------------------------------------------------------------------------------------------
     def _slot(self, need: int):
@@ -100,41 +115,60 @@ class JpegDecoder:
         return slot
 
     def _chunk(self, files, infos, out: torch.Tensor, offsets) -> torch.Tensor:
-        """Enqueues the decode of `files` into out[offsets[i]:]; returns the chunk's int32 status tensor (device)."""
+        """Enqueues the decode of `files` into out[offsets[i]:]; returns the chunk's int32 status tensor (device), in file
+        order.  Baseline files (info.reserved == 0) and progressive ones go through their own library call, one behind the
+        other on the stream, out of the same staging slot and workspace."""
         n = len(files)
-        descs = (JpegDesc * n)()
-        desc_bytes = _align16(ctypes.sizeof(descs))
-        off = desc_bytes
-        for i, (data, info) in enumerate(zip(files, infos)):
-            d = descs[i]
-            d.info = info
-            d.file_offset, d.file_bytes = off - desc_bytes, len(data)
-            off += _align16(len(data))
-            d.table_offset = off - desc_bytes
-            off += _align16(int(info.table_bytes))
-            d.out_offset = int(offsets[i])
-        need_ws = self.lib.rpo_jpeg_workspace_bytes(descs, n)
-        if need_ws == 0:
-            raise ValueError("inconsistent JPEG descriptors (were the infos produced by probe()?)")
+        groups = [[i for i in range(n) if infos[i].reserved == 0], [i for i in range(n) if infos[i].reserved != 0]]
+        calls = [(self.lib.rpo_jpeg_tables, self.lib.rpo_jpeg_workspace_bytes, self.lib.rpo_jpeg_decode_batch, "rpo_jpeg"),
+                 (self.lib.rpo_jpeg_prog_plan, self.lib.rpo_jpeg_prog_workspace_bytes, self.lib.rpo_jpeg_prog_decode_batch,
+                  "rpo_jpeg_prog")]
+        descs = [(JpegDesc * max(len(g), 1))() for g in groups]
+        desc_bytes = _align16(n * ctypes.sizeof(JpegDesc))
+        off, need_ws = desc_bytes, 0
+        for g, ds, (_, ws_bytes, _, name) in zip(groups, descs, calls):
+            for k, i in enumerate(g):
+                d = ds[k]
+                d.info = infos[i]
+                d.file_offset, d.file_bytes = off - desc_bytes, len(files[i])
+                off += _align16(len(files[i]))
+                d.table_offset = off - desc_bytes
+                off += _align16(int(infos[i].table_bytes))
+                d.out_offset = int(offsets[i])
+            if g:
+                need = ws_bytes(ds, len(g))
+                if need == 0:
+                    raise ValueError("inconsistent JPEG descriptors (were the infos produced by probe()?)")
+                need_ws = max(need_ws, need)
         slot = self._slot(off)
         host, dev = slot["host"], slot["dev"]
         hv, base = host.numpy(), host.data_ptr() + desc_bytes
-        for i, data in enumerate(files):
-            d = descs[i]
-            fo = desc_bytes + d.file_offset
-            hv[fo:fo + len(data)] = np.frombuffer(data, np.uint8)
-            check(self.lib.rpo_jpeg_tables(base + d.file_offset, len(data), base + d.table_offset, int(d.info.table_bytes)),
-                  "rpo_jpeg_tables")
-        ctypes.memmove(host.data_ptr(), descs, ctypes.sizeof(descs))
+        at = 0
+        for g, ds, (tables, _, _, name) in zip(groups, descs, calls):
+            for k, i in enumerate(g):
+                d = ds[k]
+                fo = desc_bytes + d.file_offset
+                hv[fo:fo + len(files[i])] = np.frombuffer(files[i], np.uint8)
+                check(tables(base + d.file_offset, len(files[i]), base + d.table_offset, int(d.info.table_bytes)), name + "_tables")
+            ctypes.memmove(host.data_ptr() + at, ds, len(g) * ctypes.sizeof(JpegDesc))
+            at += len(g) * ctypes.sizeof(JpegDesc)
         if self.ws is None or self.ws.numel() < need_ws:
             self.ws = torch.empty(int(need_ws) + 4096, dtype=torch.uint8, device=self.dev)
         status = torch.empty(n, dtype=torch.int32, device=self.dev)
         stream = torch.cuda.current_stream(self.dev)
         dev[:off].copy_(host[:off], non_blocking=True)
-        check(self.lib.rpo_jpeg_decode_batch(dev.data_ptr() + desc_bytes, off - desc_bytes, ctypes.addressof(descs),
-                                             dev.data_ptr(), n, out.data_ptr(), out.numel(), self.ws.data_ptr(),
-                                             self.ws.numel(), status.data_ptr(), stream.cuda_stream),
-              "rpo_jpeg_decode_batch")
+        at = 0
+        for g, ds, (_, _, decode, name) in zip(groups, descs, calls):
+            if g:
+                check(decode(dev.data_ptr() + desc_bytes, off - desc_bytes, ctypes.addressof(ds),
+                             dev.data_ptr() + at * ctypes.sizeof(JpegDesc), len(g), out.data_ptr(), out.numel(),
+                             self.ws.data_ptr(), self.ws.numel(), status.data_ptr() + 4 * at, stream.cuda_stream),
+                      name + "_decode_batch")
+            at += len(g)
+        if groups[0] and groups[1]:                     # grouped order -> file order
+            ordered = torch.empty_like(status)
+            ordered[torch.tensor(groups[0] + groups[1], device=self.dev)] = status
+            status = ordered
         slot["done"] = torch.cuda.Event()
         slot["done"].record(stream)
         return status
@@ -149,7 +183,7 @@ class JpegDecoder:
         if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.dev:
             raise ValueError(f"out must be a contiguous uint8 tensor on {self.dev}")
         if infos is None:
-            infos = [probe(f) for f in files]
+            infos = [probe(f, self.progressive) for f in files]
         if not (len(files) == len(offsets) == len(infos)):
             raise ValueError("files, offsets and infos differ in length")
         statuses, lo = [], 0
@@ -171,7 +205,7 @@ class JpegDecoder:
 
     def decode(self, files: Sequence[bytes]) -> Tuple[torch.Tensor, List[int], List[Tuple[int, int]]]:
         """-> (buffer, offsets, sizes): one packed device buffer, 16-byte aligned offsets, (H, W) per file."""
-        infos = [probe(f) for f in files]
+        infos = [probe(f, self.progressive) for f in files]
         sizes = [(int(i.height), int(i.width)) for i in infos]
         offsets, off = [], 0
         for (H, W) in sizes:
