@@ -417,6 +417,23 @@ int rpo_head_fwd_bwd_grouped_act(const float* img_f, const float* text_f, const 
                                  void* d_text_f_act, int act_dtype, int S, int B, int C, int K, int e, float* workspace,
                                  void* stream);
 
+/* (ABI 8 addition) rpo_head_fwd_bwd_grouped_act with a per-group number of pairs: k_used, S int32 values on the DEVICE,
+ * 1 <= k_used[s] <= K.  K is the ablated hyper-parameter of the method (configs/trainers/RPO/main_K4.yaml, main.yaml,
+ * main_K24.yaml differ in it alone) and enters it in the head only (trainers/rpo.py:215-227: the mean over the K pairs);
+ * group s, k = k_used[s]:
+ *   logits = (scale_exp / k) * the sum over the pairs i < k;  the loss weights use scale_exp / (k B)
+ *   rows i >= k of d_img_f / d_text_f and of their act copies are written as exact zeros, and rows i >= k of img_f /
+ *   text_f are never read (they may hold anything, NaN included)
+ * The arrays keep the stride of K rows per image / class and the workspace the layout of K; both class-count regimes, chosen
+ * from B, C, e (and K) as in rpo_head_fwd_bwd_grouped; label NULL: eval, logits only.  Per group the bits of
+ * rpo_head_fwd_bwd[_act] called with K = k on the compacted [B, k, e] / [C, k, e] copies of the group's first k rows.  A
+ * k_used[s] outside [1, K] makes that group's logits, loss and gradients NaN (as an out-of-range target does) and reads or
+ * writes nothing out of bounds.  k_used NULL: RPO_E_BADARG (callers without per-group K call the entry points above). */
+int rpo_head_fwd_bwd_grouped_k(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                               float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_f_act,
+                               void* d_text_f_act, int act_dtype, int S, int B, int C, int K, int e,
+                               const int32_t* k_used, float* workspace, void* stream);
+
 /* Linear-probe head, cross-entropy and the gradient of the probe layer (trainers/linear_prob.py:61-95, :151-184):
  *   z      = img_f . w^T + bias                 (lp_layer = nn.Linear(e, e) on the UN-normalised image feature, :89-90)
  *   logits = scale_exp * z . text_f_n^T          (text_f_n: the normalised text features of preprocess, :77-83)
@@ -486,6 +503,21 @@ int rpo_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, floa
  * skipped first step then needs no special case); first_step as in rpo_sgd_step.  One workgroup. */
 int rpo_sgd_step_guarded(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd,
                          float grad_scale, int first_step, int32_t* found_inf, void* stream);
+
+/* (ABI 8 addition) rpo_sgd_step[_guarded] for `sets` runs with their OWN optimiser settings in one launch (LR, weight decay
+ * and warm-up are what one tunes per dataset: the OPTIM block of configs/trainers/RPO/main.yaml; trainers/rpo.py:274,298-309).  Set s is
+ * row s of p / g / buf (rows set_stride floats apart), of which the two segments [0, seg0) and [seg0, seg0 + seg1) -- text |
+ * img -- are stepped.  All tables are on the DEVICE:
+ *   hyper     float [sets, 4]: (lr, momentum, weight decay, grad_scale) of the set; a new learning rate is a copy into
+ *             this table, not a new kernel argument (a captured graph of the step stays valid)
+ *   used      int32 [sets, 2] or NULL (all): the number of leading floats of each of the two segments that belong to the
+ *             set (clamped to the segment); elements outside are neither scanned nor read for the verdict nor written
+ *   found_inf int32 [sets, 2] or NULL
+ * found_inf NULL: elementwise; per element of a set the bits of rpo_sgd_step with that set's four values.  Else one
+ * 1024-thread workgroup per set: per set the bits and the [flag, count] semantics of rpo_sgd_step_guarded, the scan and
+ * the skip being the set's own.  set_stride >= seg0 + seg1, sets <= 65535, else RPO_E_SHAPE.  One launch. */
+int rpo_sgd_step_sets(float* p, const float* g, float* buf, int64_t set_stride, int sets, const float* hyper,
+                      const int32_t* used, int64_t seg0, int64_t seg1, int first_step, int32_t* found_inf, void* stream);
 
 /* fp32 -> act dtype copy with leading dimensions (weight packing at load time) */
 int rpo_convert(const float* src, int64_t lds, void* dst, int dst_dtype, int64_t ldd,

@@ -169,6 +169,8 @@ SIGNATURES = {
                                          c_vp, c_vp]),
     "rpo_head_fwd_bwd_grouped_act": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
                                              c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "rpo_head_fwd_bwd_grouped_k": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                           c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rpo_lp_head_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "rpo_lp_head_fwd_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                     c_vp, c_vp]),
@@ -182,6 +184,7 @@ SIGNATURES = {
     "rpo_attnpool_attn": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_sgd_step": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "rpo_sgd_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp]),
+    "rpo_sgd_step_sets": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
     "rpo_convert": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),
     "rpo_probe_mfma": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rpo_probe_peak_mfma": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),

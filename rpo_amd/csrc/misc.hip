@@ -164,6 +164,74 @@ __global__ __launch_bounds__(1024) void sgd_guarded_kernel(float* p, const float
   }
 }
 
+// rpo_sgd_step_sets: the two kernels above with the set (blockIdx.y / blockIdx.x) as the outer index, the four scalars
+// read from the set's row of `hyper` (lr, momentum, weight decay, grad_scale) and the element range cut to the leading
+// used[set] = (u0, u1) floats of the segments [0, seg0) and [seg0, seg0 + seg1) of the set's row.  The update is written as
+// in sgd_kernel, so that it contracts to the same instructions: per element the bits of rpo_sgd_step[_guarded].
+__device__ __forceinline__ bool sgd_set_uses(int64_t i, int64_t seg0, int64_t u0, int64_t u1) {
+  return i < seg0 ? i < u0 : i - seg0 < u1;
+}
+__device__ __forceinline__ void sgd_set_ranges(const int32_t* used, int set, int64_t seg0, int64_t seg1, int64_t& u0,
+                                               int64_t& u1) {
+  u0 = seg0; u1 = seg1;
+  if (used != nullptr) {
+    u0 = min(max((int64_t)used[2 * set], (int64_t)0), seg0);
+    u1 = min(max((int64_t)used[2 * set + 1], (int64_t)0), seg1);
+  }
+}
+
+__global__ void sgd_sets_kernel(float* p, const float* __restrict__ g, float* buf, int64_t set_stride,
+                                const float* __restrict__ hyper, const int32_t* __restrict__ used, int64_t seg0,
+                                int64_t seg1, int first) {
+  const int set = blockIdx.y;
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= seg0 + seg1) return;
+  int64_t u0, u1;
+  sgd_set_ranges(used, set, seg0, seg1, u0, u1);
+  if (!sgd_set_uses(j, seg0, u0, u1)) return;
+  const float lr = hyper[4 * set], mom = hyper[4 * set + 1], wd = hyper[4 * set + 2], gs = hyper[4 * set + 3];
+  const int64_t i = (int64_t)set * set_stride + j;
+  const float pi = p[i];
+  const float gi = gs * g[i] + wd * pi;
+  const float bi = first ? gi : mom * buf[i] + gi;
+  buf[i] = bi;
+  p[i] = pi - lr * bi;
+}
+
+__global__ __launch_bounds__(1024) void sgd_sets_guarded_kernel(float* p, const float* __restrict__ g, float* buf,
+                                                                int64_t set_stride, const float* __restrict__ hyper,
+                                                                const int32_t* __restrict__ used, int64_t seg0,
+                                                                int64_t seg1, int first, int32_t* found) {
+  __shared__ int bad;
+  const int set = blockIdx.x;
+  p += (int64_t)set * set_stride; g += (int64_t)set * set_stride; buf += (int64_t)set * set_stride; found += 2 * set;
+  int64_t u0, u1;
+  sgd_set_ranges(used, set, seg0, seg1, u0, u1);
+  const int64_t n = seg0 + seg1;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int64_t i = threadIdx.x; i < n; i += 1024) {
+    if (!sgd_set_uses(i, seg0, u0, u1)) continue;
+    const float gi = g[i];
+    mine |= !(fabsf(gi) <= 3.402823466e38f);                        // Inf or NaN
+  }
+  if (mine) bad = 1;
+  __syncthreads();
+  const int skip = bad;
+  if (threadIdx.x == 0) { found[0] = skip; found[1] += skip; }
+  if (skip) return;
+  const float lr = hyper[4 * set], mom = hyper[4 * set + 1], wd = hyper[4 * set + 2], gs = hyper[4 * set + 3];
+  for (int64_t i = threadIdx.x; i < n; i += 1024) {
+    if (!sgd_set_uses(i, seg0, u0, u1)) continue;
+    const float pi = p[i];
+    const float gi = gs * g[i] + wd * pi;
+    const float bi = first ? gi : mom * buf[i] + gi;
+    buf[i] = bi;
+    p[i] = pi - lr * bi;
+  }
+}
+
 template <typename TO>
 __global__ void convert_kernel(const float* __restrict__ src, int64_t lds, TO* dst, int64_t ldd, int rows,
                                int cols) {
@@ -206,13 +274,43 @@ struct HeadGroups {
   int64_t bc;       // B * C       (logits)
   int64_t lab;      // B           (label)
   int64_t ws;       // workspace floats per group (rpo_head_workspace_floats)
+  const int32_t* k; // rpo_head_fwd_bwd_grouped_k: pairs in use per group (device, [S]); NULL: all K in every group
+  float scale_exp;  // (read only with k: the group's own scale_exp / k and scale_exp / (k B))
 };
 template <typename T> __device__ __forceinline__ T* head_shift(T* p, int64_t off) { return p == nullptr ? p : p + off; }
 __device__ __forceinline__ void* head_shift16(void* p, int64_t off) {            // act copies: 2-byte elements
   return p == nullptr ? p : static_cast<void*>(static_cast<uint16_t*>(p) + off);
 }
+// Per-group K (rpo_head_fwd_bwd_grouped_k): group s pairs only its first k = hg.k[s] of the K rows per image / class.  Every
+// kernel below bounds its pair index by head_k instead of K and takes the two factors that hold K from head_mul / head_gmul;
+// the strides stay those of K rows.  Rows i >= k are never read; their gradient rows are written as zeros (head_fill).  A k
+// outside [1, K] counts as 0 pairs with NaN factors: that group's logits, loss and gradients are NaN, nothing is read.
+// PK: the kernel instance of rpo_head_fwd_bwd_grouped_k.  The existing entry points launch the <.., false> instances, in which
+// all of this folds away: their code is what it was.
+template <bool PK> __device__ __forceinline__ int head_k(const HeadGroups& hg, int64_t s, int K) {
+  if constexpr (!PK) return K;
+  const int k = hg.k[s];
+  return k >= 1 && k <= K ? k : 0;
+}
+template <bool PK> __device__ __forceinline__ float head_mul(const HeadGroups& hg, int k, float mul) {     // scale_exp / k
+  if constexpr (!PK) return mul;
+  return k > 0 ? hg.scale_exp / (float)k : __builtin_nanf("");
+}
+template <bool PK> __device__ __forceinline__ float head_gmul(const HeadGroups& hg, int k, float gmul) {   // scale_exp / (k B)
+  if constexpr (!PK) return gmul;
+  return k > 0 ? hg.scale_exp / ((float)k * (float)hg.lab) : __builtin_nanf("");
+}
+__device__ __forceinline__ float head_fill(int k) { return k > 0 ? 0.0f : __builtin_nanf(""); }
 
-template <bool VEC>
+__device__ __forceinline__ void head_store(float* df, void* da, int act_dtype, int64_t off, float g) {
+  df[off] = g;
+  if (da != nullptr) {                       // the act-dtype copy the dX GEMM of the projection reads (RNE, as rpo_convert)
+    if (act_dtype == RPO_BF16) reinterpret_cast<uint16_t*>(da)[off] = (uint16_t)(pack2<bf16_t>(g, 0.f) & 0xffffu);
+    else reinterpret_cast<uint16_t*>(da)[off] = (uint16_t)(pack2<f16_t>(g, 0.f) & 0xffffu);
+  }
+}
+
+template <bool VEC, bool PK>
 __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restrict__ f_img, const float* __restrict__ f_txt,
                                                           float* ni, float* nt, float* logits, int C, int K, int e,
                                                           float mul, HeadGroups hg) {
@@ -223,9 +321,11 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
   }
   const int c = blockIdx.x, b = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ku = head_k<PK>(hg, blockIdx.z, K);
+  mul = head_mul<PK>(hg, ku, mul);
   float acc = 0.f;
 #pragma unroll 2
-  for (int i = wave; i < K; i += 4) {
+  for (int i = wave; i < ku; i += 4) {
     const float* x = f_img + ((int64_t)b * K + i) * e;
     const float* t = f_txt + ((int64_t)c * K + i) * e;
     float dot = 0.f, sx = 0.f, st = 0.f;
@@ -265,6 +365,7 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
 }
 
 // per image: loss_b = logsumexp - logit[label]; dl[b,c] = (softmax - onehot) * gmul
+template <bool PK>
 __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ logits,
                                                       const int64_t* __restrict__ label, float* dl,
                                                       float* loss_b, int C, float gmul, float* dlT, int B,
@@ -273,6 +374,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
   {
     const int64_t s = blockIdx.y;
     logits += s * hg.bc; label += s * hg.lab; dl += s * hg.ws; loss_b += s * hg.ws; dlT = head_shift(dlT, s * hg.ws);
+    gmul = head_gmul<PK>(hg, head_k<PK>(hg, s, 1 << 30), gmul);
   }
   const int b = blockIdx.x;
   const float* z = logits + (int64_t)b * C;
@@ -308,7 +410,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
 // B * C <= a few thousand exps) and forms its dl weights in LDS; block 0 also writes the mean loss.  Fixed summation
 // orders throughout.  F.cross_entropy (trainers/rpo.py:230) raises on an out-of-range target; a kernel cannot, so it
 // neither reads out of bounds nor returns a plausible number: the loss becomes NaN (hosts validate labels they can see).
-template <bool FUSED_CE>
+template <bool FUSED_CE, bool PK>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ f_img,
                                                        const float* __restrict__ ni, const float* __restrict__ f_txt,
                                                        const float* __restrict__ nt, float* d_img_f, float* d_text_f,
@@ -329,6 +431,15 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   const bool img = (int)blockIdx.x < B * K;
   const int row = img ? blockIdx.x : blockIdx.x - B * K;            // g*K + i
   const int g = row / K, i = row % K;
+  const int ku = head_k<PK>(hg, blockIdx.y, K);
+  if (PK && i >= ku) {                                              // a pair this group does not use: zeros, nothing read
+    if (loss != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *loss = __builtin_nanf("");     // (i = 0: k out of range)
+    void* da = img ? d_img_a : d_text_a;
+    for (int idx = threadIdx.x; idx < e; idx += 256)
+      head_store(img ? d_img_f : d_text_f, da, act_dtype, (int64_t)row * e + idx, head_fill(ku));
+    return;
+  }
+  gmul = head_gmul<PK>(hg, ku, gmul);
   const float* self_raw = img ? f_img : f_txt;
   const float* self_inv = img ? ni : nt;
   const float* other_raw = img ? f_txt : f_img;
@@ -431,6 +542,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // D[(r & 3) + 8 (r >> 2) + 4 half][l31].
 __device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
+template <bool PK>
 __global__ __launch_bounds__(64) void head_pairs_kernel(const float* __restrict__ f_img, const float* __restrict__ f_txt,
                                                         float* ni, float* nt, float* part, int B, int C, int K, int e,
                                                         HeadGroups hg) {
@@ -441,6 +553,7 @@ __global__ __launch_bounds__(64) void head_pairs_kernel(const float* __restrict_
   }
   const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
   const int c0 = blockIdx.x * 32, i = blockIdx.y;
+  if (PK && i >= head_k<PK>(hg, blockIdx.z, K)) return;                       // (nothing downstream reads P[i], ni, nt of such a pair)
   const int c = min(c0 + l31, C - 1);
   const float* t = f_txt + ((int64_t)c * K + i) * e + 4 * half;    // this lane's k's of an 8-wide step: 4 half .. 4 half + 3
   for (int b0 = 0; b0 < B; b0 += 32) {
@@ -487,18 +600,21 @@ __global__ __launch_bounds__(64) void head_pairs_kernel(const float* __restrict_
   }
 }
 
+template <bool PK>
 __global__ __launch_bounds__(256) void head_sum_kernel(const float* __restrict__ part, float* logits, int BC, int K, float mul,
                                                       HeadGroups hg) {
   part += (int64_t)blockIdx.y * hg.ws; logits += (int64_t)blockIdx.y * hg.bc;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= BC) return;
+  const int ku = head_k<PK>(hg, blockIdx.y, K);
   float s = 0.f;
-  for (int i = 0; i < K; ++i) s += part[(int64_t)i * BC + idx];
-  logits[idx] = s * mul;
+  for (int i = 0; i < ku; ++i) s += part[(int64_t)i * BC + idx];
+  logits[idx] = s * head_mul<PK>(hg, ku, mul);
 }
 
 // blocks [0, K * ceil(C / 256)): s_t, one thread per (i, c); then B * K blocks: s_x, one block per (b, i); block 0 also the
 // mean loss
+template <bool PK>
 __global__ __launch_bounds__(256) void head_rowdots_kernel(const float* __restrict__ dl, const float* __restrict__ part,
                                                            float* s_t, float* s_x, int B, int C, int K,
                                                            const float* loss_b, float* loss, HeadGroups hg) {
@@ -513,14 +629,16 @@ __global__ __launch_bounds__(256) void head_rowdots_kernel(const float* __restri
     for (int b = 0; b < B; ++b) s += loss_b[b];
     *loss = s / (float)B;
   }
+  const int ku = head_k<PK>(hg, blockIdx.y, K);
   if ((int)blockIdx.x < K * ct) {
     const int i = blockIdx.x / ct, c = (blockIdx.x - i * ct) * 256 + threadIdx.x;
-    if (c >= C) return;
+    if (c >= C || (PK && i >= ku)) return;
     float s = 0.f;
     for (int b = 0; b < B; ++b) s = fmaf(dl[(int64_t)b * C + c], part[((int64_t)i * B + b) * C + c], s);
     s_t[(int64_t)c * K + i] = s;
   } else {
     const int row = blockIdx.x - K * ct, b = row / K, i = row - b * K;
+    if (PK && i >= ku) return;
     float s = 0.f;
     for (int c = threadIdx.x; c < C; c += 256) s = fmaf(dl[(int64_t)b * C + c], part[((int64_t)i * B + b) * C + c], s);
     s = block_sum(s, red);
@@ -528,15 +646,8 @@ __global__ __launch_bounds__(256) void head_rowdots_kernel(const float* __restri
   }
 }
 
-__device__ __forceinline__ void head_store(float* df, void* da, int act_dtype, int64_t off, float g) {
-  df[off] = g;
-  if (da != nullptr) {                       // the act-dtype copy the dX GEMM of the projection reads (RNE, as rpo_convert)
-    if (act_dtype == RPO_BF16) reinterpret_cast<uint16_t*>(da)[off] = (uint16_t)(pack2<bf16_t>(g, 0.f) & 0xffffu);
-    else reinterpret_cast<uint16_t*>(da)[off] = (uint16_t)(pack2<f16_t>(g, 0.f) & 0xffffu);
-  }
-}
-
 // d text_f: one wave per (32-class tile, i, group of e-tiles); D[class][e] over the image pairs (2 kk, 2 kk + 1)
+template <bool PK>
 __global__ __launch_bounds__(64) void head_bwd_text_kernel(const float* __restrict__ dl, const float* __restrict__ f_img,
                                                            const float* __restrict__ ni, const float* __restrict__ f_txt,
                                                            const float* __restrict__ nt, const float* __restrict__ s_t,
@@ -551,6 +662,16 @@ __global__ __launch_bounds__(64) void head_bwd_text_kernel(const float* __restri
     f_img += s * hg.img; f_txt += s * hg.txt; d_text_f += s * hg.txt; d_text_a = head_shift16(d_text_a, s * hg.txt);
   }
   const int c0 = blockIdx.x * 32, i = blockIdx.y;
+  const int ku = head_k<PK>(hg, blockIdx.z / ez, K);
+  if (PK && i >= ku) {                                              // a pair this group does not use: zeros, nothing read
+    for (int et = bz * etiles_per_block; et < min((bz + 1) * etiles_per_block, e >> 5); ++et)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int cn = c0 + mfma_row(r, half);
+        if (cn < C) head_store(d_text_f, d_text_a, act_dtype, ((int64_t)cn * K + i) * e + et * 32 + l31, head_fill(ku));
+      }
+    return;
+  }
   const int c = min(c0 + l31, C - 1);
   float itv[16], cf[16];                                            // per accumulator row: 1 / |t|, <h, dh> / |t|^2
 #pragma unroll
@@ -607,6 +728,7 @@ __global__ __launch_bounds__(64) void head_bwd_text_kernel(const float* __restri
 // pairs w, w + 8, ... in batches of 8: 24 loads in flight per wave, ~3 waves per SIMD at 1000 classes); the eight partial
 // tiles are summed through LDS in wave order.  dlT = dl transposed [C][B].
 constexpr int HEAD_IMG_WAVES = 8;
+template <bool PK>
 __global__ __launch_bounds__(64 * HEAD_IMG_WAVES) void head_bwd_img_kernel(
     const float* __restrict__ dlT, const float* __restrict__ f_img, const float* __restrict__ ni,
     const float* __restrict__ f_txt, const float* __restrict__ nt, const float* __restrict__ s_x, float* d_img_f,
@@ -619,6 +741,15 @@ __global__ __launch_bounds__(64 * HEAD_IMG_WAVES) void head_bwd_img_kernel(
     f_img += s * hg.img; f_txt += s * hg.txt; d_img_f += s * hg.img; d_img_a = head_shift16(d_img_a, s * hg.img);
   }
   const int i = blockIdx.x, col = blockIdx.y * 32 + l31, b0 = (blockIdx.z % btiles) * 32;
+  const int ku = head_k<PK>(hg, blockIdx.z / btiles, K);
+  if (PK && i >= ku) {                                              // a pair this group does not use: zeros, nothing read
+#pragma unroll
+    for (int rr = 0; rr < 16 / HEAD_IMG_WAVES; ++rr) {
+      const int bn = b0 + mfma_row(wave + HEAD_IMG_WAVES * rr, half);
+      if (bn < B) head_store(d_img_f, d_img_a, act_dtype, ((int64_t)bn * K + i) * e + col, head_fill(ku));
+    }
+    return;
+  }
   const int b = min(b0 + l31, B - 1);
   f32x16_t d;
 #pragma unroll
@@ -835,16 +966,19 @@ extern "C" int64_t rpo_head_workspace_floats(int B, int C, int K, int e) {
 
 // S independent heads (S = 1: the plain call); group s works in workspace [s * wsg, (s + 1) * wsg), wsg =
 // rpo_head_workspace_floats(B, C, K, e), laid out as a single head's.
+template <bool PK>
 static int head_impl(const float* img_f, const float* text_f, const int64_t* label, float scale_exp, float* logits,
                      float* loss, float* d_img_f, float* d_text_f, void* d_img_act, void* d_text_act, int act_dtype, int S,
-                     int B, int C, int K, int e, float* ws, void* stream) {
+                     int B, int C, int K, int e, float* ws, void* stream, const int32_t* k_used = nullptr) {
+  if (PK != (k_used != nullptr)) return RPO_E_BADARG;
   if (!img_f || !text_f || !logits || !ws || S <= 0 || B <= 0 || C <= 0 || K <= 0 || e <= 0) return RPO_E_BADARG;
   if ((d_img_act || d_text_act) && act_dtype != RPO_BF16 && act_dtype != RPO_F16) return RPO_E_DTYPE;
   if (label && (!loss || !d_img_f || !d_text_f)) return RPO_E_BADARG;
   if (e > 1024 || S > 1024 || (int64_t)((B + 31) / 32) * S > 65535) return RPO_E_SHAPE;   // (grid.z of the image backward)
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t G = (uint32_t)S;
-  const HeadGroups hg{(int64_t)B * K * e, (int64_t)C * K * e, (int64_t)B * C, (int64_t)B, rpo_head_workspace_floats(B, C, K, e)};
+  const HeadGroups hg{(int64_t)B * K * e, (int64_t)C * K * e, (int64_t)B * C, (int64_t)B, rpo_head_workspace_floats(B, C, K, e),
+                      k_used, scale_exp};
   float* ni = ws;
   float* nt = ni + (int64_t)B * K;
   float* dl = nt + (int64_t)C * K;
@@ -864,41 +998,41 @@ static int head_impl(const float* img_f, const float* text_f, const int64_t* lab
                          (s_x + (int64_t)B * K) - ws <= rpo_head_workspace_floats(B, C, K, e) && (int64_t)B * C < (1ll << 31);
 #endif
   if (mfma_head) {
-    hipLaunchKernelGGL(head_pairs_kernel, dim3((C + 31) / 32, K, G), dim3(64), 0, s, img_f, text_f, ni, nt, part, B, C, K, e, hg);
-    hipLaunchKernelGGL(head_sum_kernel, dim3((B * C + 255) / 256, G), dim3(256), 0, s, part, logits, B * C, K, mul, hg);
+    hipLaunchKernelGGL(head_pairs_kernel<PK>, dim3((C + 31) / 32, K, G), dim3(64), 0, s, img_f, text_f, ni, nt, part, B, C, K, e, hg);
+    hipLaunchKernelGGL(head_sum_kernel<PK>, dim3((B * C + 255) / 256, G), dim3(256), 0, s, part, logits, B * C, K, mul, hg);
     if (!label) return rpo_launch_status();
-    hipLaunchKernelGGL(head_ce_kernel, dim3(B, G), dim3(256), 0, s, logits, label, dl, lb, C, gmul, dlT, B, hg);
-    hipLaunchKernelGGL(head_rowdots_kernel, dim3(K * ((C + 255) / 256) + B * K, G), dim3(256), 0, s, dl, part, s_t, s_x, B, C, K,
+    hipLaunchKernelGGL(head_ce_kernel<PK>, dim3(B, G), dim3(256), 0, s, logits, label, dl, lb, C, gmul, dlT, B, hg);
+    hipLaunchKernelGGL(head_rowdots_kernel<PK>, dim3(K * ((C + 255) / 256) + B * K, G), dim3(256), 0, s, dl, part, s_t, s_x, B, C, K,
                        lb, loss, hg);
 #ifndef RPO_HEAD_TEXT_EZ
 #define RPO_HEAD_TEXT_EZ 4
 #endif
     const int etiles = e / 32, ez = etiles >= RPO_HEAD_TEXT_EZ ? RPO_HEAD_TEXT_EZ : 1;
     const int btiles = (B + 31) / 32;
-    hipLaunchKernelGGL(head_bwd_text_kernel, dim3((C + 31) / 32, K, ez * G), dim3(64), 0, s, dl, img_f, ni, text_f, nt, s_t,
+    hipLaunchKernelGGL(head_bwd_text_kernel<PK>, dim3((C + 31) / 32, K, ez * G), dim3(64), 0, s, dl, img_f, ni, text_f, nt, s_t,
                        d_text_f, d_text_act, act_dtype, B, C, K, e, (etiles + ez - 1) / ez, ez, hg);
-    hipLaunchKernelGGL(head_bwd_img_kernel, dim3(K, etiles, btiles * G), dim3(64 * HEAD_IMG_WAVES), 0, s, dlT, img_f, ni, text_f, nt, s_x,
+    hipLaunchKernelGGL(head_bwd_img_kernel<PK>, dim3(K, etiles, btiles * G), dim3(64 * HEAD_IMG_WAVES), 0, s, dlT, img_f, ni, text_f, nt, s_x,
                        d_img_f, d_img_act, act_dtype, B, C, K, e, btiles, hg);
     return rpo_launch_status();
   }
   if (B > 65535) return RPO_E_SHAPE;
   if (e % 256 == 0 && aligned16(img_f) && aligned16(text_f))
-    hipLaunchKernelGGL(head_logits_kernel<true>, dim3(C, B, G), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul, hg);
+    hipLaunchKernelGGL((head_logits_kernel<true, PK>), dim3(C, B, G), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul, hg);
   else
-    hipLaunchKernelGGL(head_logits_kernel<false>, dim3(C, B, G), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul, hg);
+    hipLaunchKernelGGL((head_logits_kernel<false, PK>), dim3(C, B, G), dim3(256), 0, s, img_f, text_f, ni, nt, logits, C, K, e, mul, hg);
   if (!label) return rpo_launch_status();
   // Small class sets (the few-shot base / new splits; 19 for Oxford-Pets base): two launches per training step, the
   // cross-entropy is recomputed inside the backward blocks.  Larger ones (ImageNet: 500 / 1000 classes) get their own
   // cross-entropy launch and a dl array.
   const int nmax = B > C ? B : C;
   if (C <= 128 && B <= 2048) {
-    hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(B * K + C * K, G), dim3(256), (size_t)(nmax + 3 * B) * sizeof(float), s,
+    hipLaunchKernelGGL((head_bwd_kernel<true, PK>), dim3(B * K + C * K, G), dim3(256), (size_t)(nmax + 3 * B) * sizeof(float), s,
                        dl, img_f, ni, text_f, nt, d_img_f, d_text_f, B, C, K, e, lb, loss, logits, label, gmul, d_img_act, d_text_act, act_dtype, hg);
     return rpo_launch_status();
   }
   if ((size_t)nmax * sizeof(float) > 64 * 1024) return RPO_E_SHAPE;
-  hipLaunchKernelGGL(head_ce_kernel, dim3(B, G), dim3(256), 0, s, logits, label, dl, lb, C, gmul, static_cast<float*>(nullptr), 0, hg);
-  hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(B * K + C * K, G), dim3(256), (size_t)nmax * sizeof(float), s, dl, img_f,
+  hipLaunchKernelGGL(head_ce_kernel<PK>, dim3(B, G), dim3(256), 0, s, logits, label, dl, lb, C, gmul, static_cast<float*>(nullptr), 0, hg);
+  hipLaunchKernelGGL((head_bwd_kernel<false, PK>), dim3(B * K + C * K, G), dim3(256), (size_t)nmax * sizeof(float), s, dl, img_f,
                      ni, text_f, nt, d_img_f, d_text_f, B, C, K, e, lb, loss, logits, label, gmul, d_img_act, d_text_act, act_dtype, hg);
   return rpo_launch_status();
 }
@@ -906,7 +1040,7 @@ static int head_impl(const float* img_f, const float* text_f, const int64_t* lab
 extern "C" int rpo_head_fwd_bwd(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
                                 float* logits, float* loss, float* d_img_f, float* d_text_f, int B, int C, int K,
                                 int e, float* ws, void* stream) {
-  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32, 1, B, C, K, e,
+  return head_impl<false>(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32, 1, B, C, K, e,
                    ws, stream);
 }
 
@@ -914,14 +1048,14 @@ extern "C" int rpo_head_fwd_bwd_act(const float* img_f, const float* text_f, con
                                     float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_act,
                                     void* d_text_act, int act_dtype, int B, int C, int K, int e, float* ws,
                                     void* stream) {
-  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, 1, B,
+  return head_impl<false>(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, 1, B,
                    C, K, e, ws, stream);
 }
 
 extern "C" int rpo_head_fwd_bwd_grouped(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
                                         float* logits, float* loss, float* d_img_f, float* d_text_f, int S, int B, int C,
                                         int K, int e, float* ws, void* stream) {
-  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32, S, B, C, K, e,
+  return head_impl<false>(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, nullptr, nullptr, RPO_F32, S, B, C, K, e,
                    ws, stream);
 }
 
@@ -929,8 +1063,19 @@ extern "C" int rpo_head_fwd_bwd_grouped_act(const float* img_f, const float* tex
                                             float scale_exp, float* logits, float* loss, float* d_img_f, float* d_text_f,
                                             void* d_img_act, void* d_text_act, int act_dtype, int S, int B, int C, int K,
                                             int e, float* ws, void* stream) {
-  return head_impl(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, S, B,
-                   C, K, e, ws, stream);
+  return head_impl<false>(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, S,
+                          B, C, K, e, ws, stream);
+}
+
+// Per-group K: the grouped head with k_used[s] of the K pairs in use in group s (HeadGroups::k).  The same kernels and
+// launches, in their PK instances; callers without per-group K keep the entry points above and the instances they had.
+extern "C" int rpo_head_fwd_bwd_grouped_k(const float* img_f, const float* text_f, const int64_t* label, float scale_exp,
+                                          float* logits, float* loss, float* d_img_f, float* d_text_f, void* d_img_act,
+                                          void* d_text_act, int act_dtype, int S, int B, int C, int K, int e,
+                                          const int32_t* k_used, float* ws, void* stream) {
+  if (!k_used) return RPO_E_BADARG;
+  return head_impl<true>(img_f, text_f, label, scale_exp, logits, loss, d_img_f, d_text_f, d_img_act, d_text_act, act_dtype, S, B,
+                         C, K, e, ws, stream, k_used);
 }
 
 // ---- CoCoOp's meta-net (trainers/cocoop.py:93-97, :137-143) -----------------------------------------------------------
@@ -1054,6 +1199,20 @@ extern "C" int rpo_sgd_step_guarded(float* p, const float* g, float* buf, int64_
   if (!p || !g || !buf || !found_inf || n <= 0) return RPO_E_BADARG;
   hipLaunchKernelGGL(sgd_guarded_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), p, g, buf, n, lr,
                      momentum, wd, grad_scale, first_step, found_inf);
+  return rpo_launch_status();
+}
+
+extern "C" int rpo_sgd_step_sets(float* p, const float* g, float* buf, int64_t set_stride, int sets, const float* hyper,
+                                 const int32_t* used, int64_t seg0, int64_t seg1, int first_step, int32_t* found_inf,
+                                 void* stream) {
+  if (!p || !g || !buf || !hyper || sets <= 0 || seg0 < 0 || seg1 < 0 || seg0 + seg1 <= 0) return RPO_E_BADARG;
+  if (set_stride < seg0 + seg1 || sets > 65535) return RPO_E_SHAPE;
+  if (found_inf)
+    hipLaunchKernelGGL(sgd_sets_guarded_kernel, dim3(sets), dim3(1024), 0, static_cast<hipStream_t>(stream), p, g, buf,
+                       set_stride, hyper, used, seg0, seg1, first_step, found_inf);
+  else
+    hipLaunchKernelGGL(sgd_sets_kernel, dim3((unsigned)((seg0 + seg1 + 255) / 256), sets), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), p, g, buf, set_stride, hyper, used, seg0, seg1, first_step);
   return rpo_launch_status();
 }
 

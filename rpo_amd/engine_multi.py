@@ -34,9 +34,14 @@ class MultiEngineMixin:
     _multi = None                       # S while a multi-run step is being enqueued (`_multi_mode`), else None
     multi_S = 0                         # S of `multi_setup`, 0 before it
 
-    def multi_setup(self, S: int, B: int) -> None:
+    m_k_used = None                     # int32 [S] on the device: the members' own K (`multi_setup(..., member_K=)`), or None
+
+    def multi_setup(self, S: int, B: int, member_K=None) -> None:
         """Buffers of the multi-run step for S members of batch B.  Allocates nothing the single-run engine uses and
-        changes none of its buffers."""
+        changes none of its buffers.  `member_K`: per member, how many of the engine's K prompt pairs it uses (DESIGN.md
+        section 9i) -- the heads then average over the member's own K_s (rpo_head_fwd_bwd_grouped_k) and the rows
+        i >= K_s ("inert") start at zero, get zero gradients and ride along through the towers: a member with K_s < K
+        costs what a K member costs.  Without it everything is as it was."""
         from .engine import SPLIT_FC, SPLIT_Q
         cfg, dev, act = self.cfg, self.dev, self.act
         self._refuse_rn("multi_setup")
@@ -46,6 +51,11 @@ class MultiEngineMixin:
             raise ValueError(f"multi_setup: S * B = {S * B} images per step, the engine was built with max_batch = "
                              f"{self.max_batch} (build it with max_batch >= S * B: the image tower's plans are chosen for it)")
         K, dv, dt, e, n, Lt = cfg.K, cfg.d_v, cfg.d_t, cfg.embed, cfg.n_cls, cfg.layers_t
+        if member_K is not None:
+            member_K = [int(k) for k in member_K]
+            if len(member_K) != S or any(not 1 <= k <= K for k in member_K):
+                raise ValueError(f"multi_setup: member_K = {member_K} for S = {S} members of an engine with K = {K}: one "
+                                 "value in [1, K] per member")
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         a = lambda *s: torch.empty(*s, dtype=act, device=dev)
         au = f32 if os.environ.get("RPO_AUX_F32") == "1" else a
@@ -74,6 +84,11 @@ class MultiEngineMixin:
         self.multi_S, self.multi_B = S, B
         nt, ni = K * dt, K * dv
         self.m_params = f32(S, nt + ni)
+        self.multi_K = member_K
+        self.m_k_used = None
+        if member_K is not None:
+            self.m_params.zero_()                                    # (inert rows: finite whatever the caller sets later)
+            self.m_k_used = torch.tensor(member_K, dtype=torch.int32, device=dev)
         self.m_grads = torch.zeros(S, nt + ni, dtype=torch.float32, device=dev)
         self.m_mom = torch.zeros(S, nt + ni, dtype=torch.float32, device=dev)
         # member s's prompts / gradients: column blocks of its row (sets strided by nt + ni floats)
@@ -155,7 +170,7 @@ class MultiEngineMixin:
                                  self.logit_scale_exp, self.m_logits, self.m_loss if train else None,
                                  self.d_img_f[:S * B * K].view(S * B, K, e) if train else None,
                                  mb["d_text_f"].view(S * n, K, e) if train else None, self.m_head_ws, S,
-                                 **(act if train else {}))
+                                 k_used=self.m_k_used, **(act if train else {}))
 
     def multi_forward_backward(self, image: torch.Tensor, label: torch.Tensor) -> None:
         """Enqueue loss + both prompt gradients of every member: image [S*B, 3, H, W] and label [S*B], member-major.

@@ -149,32 +149,34 @@ class PromptRowsEngineMixin:
         self._gemm(self.pr_y_post[:R], self.img_proj_t, self.pr_img_f[:R], EPI_NONE)
         return self.pr_img_f[:R]
 
-    def _prompt_rows_body(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor) -> None:
+    def _prompt_rows_body(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor, k_used=None) -> None:
         S, K, e, n = img_prompts.shape[0], self.cfg.K, self.cfg.embed, self.cfg.n_cls
         img_f = self.image_prompt_rows(B, kv, img_prompts)
         ops.head_fwd_bwd_grouped(img_f.view(S * B, K, e), text_f.view(S * n, K, e), None, self.logit_scale_exp,
-                                 self.pr_logits[:S * B], None, None, None, self.pr_head_ws, S)
+                                 self.pr_logits[:S * B], None, None, None, self.pr_head_ws, S, k_used=k_used)
 
     def shared_eval_logits(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor,
-                           use_graph: bool = True) -> torch.Tensor:
+                           use_graph: bool = True, k_used: Optional[torch.Tensor] = None) -> torch.Tensor:
         """logits [S, B, n_cls] (the engine's own buffer, valid until the next call) of the S prompt sets for the chunk `kv`
         names: the prompt-row pass and the grouped head, ONE HIP graph per (S, B) and K / V source on the current
-        stream -- eager warm-up first, then capture, as `forward_eval`.  text_f [S * n_cls * K, e]: the sets' text features."""
+        stream -- eager warm-up first, then capture, as `forward_eval`.  text_f [S * n_cls * K, e]: the sets' text features.
+        k_used: int32 [S] on the device -- set s averages over its first k_used[s] pairs (rpo_head_fwd_bwd_grouped_k)."""
         S, n = img_prompts.shape[0], self.cfg.n_cls
         assert text_f.shape[0] == S * n * self.cfg.K and text_f.is_contiguous()
         if S * B > self.pr_logits.shape[0] or B > self.pr_B or S > self.pr_S:
             raise RuntimeError(f"shared_eval_logits: S = {S}, B = {B}; prompt_rows_setup({self.pr_S}, {self.pr_B})")
         if not use_graph or os.environ.get("RPO_NO_EVAL_GRAPH") == "1":
-            self._prompt_rows_body(B, kv, img_prompts, text_f)
+            self._prompt_rows_body(B, kv, img_prompts, text_f, k_used)
             return self.pr_logits[:S * B].view(S, B, n)
-        key = (self.pr_gen, S, B, img_prompts.data_ptr(), img_prompts.stride(0), text_f.data_ptr())
+        key = (self.pr_gen, S, B, img_prompts.data_ptr(), img_prompts.stride(0), text_f.data_ptr()) + (
+            () if k_used is None else (k_used.data_ptr(),))
         g = kv.graphs.get(key)
         if g is None:
-            self._prompt_rows_body(B, kv, img_prompts, text_f)         # eager warm-up: sets kernel attributes
+            self._prompt_rows_body(B, kv, img_prompts, text_f, k_used)         # eager warm-up: sets kernel attributes
             torch.cuda.synchronize(self.dev)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._prompt_rows_body(B, kv, img_prompts, text_f)
+                self._prompt_rows_body(B, kv, img_prompts, text_f, k_used)
             kv.graphs[key] = g
         g.replay()
         return self.pr_logits[:S * B].view(S, B, n)

@@ -91,8 +91,9 @@ class EvalMixin:
         """`test` for S prompt sets at once on the shared frozen image rows (rpo_amd/engine_prompt_rows.py): per chunk
         (those of `test`) one frozen pass -- none with `frozen`, a `FrozenImageKV` of this set -- and ONE prompt-row pass +
         grouped head for all sets; every set has its own counts / confusion matrix, filled by `rpo_eval_accumulate` on
-        its slice of the logits; one read-back.  `sides()` -> (img_prompts [S, K, d_v], text_f [S * n_cls * K, e]), called
-        once with the device current.  `hook(b0, logits [S, B, n_cls])` sees each chunk's logits (the engine's buffer)."""
+        its slice of the logits; one read-back.  `sides()` -> (img_prompts [S, K, d_v], text_f [S * n_cls * K, e], k_used), called once
+        with the device current; k_used is None, or int32 [S] on the device for sets that average over their own number
+        of pairs (`RPOSweep`).  `hook(b0, logits [S, B, n_cls])` sees each chunk's logits (the engine's buffer)."""
         eng, n, C = self.engine, len(image_set), self.cfg.n_cls
         if frozen is not None:
             frozen.check(eng, image_set)
@@ -100,7 +101,7 @@ class EvalMixin:
         evs = [Classification(C, per_class_result) for _ in range(S)]
         with torch.cuda.device(self.device):
             eng.prompt_rows_setup(S, chunk)
-            img_prompts, text_f = sides()
+            img_prompts, text_f, k_used = sides()
             counts = torch.zeros(S, 2, dtype=torch.int64, device=self.device)
             cmat = torch.zeros(S, C * C, dtype=torch.int32, device=self.device)
             if frozen is None:
@@ -118,7 +119,7 @@ class EvalMixin:
                 else:
                     kv = frozen.kv
                     kv.set_first(b0, B)
-                logits = eng.shared_eval_logits(B, kv, img_prompts, text_f)
+                logits = eng.shared_eval_logits(B, kv, img_prompts, text_f, k_used=k_used)
                 if hook is not None:
                     hook(b0, logits)
                 for s in range(S):

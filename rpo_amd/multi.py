@@ -88,6 +88,8 @@ def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig)
 
 
 class RPOMulti(EvalMixin):
+    captures = 0                                        # HIP graphs of the step captured so far (one per distinct learning rate)
+
     def __init__(self, cfg, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None, n_runs: int = 1,
                  batch_size: int = 4, prompts: Optional[Sequence[tuple]] = None, seeds: Optional[Sequence[int]] = None,
                  optim=None, device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.bfloat16,
@@ -109,15 +111,21 @@ class RPOMulti(EvalMixin):
             raise ValueError("RPOMulti: pass exactly one of prompts=[(text_prompt, img_prompt)] * n_runs or seeds=[...]")
         if len(prompts if prompts is not None else seeds) != S:
             raise ValueError(f"RPOMulti: {len(prompts if prompts is not None else seeds)} prompts / seeds for n_runs = {S}")
-        self.cfg, self.n_runs, self.batch_size, self.num_batches = cfg, S, B, num_batches
         self.optim_cfg = optim or OptimConfig()
-        self.use_graph = use_graph
-        self.epoch = self.batch_idx = self._steps = 0
         self.lr = lr_at_epoch(self.optim_cfg, 0)
-        self._graph = None                              # (HIP graph of one step, the learning rate it was captured with)
-        self._warm = False
         if prompts is None:
             prompts = seeded_prompts(state_dict, cfg, seeds)
+        self._build(cfg, state_dict, tokens, S, B, prompts, device, act_dtype, num_batches, use_graph)
+
+    def _build(self, cfg, state_dict, tokens, S: int, B: int, prompts, device, act_dtype, num_batches: int, use_graph: bool,
+               member_K: Optional[Sequence[int]] = None) -> None:
+        """Everything behind the refusals: the loop state, the engine for S * B images and the members' buffers (shared with
+        `RPOSweep`, whose members bring their own K: `member_K`)."""
+        self.cfg, self.n_runs, self.batch_size, self.num_batches = cfg, S, B, num_batches
+        self.use_graph = use_graph
+        self.epoch = self.batch_idx = self._steps = 0
+        self._graph = None                              # (HIP graph of one step, the `_graph_key` it was captured with)
+        self._warm = False
         self.device = torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -131,7 +139,7 @@ class RPOMulti(EvalMixin):
         with torch.cuda.device(self.device):
             # the image tower's workspace, GEMM plans and row-unit hints are those of S * B images
             self.engine = make_engine(cfg, state_dict, tokens, self.device, act_dtype, S * B)
-            self.engine.multi_setup(S, B)
+            self.engine.multi_setup(S, B, **({} if member_K is None else dict(member_K=member_K)))
             self.set_prompts(prompts)
             self._image = torch.zeros(S * B, 3, cfg.image_size, cfg.image_size, device=self.device)
             self._label = torch.zeros(S * B, dtype=torch.int64, device=self.device)
@@ -169,7 +177,7 @@ class RPOMulti(EvalMixin):
             self._enqueue(self._image, self._label)
             self._warm = True
         else:
-            if self._graph is None or self._graph[1] != self.lr:
+            if self._graph is None or self._graph[1] != self._graph_key():
                 if not self._warm:                      # (a resumed run: kernel attributes are set by an eager launch, not in
                     self.engine.multi_forward_backward(self._image, self._label)    # a capture; it writes only what the step
                     self._warm = True                                                 # overwrites)
@@ -177,12 +185,17 @@ class RPOMulti(EvalMixin):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._enqueue(self._image, self._label)
-                self._graph = (g, self.lr)             # (capture does not execute: the replay below is this step)
+                self._graph = (g, self._graph_key())   # (capture does not execute: the replay below is this step)
+                self.captures += 1
             self._graph[0].replay()
         self._steps += 1
         self._eval_member = None
         self.engine.text_f_version = -1
         return self.engine.m_loss
+
+    def _graph_key(self):
+        """What a captured step has baked in besides addresses: the learning rate (a kernel argument of rpo_sgd_step)."""
+        return self.lr
 
     def parse_batch_train(self, batches: Sequence[dict]):
         """S Dassl-style batches {"img": float [B, 3, H, W], "label": [B]} -> one member-major device batch."""
@@ -300,24 +313,31 @@ class RPOMulti(EvalMixin):
 
     # ------------------------------------------------------------------ evaluation: all members per frozen image pass
     def _shared_sides(self):
+        """(img_prompts [S, K, d_v], text_f [S * n_cls * K, e], k_used): k_used is None here -- every member averages over
+        all K pairs; `RPOSweep` returns its members' own K as int32 [S] on the device."""
         eng = self.engine
-        return eng.m_img_prompt, eng.multi_text_features()
+        return eng.m_img_prompt, eng.multi_text_features(), None
+
+    @torch.no_grad()
+    def _sides_logits(self, image: torch.Tensor, sides) -> torch.Tensor:
+        """One frozen image pass for the batch, then the prompt rows of the sets `sides()` names: logits [S', B, n_cls]."""
+        eng = self.engine
+        with torch.cuda.device(self.device):
+            image = image.to(device=self.device, dtype=torch.float32).contiguous()
+            B = image.shape[0]
+            eng.prompt_rows_setup(self.n_runs, B)
+            img_prompts, text_f, k_used = sides()
+            eng.frozen_pass(image)
+            kv = eng.live_kv()
+            kv.set_first(0, B)
+            return eng.shared_eval_logits(B, kv, img_prompts, text_f, k_used=k_used).clone()
 
     @torch.no_grad()
     def model_inference_all(self, image: torch.Tensor) -> torch.Tensor:
         """logits [S, B, n_cls] of every member for one batch: ONE frozen image pass, then the S * B * K prompt rows of all
         members on its K / V (rpo_amd/engine_prompt_rows.py).  Member s's slice is what `model_inference(image, member=s)`
         computes, up to the summation order of the GEMM plans."""
-        eng, S = self.engine, self.n_runs
-        with torch.cuda.device(self.device):
-            image = image.to(device=self.device, dtype=torch.float32).contiguous()
-            B = image.shape[0]
-            eng.prompt_rows_setup(S, B)
-            img_prompts, text_f = self._shared_sides()
-            eng.frozen_pass(image)
-            kv = eng.live_kv()
-            kv.set_first(0, B)
-            return eng.shared_eval_logits(B, kv, img_prompts, text_f).clone()
+        return self._sides_logits(image, self._shared_sides)
 
     def test_all(self, image_set, batch_size: int = 100, frozen=None, verbose: bool = True, per_class_result: bool = False,
                  hook=None) -> List[dict]:

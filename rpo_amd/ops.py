@@ -540,9 +540,10 @@ def head_fwd_bwd(img_f, text_f, label, scale_exp: float, logits, loss, d_img_f, 
 
 
 def head_fwd_bwd_grouped(img_f, text_f, label, scale_exp: float, logits, loss, d_img_f, d_text_f, ws, S: int,
-                         d_img_f_act=None, d_text_f_act=None):
+                         d_img_f_act=None, d_text_f_act=None, k_used=None):
     """S independent heads in one call (rpo_head_fwd_bwd_grouped[_act]): img_f [S*B, K, e], text_f [S*C, K, e], label [S*B]
-    or None, logits [S*B, C], loss [S]; ws: S * head_workspace_floats(B, C, K, e) floats."""
+    or None, logits [S*B, C], loss [S]; ws: S * head_workspace_floats(B, C, K, e) floats.  k_used: int32 [S] on the device
+    -- group s pairs only its first k_used[s] of the K rows (rpo_head_fwd_bwd_grouped_k); None: the entry point without."""
     SB, K, e = img_f.shape
     assert SB % S == 0 and text_f.shape[0] % S == 0
     B, Cc = SB // S, text_f.shape[0] // S
@@ -552,6 +553,15 @@ def head_fwd_bwd_grouped(img_f, text_f, label, scale_exp: float, logits, loss, d
     assert ws.numel() >= S * head_workspace_floats(B, Cc, K, e)
     act = d_img_f_act if d_img_f_act is not None else d_text_f_act
     assert act is None or (act.is_contiguous() and (d_text_f_act is None or d_text_f_act.is_contiguous()))
+    if k_used is not None:
+        assert k_used.dtype == torch.int32 and k_used.is_cuda and k_used.numel() == S and k_used.is_contiguous()
+        check(_lib.load().rpo_head_fwd_bwd_grouped_k(img_f.data_ptr(), text_f.data_ptr(), _p(label), scale_exp,
+                                                     logits.data_ptr(), _p(loss), _p(d_img_f), _p(d_text_f),
+                                                     _p(d_img_f_act), _p(d_text_f_act),
+                                                     _lib.RPO_F32 if act is None else dtype_code(act.dtype),
+                                                     S, B, Cc, K, e, k_used.data_ptr(), ws.data_ptr(), _stream()),
+              "rpo_head_fwd_bwd_grouped_k")
+        return logits
     check(_lib.load().rpo_head_fwd_bwd_grouped_act(img_f.data_ptr(), text_f.data_ptr(), _p(label), scale_exp,
                                                    logits.data_ptr(), _p(loss), _p(d_img_f), _p(d_text_f),
                                                    _p(d_img_f_act), _p(d_text_f_act),
@@ -628,6 +638,21 @@ def sgd_step_guarded(p, g, buf, lr: float, momentum: float, wd: float, grad_scal
     check(_lib.load().rpo_sgd_step_guarded(p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), lr, momentum, wd,
                                            grad_scale, int(first_step), found_inf.data_ptr(), _stream()),
           "rpo_sgd_step_guarded")
+    return p
+
+
+def sgd_step_sets(p, g, buf, hyper, seg0: int, seg1: int, first_step: bool, used=None, found_inf=None):
+    """rpo_sgd_step_sets: p / g / buf [sets, >= seg0 + seg1] fp32 with one row stride; hyper float32 [sets, 4] (lr, momentum,
+    weight decay, grad_scale), used int32 [sets, 2] or None, found_inf int32 [sets, 2] or None -- all on the device."""
+    sets, stride = p.shape[0], p.stride(0)
+    for t in (p, g, buf):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == sets and t.stride() == (stride, 1)
+        assert t.shape[1] >= seg0 + seg1
+    assert hyper.dtype == torch.float32 and hyper.is_cuda and tuple(hyper.shape) == (sets, 4) and hyper.is_contiguous()
+    for t in (used, found_inf):
+        assert t is None or (t.dtype == torch.int32 and t.is_cuda and tuple(t.shape) == (sets, 2) and t.is_contiguous())
+    check(_lib.load().rpo_sgd_step_sets(p.data_ptr(), g.data_ptr(), buf.data_ptr(), stride, sets, hyper.data_ptr(), _p(used),
+                                        seg0, seg1, int(first_step), _p(found_inf), _stream()), "rpo_sgd_step_sets")
     return p
 
 

@@ -513,13 +513,13 @@ class RPO(LoopMixin):
         return self.model.eval_logits(image)
 
     def _shared_sides(self):
-        """(img_prompts [1, K, d_v], text_f) of the current prompts for the prompt-row pass."""
+        """(img_prompts [1, K, d_v], text_f, k_used = None) of the current prompts for the prompt-row pass."""
         eng, pl = self.engine, self.model.prompt_learner
         ver = (pl.text_prompt._version, pl.img_prompt._version)       # (edits through the nn.Parameter views: eval_logits)
         if ver != getattr(self.model, "_seen_version", None):
             eng.params_version += 1
             self.model._seen_version = ver
-        return eng.img_prompt.unsqueeze(0), eng.eval_text_features()
+        return eng.img_prompt.unsqueeze(0), eng.eval_text_features(), None
 
     def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, frozen=None,
              hook=None):
