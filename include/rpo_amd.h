@@ -451,6 +451,22 @@ int rpo_lp_head_fwd_bwd(const float* img_f, const float* w, const float* bias, c
                         const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
                         float* g_w, float* g_bias, int B, int C, int e, float* workspace, void* stream);
 
+/* (ABI 8 addition) Prompt ensembling (trainers/zsclip.py:85-96, ZeroshotCLIP2): the classifier is the normalised mean over
+ * the templates of the normalised text features.  rpo_amd/csrc/ensemble.hip.
+ *   accumulate: acc[c,:] = (first ? 0 : acc[c,:]) + sum_t feat[t,c,:] / ||feat[t,c,:]||_2     t = 0 .. T-1, ascending
+ *   finish:     out[c,:] = m / ||m||_2,  m = acc[c,:] / T_total
+ * feat: T blocks of n_cls rows, row t * template_stride_rows + c with e valid floats and leading dimension ld >= e
+ * (template_stride_rows >= n_cls where T > 1); acc, out [n_cls, e] contiguous; out may alias acc; all fp32 device memory.
+ * One wave owns a class row, the sum over t is sequential in fp32, no atomics: the bits repeat, and one call over T
+ * templates gives the bits of a call over the first T1 (first = 1) followed by one over the rest (first = 0) -- provided
+ * both take the same element map: 16-byte loads where e % 4 == 0, ld % 4 == 0 and feat / acc (finish: acc / out) are
+ * 16-byte aligned, single floats otherwise.  1 <= e <= 1024, any n_cls >= 1, T >= 1, T_total >= 1; a null pointer, a size
+ * out of range, ld < e or overlapping blocks: RPO_E_BADARG with nothing launched.  A zero row gives NaN, as the reference
+ * does.  One launch each on `stream`, no allocation, capturable in a HIP graph. */
+int rpo_text_ensemble_accumulate(const float* feat, int64_t ld, int T, int64_t template_stride_rows, int n_cls, int e,
+                                 float* acc, int first, void* stream);
+int rpo_text_ensemble_finish(const float* acc, int n_cls, int e, int T_total, float* out, void* stream);
+
 /* Classification evaluator (Dassl's `Classification.process`, and `compute_accuracy` of the CoOp / LP steps), accumulating
  * on the device: pred[b] = logits[b].max()'s index as torch computes it on the CPU for fp32 -- the FIRST index of the row
  * maximum, a row holding NaN predicts its first NaN, ties (+inf included, all -inf too) take the lowest index.

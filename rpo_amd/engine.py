@@ -36,6 +36,7 @@ from .engine_lp import LpEngineMixin
 from .engine_multi import MultiEngineMixin
 from .engine_prompt_rows import PromptRowsEngineMixin
 from .engine_rn import RnEngineMixin
+from .engine_text import TextEncodeEngineMixin
 
 import contextlib
 
@@ -71,7 +72,7 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin):
+class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under
@@ -134,6 +135,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         self._stats_group = {}          # batch size -> columns per partial LayerNorm statistic (64 or 96)
         self.img_cls_f = self.rn_img_f if cfg.is_rn else None     # (the ResNet tower writes its features there)
         self.plain_text_f = None
+        self.plain_text_override = None  # caller-given classifier of forward_plain (set_plain_text_features)
         self.text_x_final = None
         self._eval_graphs = {}          # batch size -> (captured image tower + head, its static input)
         self.probe = None               # optional callable(name) -> context manager bracketing one launch (bench.py)
@@ -281,6 +283,8 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         # the token embeddings alone (CoOp's "middle" / "front" class-token positions re-order them before the positional
         # embedding is added, trainers/coop.py:136-183)
         self.text_tok = self._f32(sd["token_embedding.weight"][tokens][:, :self.Lmax].reshape(cfg.n_cls * self.Lmax, cfg.d_t))
+        # encode_text embeds prompts the engine was not built with: the host table by reference (not a copy)
+        self._tok_emb_host, self._pos_host = sd["token_embedding.weight"], sd["positional_embedding"]
 
     def _pack_vit_embed(self, sd) -> None:
         """The ViT's patch embedding, class / positional embeddings, ln_pre / ln_post and visual.proj."""
@@ -391,25 +395,8 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         """Frozen text tokens (positions < len_c) of every class through all blocks with the
         causal AND col<len_c mask (trainers/rpo.py:146-149); keeps each layer's K and V.
         Independent of prompts and images, so it runs once per class set."""
-        cfg, act = self.cfg, self.act
-        n, L, dt, H = cfg.n_cls, self.Lmax, cfg.d_t, cfg.heads_t
-        Rf = n * L
         x = self.text_x_frozen.clone()
-        xm = torch.empty_like(x)
-        h = torch.empty(Rf, dt, dtype=act, device=self.dev)
-        qkv = torch.empty(Rf, 3 * dt, dtype=act, device=self.dev)
-        att = torch.empty(Rf, dt, dtype=act, device=self.dev)
-        g = torch.empty(Rf, 4 * dt, dtype=act, device=self.dev)
-        for l, blk in enumerate(self.txt):
-            ops.layernorm_fwd(x, blk.ln1_w, blk.ln1_b, h)
-            ops.gemm_nt(h, blk.w_in, qkv, EPI_BIAS, bias=blk.b_in)
-            ops.text_attn_fwd(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], att, self.len_i32, n, L, L, H,
-                              causal=True, scale=SCALE)
-            self.kv_t[l].copy_(qkv[:, dt:])
-            ops.gemm_nt(att, blk.w_out, xm, EPI_BIAS_RESID, bias=blk.b_out, resid=x)
-            ops.layernorm_fwd(xm, blk.ln2_w, blk.ln2_b, h)
-            ops.gemm_nt(h, blk.w_fc, g, EPI_BIAS_QGELU, bias=blk.b_fc, aux=None, aux_row0=Rf)
-            ops.gemm_nt(g, blk.w_proj, x, EPI_BIAS_RESID, bias=blk.b_proj, resid=xm)
+        self._text_blocks_plain(x, self.len_i32, self.cfg.n_cls, self.Lmax, self.kv_t)
         self.text_x_final = x                       # output of the last block for the frozen tokens (forward_plain)
         self.plain_text_f = None
         self.text_cache_ready = True
@@ -917,12 +904,9 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         if not self.text_cache_ready:
             self.cache_text_kv()
         if self.plain_text_f is None:
-            rows = torch.arange(n, device=self.dev) * self.Lmax + (self.len_i32.to(torch.int64) - 1)   # EOT positions
-            eot = self.text_x_final.index_select(0, rows).contiguous()
-            y = torch.empty(n, cfg.d_t, dtype=self.act, device=self.dev)
-            ops.layernorm_fwd(eot, self.ln_final[0], self.ln_final[1], y)
-            self.plain_text_f = torch.empty(n, e, dtype=torch.float32, device=self.dev)
-            ops.gemm_nt(y, self.text_proj_t, self.plain_text_f, EPI_NONE)
+            self.plain_text_f = self._text_eot_features(self.text_x_final, self.len_i32, n, self.Lmax,
+                                                        torch.empty(n, e, dtype=torch.float32, device=self.dev))
+        text_f = self.plain_text_f if self.plain_text_override is None else self.plain_text_override
         if cfg.is_rn:
             self.rn_forward(image)                                             # -> img_cls_f[:B] (engine_rn.py)
         else:
@@ -932,7 +916,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
             if self.img_cls_f is None:
                 self.img_cls_f = torch.empty(self.max_batch, e, dtype=torch.float32, device=self.dev)
             ops.gemm_nt(self.y_post[:B], self.img_proj_t, self.img_cls_f[:B], EPI_NONE)
-        ops.head_fwd_bwd(self.img_cls_f[:B].view(B, 1, e), self.plain_text_f.view(n, 1, e), None, self.logit_scale_exp,
+        ops.head_fwd_bwd(self.img_cls_f[:B].view(B, 1, e), text_f.view(n, 1, e), None, self.logit_scale_exp,
                          self.logits[:B], None, None, None, self.head_ws)
         return self.logits[:B]
 

@@ -1,0 +1,106 @@
+"""The plain text tower of the engine for prompts it was NOT built with (rpo_amd/engine.py mixes this in): the block loop
+`cache_text_kv` runs, the EOT feature tail `forward_plain` runs, `encode_text` on top of the two (any [P, 77] token ids,
+chunked), and the caller-given classifier of `forward_plain`.  Prompt ensembling (rpo_amd.zeroshot.ZeroshotCLIP2,
+DESIGN.md 9j) is built on it."""
+from __future__ import annotations
+
+import math
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_NONE
+
+SCALE = 1.0 / math.sqrt(64.0)
+
+
+class TextEncodeEngineMixin:
+    def _text_blocks_plain(self, x: torch.Tensor, len_i32: torch.Tensor, n: int, L: int,
+                           kv: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+        """The text blocks over the first L positions of n prompts, x [n * L, d_t] fp32 updated in place to the last
+        block's output, under the causal AND col < len mask.  kv: per layer [n * L, 2 d_t], receives that layer's K | V."""
+        cfg, act = self.cfg, self.act
+        dt, H = cfg.d_t, cfg.heads_t
+        Rf = n * L
+        xm = torch.empty_like(x)
+        h = torch.empty(Rf, dt, dtype=act, device=self.dev)
+        qkv = torch.empty(Rf, 3 * dt, dtype=act, device=self.dev)
+        att = torch.empty(Rf, dt, dtype=act, device=self.dev)
+        g = torch.empty(Rf, 4 * dt, dtype=act, device=self.dev)
+        for l, blk in enumerate(self.txt):
+            ops.layernorm_fwd(x, blk.ln1_w, blk.ln1_b, h)
+            ops.gemm_nt(h, blk.w_in, qkv, EPI_BIAS, bias=blk.b_in)
+            ops.text_attn_fwd(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], att, len_i32, n, L, L, H,
+                              causal=True, scale=SCALE)
+            if kv is not None:
+                kv[l].copy_(qkv[:, dt:])
+            ops.gemm_nt(att, blk.w_out, xm, EPI_BIAS_RESID, bias=blk.b_out, resid=x)
+            ops.layernorm_fwd(xm, blk.ln2_w, blk.ln2_b, h)
+            ops.gemm_nt(h, blk.w_fc, g, EPI_BIAS_QGELU, bias=blk.b_fc, aux=None, aux_row0=Rf)
+            ops.gemm_nt(g, blk.w_proj, x, EPI_BIAS_RESID, bias=blk.b_proj, resid=xm)
+        return x
+
+    def _text_eot_features(self, x: torch.Tensor, len_i32: torch.Tensor, n: int, L: int, out: torch.Tensor) -> torch.Tensor:
+        """out [n, e] fp32 = text_projection of ln_final of every prompt's EOT row of x [n * L, d_t] (clip/model.py:352-354)."""
+        rows = torch.arange(n, device=self.dev) * L + (len_i32.to(torch.int64) - 1)            # EOT positions
+        eot = x.index_select(0, rows).contiguous()
+        y = torch.empty(n, self.cfg.d_t, dtype=self.act, device=self.dev)
+        ops.layernorm_fwd(eot, self.ln_final[0], self.ln_final[1], y)
+        return ops.gemm_nt(y, self.text_proj_t, out, EPI_NONE)
+
+    # prompts per pass of encode_text: bounds its workspace to TEXT_CHUNK * 77 rows of [fp32 x 2 | act x 9] d_t-wide
+    # buffers -- 0.26 GB in the 16-bit modes and 0.44 GB in f32 at d_t = 512 if every prompt filled the context; a chunk
+    # allocates for its own longest prompt (class-name prompts: 10-20 tokens, a quarter of that).  Measured at 7 000 and
+    # 80 000 prompts of 8-20 tokens (profiles/ensemble_bench.json): 256 per pass is faster than 1024 or 4096 (50 / 159 /
+    # 147 ms at 7 000), so the smaller bound costs nothing
+    TEXT_CHUNK = 256
+
+    @torch.no_grad()
+    def encode_text(self, tokens: np.ndarray, chunk: Optional[int] = None) -> torch.Tensor:
+        """Plain `CLIP.encode_text` (clip/model.py:344-356) of ANY prompts: tokens int64 [P, 77] -> [P, e] fp32 on the
+        device, un-normalised as the reference's.  P has nothing to do with cfg.n_cls, and the engine may hold any model
+        (RPO / CoOp / LP): nothing of its own text state is read or written (K / V cache, frozen-token rows, cached
+        features, prompts versions).  A learned CoOp context (`set_context`) is not applied.
+        `chunk` prompts run per pass (default TEXT_CHUNK = 256, which bounds the workspace by the chunk instead of P:
+        see the note at TEXT_CHUNK); each pass runs the positions up to ITS longest prompt -- what follows a prompt's
+        EOT cannot reach the EOT row under the causal mask -- through the block sequence of `cache_text_kv`, keeps no
+        K / V, and ends in ln_final + text_projection of the EOT rows as `forward_plain` does.  The token embeddings of
+        a chunk are gathered on the host from the state dict's table (held by reference, never copied) and uploaded."""
+        cfg = self.cfg
+        tokens = np.asarray(tokens)
+        assert tokens.ndim == 2 and tokens.shape[1] == cfg.context and tokens.shape[0] >= 1, \
+            f"tokens: [P, {cfg.context}] prompt ids"
+        assert np.issubdtype(tokens.dtype, np.integer), "tokens: integer prompt ids"
+        tokens = tokens.astype(np.int64, copy=False)
+        assert int(tokens.min()) >= 0 and int(tokens.max()) < self._tok_emb_host.shape[0], "token id outside the vocabulary"
+        P = tokens.shape[0]
+        chunk = self.TEXT_CHUNK if chunk is None else int(chunk)
+        assert chunk >= 1, "chunk: prompts per pass, >= 1"
+        lens = tokens.argmax(-1) + 1                                   # EOT has the highest id (clip/model.py:354)
+        # host tensors over the state dict's own memory (no copy of the table): torch's embedding gathers a pass's rows on
+        # the host's threads, numpy's fancy index on one (7 000 prompts: 68 -> 50 ms)
+        table, pos = torch.as_tensor(np.asarray(self._tok_emb_host)), torch.as_tensor(np.asarray(self._pos_host))
+        ids = torch.from_numpy(np.ascontiguousarray(tokens))
+        with torch.cuda.device(self.dev):
+            out = torch.empty(P, cfg.embed, dtype=torch.float32, device=self.dev)
+            for p0 in range(0, P, chunk):
+                p1 = min(P, p0 + chunk)
+                n, L = p1 - p0, int(lens[p0:p1].max())
+                emb = torch.nn.functional.embedding(ids[p0:p1, :L], table) + pos[None, :L]
+                x = emb.reshape(n * L, cfg.d_t).to(device=self.dev, dtype=torch.float32)
+                len_i32 = torch.tensor(lens[p0:p1], dtype=torch.int32, device=self.dev)
+                self._text_blocks_plain(x, len_i32, n, L)
+                self._text_eot_features(x, len_i32, n, L, out[p0:p1])
+        return out
+
+    def set_plain_text_features(self, features: Optional[torch.Tensor]) -> None:
+        """The classifier of `forward_plain` becomes `features` [n_cls, e] (the head normalises them) instead of the
+        engine's own prompts' text features, until None is passed; `cache_text_kv` leaves the override alone."""
+        if features is None:
+            self.plain_text_override = None
+            return
+        f = torch.as_tensor(features, dtype=torch.float32, device=self.dev)
+        assert tuple(f.shape) == (self.cfg.n_cls, self.cfg.embed), f"features: [{self.cfg.n_cls}, {self.cfg.embed}]"
+        self.plain_text_override = f.contiguous().clone()

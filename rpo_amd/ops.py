@@ -591,6 +591,32 @@ def lp_head_fwd_bwd(img_f, w, bias, text_f_n, label, scale_exp: float, z, logits
     return logits
 
 
+def text_ensemble_accumulate(feat, n_cls: int, acc, first: bool = True, template_stride_rows: Optional[int] = None):
+    """Prompt ensembling, first half (include/rpo_amd.h rpo_text_ensemble_accumulate): feat [rows, e] fp32 (row stride >= e)
+    holds T blocks of n_cls rows, block t at row t * template_stride_rows (default n_cls: T = rows / n_cls); adds every
+    block's L2-normalised rows to acc [n_cls, e] in ascending t (first: acc starts from zero).  Enqueue only."""
+    stride = n_cls if template_stride_rows is None else int(template_stride_rows)
+    assert feat.dim() == 2 and feat.dtype == torch.float32 and feat.stride(1) == 1 and n_cls >= 1 and stride >= n_cls
+    e = feat.shape[1]
+    T = (feat.shape[0] - n_cls) // stride + 1
+    assert T >= 1 and (T - 1) * stride + n_cls <= feat.shape[0], "feat holds no whole block of n_cls rows"
+    assert acc.dtype == torch.float32 and acc.shape == (n_cls, e) and acc.is_contiguous() and acc.device == feat.device
+    check(_lib.load().rpo_text_ensemble_accumulate(feat.data_ptr(), feat.stride(0), T, stride, n_cls, e, acc.data_ptr(),
+                                                   1 if first else 0, _stream()), "rpo_text_ensemble_accumulate")
+    return acc
+
+
+def text_ensemble_finish(acc, T_total: int, out=None):
+    """Prompt ensembling, second half (rpo_text_ensemble_finish): out = normalise(acc / T_total); out None: in place."""
+    out = acc if out is None else out
+    n_cls, e = acc.shape
+    assert acc.dtype == torch.float32 and acc.is_contiguous()
+    assert out.dtype == torch.float32 and out.shape == acc.shape and out.is_contiguous() and out.device == acc.device
+    check(_lib.load().rpo_text_ensemble_finish(acc.data_ptr(), n_cls, e, int(T_total), out.data_ptr(), _stream()),
+          "rpo_text_ensemble_finish")
+    return out
+
+
 def eval_accumulate(logits, label, counts, cmat=None, pred=None):
     """The classification evaluator's device half (include/rpo_amd.h rpo_eval_accumulate): counts int64 [2] (correct, total)
     and cmat int32 [C, C] (row = true class) accumulate; pred int32 [B] is overwritten.  Enqueue only."""

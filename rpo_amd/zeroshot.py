@@ -17,7 +17,7 @@ from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .engine import Engine, make_engine
 from .loop import EvalMixin
-from . import synth
+from . import ops, synth
 
 
 class ZeroshotCLIP(EvalMixin):
@@ -40,10 +40,25 @@ class ZeroshotCLIP(EvalMixin):
 
     def set_context(self, ctx) -> None:
         """Evaluate CoOp-style learned context vectors (trainers/coop.py:117-134: generic context [n_ctx, d_t], class
-        token at the end): `tokens` must then be the ids of the reference's "X X .. name." prompts."""
+        token at the end): `tokens` must then be the ids of the reference's "X X .. name." prompts.  Clears a classifier
+        given through `set_text_features`."""
         with torch.cuda.device(self.engine.dev):
+            self.engine.set_plain_text_features(None)
             self.engine.set_context(ctx)
             self.engine.cache_text_kv()
+
+    @torch.no_grad()
+    def encode_text(self, tokens: np.ndarray, chunk: Optional[int] = None) -> torch.Tensor:
+        """`CLIP.encode_text` of any prompts: tokens int64 [P, 77] -> [P, e] fp32 on the device, un-normalised
+        (Engine.encode_text; P is independent of n_cls, the model's own text features are untouched)."""
+        return self.engine.encode_text(tokens, chunk)
+
+    def set_text_features(self, features) -> None:
+        """The classifier of `model_inference` / `test` becomes `features` [n_cls, e] (normalised or not: the head
+        normalises) instead of the text features of the prompts the model was built with.  It stays through later
+        `cache_text_kv` calls; `set_text_features(None)` or `set_context` drops it."""
+        with torch.cuda.device(self.engine.dev):
+            self.engine.set_plain_text_features(features)
 
     @torch.no_grad()
     def model_inference(self, image: torch.Tensor) -> torch.Tensor:
@@ -58,3 +73,34 @@ class ZeroshotCLIP(EvalMixin):
     def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
         """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
         return self.engine.forward_plain(image)
+
+
+class ZeroshotCLIP2(ZeroshotCLIP):
+    """Prompt ensembling (trainers/zsclip.py:63-99): the class names under T templates; the classifier is the normalised
+    mean over the templates of each template's normalised text features.  The caller tokenises (template strings are
+    the caller's: the reference takes 7 of `IMAGENET_TEMPLATES_SELECT` plus the dataset's own)."""
+    def __init__(self, state_dict: Dict[str, np.ndarray], tokens: np.ndarray, device: str | torch.device = "cuda:0",
+                 act_dtype: torch.dtype = torch.float16, max_batch: int = 100, cfg: Optional[RPOConfig] = None,
+                 chunk: Optional[int] = None):
+        """tokens: int64 [T, n_cls, 77], template-major, in the order the reference sums them (zsclip.py:89-94); the
+        engine is built on tokens[0].  chunk: prompts per text pass (Engine.encode_text)."""
+        tokens = np.asarray(tokens)
+        if tokens.ndim != 3:
+            raise ValueError(f"ZeroshotCLIP2: tokens must be [T, n_cls, 77] (one block of class prompts per template), "
+                             f"got {tokens.ndim} dimension(s)")
+        if tokens.shape[2] != 77 or tokens.shape[0] < 1 or tokens.shape[1] < 1:
+            raise ValueError(f"ZeroshotCLIP2: tokens must be [T, n_cls, 77] with CLIP's context of 77 ids, "
+                             f"got {tuple(tokens.shape)}")
+        tokens = tokens.astype(np.int64, copy=False)
+        super().__init__(state_dict, tokens[0], device, act_dtype, max_batch, cfg)
+        T, n, _ = tokens.shape
+        self.n_templates = T
+        with torch.cuda.device(self.engine.dev):
+            feats = self.engine.encode_text(tokens.reshape(T * n, 77), chunk)         # [T * n, e], stays on the device
+            acc = torch.empty(n, self.cfg.embed, dtype=torch.float32, device=self.device)
+            ops.text_ensemble_accumulate(feats, n, acc, first=True)                   # sum_t f_t / |f_t|, ascending t
+            self.text_features = ops.text_ensemble_finish(acc, T)                      # normalise(mean)
+            self.set_text_features(self.text_features)
+
+    def set_context(self, ctx) -> None:
+        raise NotImplementedError("ZeroshotCLIP2.set_context: a learned context belongs to one template, the ensemble has T")
