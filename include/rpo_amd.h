@@ -535,6 +535,44 @@ int rpo_sgd_step_guarded(float* p, const float* g, float* buf, int64_t n, float 
 int rpo_sgd_step_sets(float* p, const float* g, float* buf, int64_t set_stride, int sets, const float* hyper,
                       const int32_t* used, int64_t seg0, int64_t seg1, int first_step, int32_t* found_inf, void* stream);
 
+/* (ABI 8 addition) Dassl's optimisers beyond plain SGD (`build_optimizer(..., cfg.OPTIM)`, trainers/rpo.py:274, and the
+ * step at :298-309; the same pair of calls in coop.py, cocoop.py, linear_prob.py): rpo_sgd_step_sets generalised to
+ * torch.optim's SGD (dampening, Nesterov), Adam, AdamW, Adam with amsgrad and RMSprop (not centered) -- single-tensor
+ * rules, maximize = False.  Set s is row s of p / g and of the fp32 state rows s0 / s1 / s2 (rows set_stride floats apart);
+ * the segments [0, seg0) and [seg0, seg0 + seg1) are stepped; `used` and `found_inf` mean what they mean there.
+ *   s0  SGD, RMSprop: momentum_buffer;  Adam kinds: exp_avg          (must start at zero)
+ *   s1  RMSprop: square_avg;            Adam kinds: exp_avg_sq       (must start at zero; SGD does not touch it)
+ *   s2  AMSGRAD: max_exp_avg_sq (must start at zero); no other kind touches it
+ * All tables are on the DEVICE, so a captured graph of the step stays valid across epochs, across a resume and from the
+ * very first step:
+ *   kind   int32 [sets]: RPO_OPT_*.  A value outside the enum cannot be seen by the host: such a set is IGNORED on the
+ *          device (nothing of it is scanned, read or written, its counter stays), and so is a set with a negative counter
+ *          and an AMSGRAD set when s2 is NULL.
+ *   hyper  float [sets, 8]:
+ *            0 lr             1 grad_scale (1 / world_size after a sum all-reduce)         2 weight decay
+ *            3 SGD, RMSprop: momentum;  Adam kinds: beta1
+ *            4 SGD: dampening;  Adam kinds: beta2;  RMSprop: alpha                         5 eps (unused by SGD)
+ *            6 SGD: the Nesterov flag (non-zero = on);  Adam kinds: beta1 - (float)beta1, the low-order part of column 3
+ *            7 the low-order part of column 4: x - (float)x for x = dampening | beta2 | alpha
+ *          torch forms 1 - beta, 1 - beta^t, lr / (1 - beta1^t) and sqrt(1 - beta2^t) in doubles from the Python floats; the
+ *          kernel forms them in double from (column 3 + column 6) and (column 4 + column 7), once per workgroup, and rounds
+ *          each to fp32 once.  Zero low-order parts are valid (the betas are then their fp32 roundings).
+ *   step   int32 [sets]: the number of updates the set has APPLIED.  Read by the kernel (0 = the first step: SGD's
+ *          buf = g'; t = step + 1 feeds the bias corrections) and advanced by one per call unless the set's step is skipped
+ *          or the set is ignored.  It replaces the first_step argument of rpo_sgd_step*.  No workgroup reads a counter
+ *          that a workgroup of the same launch writes: the guarded form has one workgroup per set, the elementwise form
+ *          only reads and a one-thread-per-set launch behind it, inside this call, advances.
+ * found_inf NULL: elementwise.  Else one 1024-thread workgroup per set: when a used gradient element of the set is Inf or
+ * NaN, nothing of the set changes (p, the state rows, step[s]) and found_inf[s] = [1, += 1] (GradScaler.step does not
+ * call optimizer.step(): Adam's count does not advance).  Kind SGD with dampening 0 and Nesterov off gives, per element,
+ * the bits of rpo_sgd_step_sets.  s0, s1 are always required; s2 must be non-NULL when needs_s2 != 0 (the caller knows
+ * whether one of its sets is AMSGRAD), else RPO_E_BADARG.  set_stride >= seg0 + seg1, sets <= 65535,
+ * seg0 + seg1 <= (2^31 - 1) * 256, else RPO_E_SHAPE. */
+enum { RPO_OPT_SGD = 0, RPO_OPT_ADAM = 1, RPO_OPT_ADAMW = 2, RPO_OPT_AMSGRAD = 3, RPO_OPT_RMSPROP = 4 };
+int rpo_optim_step_sets(float* p, const float* g, float* s0, float* s1, float* s2, int64_t set_stride, int sets,
+                        const int32_t* kind, const float* hyper, int32_t* step, const int32_t* used, int64_t seg0,
+                        int64_t seg1, int needs_s2, int32_t* found_inf, void* stream);
+
 /* fp32 -> act dtype copy with leading dimensions (weight packing at load time) */
 int rpo_convert(const float* src, int64_t lds, void* dst, int dst_dtype, int64_t ldd,
                 int rows, int cols, void* stream);

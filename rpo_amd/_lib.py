@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "librpo_hip.so")
 
 RPO_F32, RPO_BF16, RPO_F16 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_QGELU_BWD, EPI_PATCH, EPI_LN_BIAS, EPI_LN_BIAS_QGELU = range(8)
+OPT_SGD, OPT_ADAM, OPT_ADAMW, OPT_AMSGRAD, OPT_RMSPROP = range(5)                          # include/rpo_amd.h RPO_OPT_*
 E_BADARG, E_SHAPE, E_DTYPE, E_ALIGN, E_WORKSPACE = -1, -2, -3, -4, -5      # include/rpo_amd.h RPO_E_*
 (E_JPEG_CORRUPT, E_JPEG_PROGRESSIVE, E_JPEG_ARITHMETIC, E_JPEG_LOSSLESS, E_JPEG_PRECISION, E_JPEG_COMPONENTS, E_JPEG_RGB,
  E_JPEG_SAMPLING, E_JPEG_MULTISCAN, E_JPEG_SCRIPT, E_JPEG_SEQUENTIAL) = range(-20, -31, -1)
@@ -187,6 +188,8 @@ SIGNATURES = {
     "rpo_sgd_step": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "rpo_sgd_step_guarded": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp]),
     "rpo_sgd_step_sets": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "rpo_optim_step_sets": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32,
+                                    c_vp, c_vp]),
     "rpo_convert": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),
     "rpo_probe_mfma": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rpo_probe_peak_mfma": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),

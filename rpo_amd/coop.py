@@ -30,7 +30,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, optim as _optim
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .engine import Engine, make_engine
@@ -124,6 +124,7 @@ class CoOp(LoopMixin):
     un-vendored, hence explicit: OptimConfig)."""
 
     _reports_acc = True              # forward_backward reports "acc": run_epoch sums it on the device
+    _opt = None                      # optim.OptimState: every optimiser but plain SGD
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int = 16,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",
@@ -150,6 +151,16 @@ class CoOp(LoopMixin):
         self.amp = amp
         self._found_inf = torch.zeros(2, dtype=torch.int32, device=self.device) if amp else None
         self.best_result = -float("inf")
+        # every optimiser but plain SGD: the table-driven kernel on the flat buffer as one set
+        _optim.validate(self.optim_cfg)
+        self._opt = None
+        if not _optim.is_plain_sgd(self.optim_cfg):
+            n = self.engine.coop_params.numel()
+            with torch.cuda.device(self.device):
+                self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.coop_moms)
+
+    def _param_shapes(self):
+        return [tuple(t.shape) for _, t in self.model.prompt_learner.named_parameters()]
 
     def _forward_backward(self, image: torch.Tensor, label: torch.Tensor) -> None:
         self.engine.coop_forward_backward(image, label)
@@ -157,7 +168,9 @@ class CoOp(LoopMixin):
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
         eng, oc = self.engine, self.optim_cfg
         self._forward_backward(image, label)
-        if self.amp:
+        if self._opt is not None:
+            self._opt.step(eng.coop_params, eng.coop_grads, self._found_inf)
+        elif self.amp:
             ops.sgd_step_guarded(eng.coop_params, eng.coop_grads, eng.coop_moms, self.lr, oc.momentum, oc.weight_decay,
                                  1.0, first_step=(self._steps == 0), found_inf=self._found_inf)
         else:
@@ -189,6 +202,8 @@ class CoOp(LoopMixin):
                  "params": list(range(len(names)))}
         ck = {"state_dict": pl.state_dict(), "epoch": int(epoch), "optimizer": {"state": state, "param_groups": [group]},
               "scheduler": {"last_epoch": int(epoch)}, "val_result": val_result, "steps": int(self._steps)}
+        if self._opt is not None:                                # torch's own layout for the kind
+            ck["optimizer"] = self._opt.state_dict(self._param_shapes(), lr=self.lr)
         return write_checkpoint(directory, ck, epoch, is_best)
 
     def load_model(self, directory: str, epoch: Optional[int] = None) -> Optional[dict]:
@@ -229,7 +244,13 @@ class CoOp(LoopMixin):
             raise ValueError("resume_model needs a checkpoint directory (load_model skipped: nothing was loaded)")
         params = list(self.model.prompt_learner.named_parameters())
         st = (ck.get("optimizer") or {}).get("state") or {}
-        if st:
+        if self._opt is not None:
+            if st and not self._opt.load_state_dict(ck.get("optimizer"), self._param_shapes(), steps=ck.get("steps", 1)):
+                raise ValueError(f"the checkpoint's optimiser state is not {self.optim_cfg.name}'s for these tensors: it was "
+                                 "written with another optimiser or other context settings")
+            if st:
+                self._steps = max(1, int(ck.get("steps", 1)))
+        elif st:
             bufs = [st[i]["momentum_buffer"] for i in range(len(params))]
             flat = torch.cat([torch.as_tensor(b).reshape(-1).float() for b in bufs])
             if flat.numel() != self.engine.coop_moms.numel():
@@ -246,10 +267,14 @@ class CoOp(LoopMixin):
         """One optimisation step, nothing synchronised; returns the device loss scalar.  With use_graph the ~250 launches
         of a step (plain image tower, dense text tower forward + backward, head, SGD) are replayed from ONE HIP graph,
         captured after the first (eager) step and again whenever the learning rate changes (it is a kernel argument)."""
+        key = self.lr
+        if self._opt is not None:                       # the rate is device data: one capture serves every epoch
+            self._opt.set_epoch(self.epoch)
+            key = None
         if not self.use_graph or self._steps == 0 or image.shape[0] != self.batch_size:
             self._enqueue(image, label)
         else:
-            if self._graph is None or self._graph[1] != self.lr:
+            if self._graph is None or self._graph[1] != key:
                 self._img = torch.empty_like(image)
                 self._lab = torch.empty_like(label)
                 self._img.copy_(image); self._lab.copy_(label)
@@ -257,7 +282,7 @@ class CoOp(LoopMixin):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._enqueue(self._img, self._lab)
-                self._graph = (g, self.lr)
+                self._graph = (g, key)
                 # (capture does not execute: the replay below is this step)
             if image.data_ptr() != self._img.data_ptr():
                 self._img.copy_(image, non_blocking=True)

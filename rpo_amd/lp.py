@@ -21,7 +21,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, optim as _optim
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .dist import GradSync
@@ -108,6 +108,7 @@ class LP(LoopMixin):
     (GradSync), grad_scale 1 / world_size in the SGD step."""
 
     _reports_acc = True              # forward_backward reports "acc": run_epoch sums it on the device
+    _opt = None                      # optim.OptimState: every optimiser but plain SGD
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, optim: Optional[OptimConfig] = None,
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float32, batch_size: int = 32,
@@ -136,6 +137,14 @@ class LP(LoopMixin):
         self.amp = amp
         self._found_inf = torch.zeros(2, dtype=torch.int32, device=self.device) if amp else None
         self.best_result = -float("inf")
+        # every optimiser but plain SGD: the table-driven kernel on the flat [W | b] buffer as one set
+        _optim.validate(self.optim_cfg)
+        self._opt = None
+        if not _optim.is_plain_sgd(self.optim_cfg):
+            n = self.engine.lp_params.numel()
+            with torch.cuda.device(self.device):
+                self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.lp_moms,
+                                              grad_scale=self.sync.grad_scale)
         if self.sync.enabled:                            # identical layer on every rank
             with torch.cuda.device(self.device):
                 self.sync.broadcast(self.engine.lp_params)
@@ -146,7 +155,9 @@ class LP(LoopMixin):
         if self.sync.enabled:
             self.sync.all_reduce_sum(eng.lp_grads)
         gs = self.sync.grad_scale
-        if self.amp:
+        if self._opt is not None:
+            self._opt.step(eng.lp_params, eng.lp_grads, self._found_inf)
+        elif self.amp:
             ops.sgd_step_guarded(eng.lp_params, eng.lp_grads, eng.lp_moms, self.lr, oc.momentum, oc.weight_decay, gs,
                                  first_step=(self._steps == 0), found_inf=self._found_inf)
         else:
@@ -162,10 +173,14 @@ class LP(LoopMixin):
         """One optimisation step, nothing synchronised; returns the device loss scalar.  With use_graph the whole step
         (plain image tower, LP head, SGD) is replayed from ONE HIP graph, captured after the first (eager) step and again
         whenever the learning rate changes (it is a kernel argument)."""
+        key = self.lr
+        if self._opt is not None:                       # the rate is device data: one capture serves every epoch
+            self._opt.set_epoch(self.epoch)
+            key = None
         if not self.use_graph or self._steps == 0 or image.shape[0] != self.batch_size:
             self._enqueue(image, label)
         else:
-            if self._graph is None or self._graph[1] != self.lr:
+            if self._graph is None or self._graph[1] != key:
                 self._img = torch.empty_like(image)
                 self._lab = torch.empty_like(label)
                 self._img.copy_(image); self._lab.copy_(label)
@@ -173,7 +188,7 @@ class LP(LoopMixin):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._enqueue(self._img, self._lab)
-                self._graph = (g, self.lr)
+                self._graph = (g, key)
                 # (capture does not execute: the replay below is this step)
             if image.data_ptr() != self._img.data_ptr():
                 self._img.copy_(image, non_blocking=True)
@@ -228,8 +243,11 @@ class LP(LoopMixin):
         group = {"lr": self.lr, "momentum": oc.momentum, "dampening": 0, "weight_decay": oc.weight_decay, "nesterov": False,
                  "maximize": False, "foreach": None, "differentiable": False, "fused": None, "initial_lr": oc.lr,
                  "params": list(range(len(params)))}
+        optimizer = {"state": state, "param_groups": [group]}
+        if self._opt is not None:                                # torch's own layout for the kind
+            optimizer = self._opt.state_dict([tuple(t.shape) for _, t in params], lr=self.lr)
         return {"state_dict": self.model.state_dict(), "epoch": int(epoch),
-                "optimizer": {"state": state, "param_groups": [group]}, "scheduler": {"last_epoch": int(epoch)},
+                "optimizer": optimizer, "scheduler": {"last_epoch": int(epoch)},
                 "val_result": val_result, "steps": int(self._steps)}
 
     def save_model(self, directory: str, epoch: Optional[int] = None, is_best: bool = False,
@@ -278,7 +296,13 @@ class LP(LoopMixin):
         if any(n not in sd for n, _ in params):
             raise ValueError("checkpoint lacks lp_layer's weight / bias: it was written by another trainer")
         st = (ck.get("optimizer") or {}).get("state") or {}
-        if st:
+        if self._opt is not None:
+            if st and not self._opt.load_state_dict(ck.get("optimizer"), [tuple(p.shape) for _, p in params],
+                                                    steps=ck.get("steps", 1)):
+                raise ValueError(f"the checkpoint's optimiser state is not {self.optim_cfg.name}'s for lp_layer's shapes")
+            if st:
+                self._steps = max(1, int(ck.get("steps", 1)))
+        elif st:
             bufs = [torch.as_tensor(st[i]["momentum_buffer"]) for i in range(len(params))]
             for (name, p), b in zip(params, bufs):
                 if tuple(b.shape) != tuple(p.shape):

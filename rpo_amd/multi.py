@@ -20,11 +20,11 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, optim as _optim
 from .config import RPOConfig
 from .custom_clip import init_prompts, refuse_rn
 from .loop import EvalMixin, epoch_indices
-from .trainer import (OptimConfig, _momentum_from_optimizer_state, checkpoint_dict, load_checkpoint_file, lr_at_epoch,
+from .trainer import (OptimConfig, _momentum_from_optimizer_state, _prompt_shapes, checkpoint_dict, load_checkpoint_file, lr_at_epoch,
                       write_checkpoint)
 
 
@@ -88,6 +88,7 @@ def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig)
 
 
 class RPOMulti(EvalMixin):
+    _opt = None                                         # optim.OptimState: every optimiser but plain SGD
     captures = 0                                        # HIP graphs of the step captured so far (one per distinct learning rate)
 
     def __init__(self, cfg, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None, n_runs: int = 1,
@@ -112,10 +113,15 @@ class RPOMulti(EvalMixin):
         if len(prompts if prompts is not None else seeds) != S:
             raise ValueError(f"RPOMulti: {len(prompts if prompts is not None else seeds)} prompts / seeds for n_runs = {S}")
         self.optim_cfg = optim or OptimConfig()
+        _optim.validate(self.optim_cfg)
         self.lr = lr_at_epoch(self.optim_cfg, 0)
         if prompts is None:
             prompts = seeded_prompts(state_dict, cfg, seeds)
         self._build(cfg, state_dict, tokens, S, B, prompts, device, act_dtype, num_batches, use_graph)
+        if not _optim.is_plain_sgd(self.optim_cfg):     # the members share the config: the flat buffer is ONE set
+            n = self.engine.m_params.numel()
+            with torch.cuda.device(self.device):
+                self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.m_mom)
 
     def _build(self, cfg, state_dict, tokens, S: int, B: int, prompts, device, act_dtype, num_batches: int, use_graph: bool,
                member_K: Optional[Sequence[int]] = None) -> None:
@@ -158,6 +164,9 @@ class RPOMulti(EvalMixin):
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
         eng, oc = self.engine, self.optim_cfg
         eng.multi_forward_backward(image, label)
+        if self._opt is not None:
+            self._opt.step(eng.m_params, eng.m_grads)
+            return
         # one launch over the flat [S, text | img] buffers: the members share the rate, the update is elementwise
         ops.sgd_step(eng.m_params.view(-1), eng.m_grads.view(-1), eng.m_mom.view(-1), self.lr, oc.momentum, oc.weight_decay,
                      1.0, first_step=(self._steps == 0))
@@ -195,7 +204,7 @@ class RPOMulti(EvalMixin):
 
     def _graph_key(self):
         """What a captured step has baked in besides addresses: the learning rate (a kernel argument of rpo_sgd_step)."""
-        return self.lr
+        return self.lr if self._opt is None else 0      # (device data with an OptimState: one capture)
 
     def parse_batch_train(self, batches: Sequence[dict]):
         """S Dassl-style batches {"img": float [B, 3, H, W], "label": [B]} -> one member-major device batch."""
@@ -226,6 +235,8 @@ class RPOMulti(EvalMixin):
     def update_lr(self) -> None:
         self.epoch += 1
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
+        if self._opt is not None:
+            self._opt.set_epoch(self.epoch)
 
     def _loop_advance(self) -> None:
         if (self.batch_idx + 1) == self.num_batches:
@@ -359,6 +370,10 @@ class RPOMulti(EvalMixin):
         for s, d in enumerate(directories):
             ck = member_checkpoint(p[s], m[s], self.cfg, epoch, self.optim_cfg, self.lr, self._steps,
                                    None if val_results is None else val_results[s])
+            if self._opt is not None:
+                n = p.shape[1]
+                ck["optimizer"] = self._opt.state_dict(_prompt_shapes(ck["state_dict"]), lr=self.lr,
+                                                       gather=lambda row, s=s: row[s * n:(s + 1) * n])
             out.append(write_checkpoint(d, ck, epoch, is_best))
         return out
 
@@ -376,11 +391,25 @@ class RPOMulti(EvalMixin):
             raise ValueError("RPOMulti.load_model: some checkpoints carry momentum and some do not (one first-step flag "
                              "covers every member)")
         eng = self.engine
+        if self._opt is not None:
+            n, shapes = eng.m_params.shape[1], [(self.cfg.K, self.cfg.d_t), (self.cfg.K, self.cfg.d_v)]
+            have = [_optim.rows_from_state_dict(self.optim_cfg, ck.get("optimizer"), shapes) is not None for _, _, ck in got]
+            if any(have) != all(have):
+                raise ValueError("RPOMulti.load_model: some checkpoints carry optimiser state and some do not (one step "
+                                 "counter covers every member)")
+            for s, (_, _, ck) in enumerate(got):
+                self._opt.load_state_dict(ck.get("optimizer"), shapes, steps=ck.get("steps", 1),
+                                          scatter=lambda d, r, s=s: d[s * n:(s + 1) * n].copy_(r))
+            if all(have):
+                self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
+            moms = [None]
         eng.m_params.copy_(torch.stack([p for p, _, _ in got]))
         if moms[0] is not None:
             eng.m_mom.copy_(torch.stack(moms))
             self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
         self.epoch = epochs[0]
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
+        if self._opt is not None:
+            self._opt.set_epoch(self.epoch)
         self._eval_member = None
         eng.text_f_version = -1

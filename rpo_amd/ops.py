@@ -682,6 +682,26 @@ def sgd_step_sets(p, g, buf, hyper, seg0: int, seg1: int, first_step: bool, used
     return p
 
 
+def optim_step_sets(p, g, s0, s1, s2, kind, hyper, step, seg0: int, seg1: int, used=None, found_inf=None,
+                    needs_s2: bool = False):
+    """rpo_optim_step_sets: p / g / s0 / s1 (/ s2 or None) [sets, >= seg0 + seg1] fp32 with one row stride; kind int32 [sets],
+    hyper float32 [sets, 8], step int32 [sets], used / found_inf int32 [sets, 2] or None -- all on the device (columns and
+    rules: include/rpo_amd.h)."""
+    sets, stride = p.shape[0], p.stride(0)
+    for t in (p, g, s0, s1) + (() if s2 is None else (s2,)):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == sets and t.stride() == (stride, 1)
+        assert t.shape[1] >= seg0 + seg1
+    assert hyper.dtype == torch.float32 and hyper.is_cuda and tuple(hyper.shape) == (sets, 8) and hyper.is_contiguous()
+    for t in (kind, step):
+        assert t.dtype == torch.int32 and t.is_cuda and tuple(t.shape) == (sets,) and t.is_contiguous()
+    for t in (used, found_inf):
+        assert t is None or (t.dtype == torch.int32 and t.is_cuda and tuple(t.shape) == (sets, 2) and t.is_contiguous())
+    check(_lib.load().rpo_optim_step_sets(p.data_ptr(), g.data_ptr(), s0.data_ptr(), s1.data_ptr(), _p(s2), stride, sets,
+                                          kind.data_ptr(), hyper.data_ptr(), step.data_ptr(), _p(used), seg0, seg1,
+                                          int(needs_s2), _p(found_inf), _stream()), "rpo_optim_step_sets")
+    return p
+
+
 def convert(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     assert src.dtype == torch.float32 and src.shape == dst.shape
     check(_lib.load().rpo_convert(src.data_ptr(), _ld(src), dst.data_ptr(), dtype_code(dst.dtype), _ld(dst),

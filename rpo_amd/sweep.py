@@ -25,10 +25,10 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, optim as _optim
 from .custom_clip import init_prompts, refuse_rn
 from .multi import RPOMulti, member_checkpoint, read_member_checkpoint
-from .trainer import OptimConfig, lr_at_epoch, write_checkpoint
+from .trainer import OptimConfig, _prompt_shapes, lr_at_epoch, write_checkpoint
 
 
 def member_row_to_flat(row: torch.Tensor, K: int, K_s: int, d_t: int, d_v: int) -> torch.Tensor:
@@ -112,6 +112,7 @@ class RPOSweep(RPOMulti):
                 raise ValueError(f"RPOSweep: member {s} has K = {m.get('K')}: every member names its own K >= 1")
             m["K"] = int(m["K"])
             m["optim"] = m.get("optim") or OptimConfig()
+            _optim.validate(m["optim"])
         self.optim_cfgs = [m["optim"] for m in members]
         epochs = [oc.max_epoch for oc in self.optim_cfgs]
         if any(e != epochs[0] for e in epochs):
@@ -138,6 +139,11 @@ class RPOSweep(RPOMulti):
                                               for e in range(self.optim_cfgs[0].max_epoch + 1)]).to(self.device)
             self._used = used_table(self.member_K, cfg.d_t, cfg.d_v).to(self.device)
             self._found_inf = torch.zeros(S, 2, dtype=torch.int32, device=self.device) if self.amp else None
+            # a member that is not plain SGD: every member goes through rpo_optim_step_sets, `kind` and `hyper` per member
+            # (plain-SGD members keep their momentum in m_mom and get the bits of rpo_sgd_step_sets)
+            if not all(_optim.is_plain_sgd(oc) for oc in self.optim_cfgs):
+                self._opt = _optim.OptimState(self.optim_cfgs, self.engine.m_params.stride(0), cfg.K * cfg.d_t,
+                                              cfg.K * cfg.d_v, self.device, s0=self.engine.m_mom, used=self._used)
 
     # ------------------------------------------------------------------ members' state
     def _dims(self, s: int):
@@ -163,7 +169,9 @@ class RPOSweep(RPOMulti):
         return 0                                        # the rates are device data: one capture serves every epoch
 
     def _refresh_hyper(self) -> None:
-        if self._hyper_epoch != self.epoch:
+        if self._opt is not None:
+            self._opt.set_epoch(self.epoch)
+        elif self._hyper_epoch != self.epoch:
             if 0 <= self.epoch < self._hyper_epochs.shape[0]:
                 self._hyper.copy_(self._hyper_epochs[self.epoch])
             else:                                       # (past the schedule's end: the formula still gives a rate)
@@ -173,6 +181,9 @@ class RPOSweep(RPOMulti):
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
         eng, cfg = self.engine, self.cfg
         eng.multi_forward_backward(image, label)
+        if self._opt is not None:
+            self._opt.step(eng.m_params, eng.m_grads, self._found_inf)
+            return
         ops.sgd_step_sets(eng.m_params, eng.m_grads, eng.m_mom, self._hyper, cfg.K * cfg.d_t, cfg.K * cfg.d_v,
                           first_step=(self._steps == 0), used=self._used, found_inf=self._found_inf)
 
@@ -244,6 +255,9 @@ class RPOSweep(RPOMulti):
             ck = member_checkpoint(member_row_to_flat(p[s], *self._dims(s)), member_row_to_flat(m[s], *self._dims(s)),
                                    self.member_cfgs[s], epoch, self.optim_cfgs[s], self.lr[s], self._steps,
                                    None if val_results is None else val_results[s])
+            if self._opt is not None and not _optim.is_plain_sgd(self.optim_cfgs[s]):
+                ck["optimizer"] = self._opt.state_dict(_prompt_shapes(ck["state_dict"]), s=s, lr=self.lr[s],
+                                                       gather=lambda row, s=s: member_row_to_flat(row, *self._dims(s)))
             out.append(write_checkpoint(d, ck, epoch, is_best))
         return out
 
@@ -257,6 +271,22 @@ class RPOSweep(RPOMulti):
         if any(e != epochs[0] for e in epochs):
             raise ValueError(f"RPOSweep.load_model: the checkpoints are of epochs {epochs}; one loop runs all members")
         moms = [m for _, m, _ in got]
+        if self._opt is not None:
+            # per member its own kind's state; a plain-SGD member's momentum is `moms[s]` as before
+            shapes = [[(k, self.cfg.d_t), (k, self.cfg.d_v)] for k in self.member_K]
+            plain = [_optim.is_plain_sgd(oc) for oc in self.optim_cfgs]
+            have = [(moms[s] is not None) if plain[s] else
+                    (_optim.rows_from_state_dict(self.optim_cfgs[s], got[s][2].get("optimizer"), shapes[s]) is not None)
+                    for s in range(self.n_runs)]
+            if any(have) != all(have):
+                raise ValueError("RPOSweep.load_model: some checkpoints carry optimiser state and some do not")
+            if all(have):
+                for s, (_, _, ck) in enumerate(got):
+                    self._opt.load_state_dict(ck.get("optimizer"), shapes[s], s=s, steps=ck.get("steps", 1),
+                                              scatter=lambda d, r, s=s: d.copy_(flat_to_member_row(r, *self._dims(s))))
+                self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
+            self._opt.epoch = None
+            moms = [None] * self.n_runs
         if any(m is None for m in moms) != all(m is None for m in moms):
             raise ValueError("RPOSweep.load_model: some checkpoints carry momentum and some do not (one first-step flag "
                              "covers every member)")

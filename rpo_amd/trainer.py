@@ -14,13 +14,14 @@ from __future__ import annotations
 import collections
 import math
 import os
+import bisect
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, optim as _optim
 from .config import RPOConfig
 from .custom_clip import CustomCLIP
 from .dist import GradSync
@@ -31,7 +32,11 @@ from ._lib import xenv as _xenv
 @dataclass
 class OptimConfig:
     """configs/trainers/RPO/main_K24.yaml:15-22.  momentum / weight_decay are Dassl's
-    defaults (un-vendored; 0.9 / 5e-4 upstream) and therefore explicit here."""
+    defaults (un-vendored; 0.9 / 5e-4 upstream) and therefore explicit here.  So are the fields from `name` on: Dassl's
+    OPTIM block (NAME, SGD_DAMPNING, SGD_NESTEROV, RMSPROP_ALPHA, ADAM_BETA1, ADAM_BETA2, STEPSIZE, GAMMA, WARMUP_MIN_LR)
+    with Dassl's defaults as its source is remembered -- Dassl is not installed to pin them against.  `name`:
+    sgd | adam | amsgrad | adamw | rmsprop (rpo_amd/optim.py); eps is torch's 1e-8 for all kinds.
+    `lr_scheduler`: cosine | single_step | multi_step | anything else = constant."""
     lr: float = 0.01
     max_epoch: int = 15
     lr_scheduler: str = "cosine"
@@ -40,6 +45,15 @@ class OptimConfig:
     warmup_cons_lr: float = 1e-5
     momentum: float = 0.9
     weight_decay: float = 5e-4
+    name: str = "sgd"
+    sgd_dampening: float = 0.0
+    sgd_nesterov: bool = False
+    rmsprop_alpha: float = 0.99
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.999
+    stepsize: Tuple[int, ...] = (-1,)
+    gamma: float = 0.1
+    warmup_min_lr: float = 1e-5
 
 
 def lr_at_epoch(oc: OptimConfig, epoch: int) -> float:
@@ -47,17 +61,30 @@ def lr_at_epoch(oc: OptimConfig, epoch: int) -> float:
     CosineAnnealingLR(T_max=max_epoch) (`build_lr_scheduler`, trainers/rpo.py:275): the warm-up wrapper does NOT
     step its successor while it warms up, so the cosine starts at its own epoch 0 when the warm-up ends --
     epoch e >= warmup runs at cos(pi * (e - warmup) / T), i.e. epoch 1 of the yaml's schedule runs at the full
-    0.01 (pinned against a re-creation driven by torch's CosineAnnealingLR in tests/test_host_logic.py)."""
-    warm = oc.warmup_epoch if oc.warmup_type == "constant" else 0
+    0.01 (pinned against a re-creation driven by torch's CosineAnnealingLR in tests/test_host_logic.py).
+    "single_step" is StepLR(step_size = stepsize[-1], or max_epoch when that is <= 0; gamma), "multi_step" is
+    MultiStepLR(milestones = stepsize, gamma), both in closed form.  Warm-up "linear" (Dassl's LinearWarmupScheduler as
+    remembered): epoch 0 at warmup_min_lr, epoch e < warmup_epoch at lr * e / warmup_epoch; its successor starts at its own
+    epoch 0 as after the constant warm-up."""
+    warm = oc.warmup_epoch if oc.warmup_type in ("constant", "linear") else 0
     if epoch < warm:
-        return oc.warmup_cons_lr
+        if oc.warmup_type == "constant":
+            return oc.warmup_cons_lr
+        return oc.warmup_min_lr if epoch == 0 else oc.lr * epoch / oc.warmup_epoch
+    e = epoch - warm
     if oc.lr_scheduler == "cosine":
-        return 0.5 * oc.lr * (1.0 + math.cos(math.pi * (epoch - warm) / oc.max_epoch))
+        return 0.5 * oc.lr * (1.0 + math.cos(math.pi * e / oc.max_epoch))
+    if oc.lr_scheduler == "single_step":
+        size = oc.stepsize[-1] if oc.stepsize[-1] > 0 else oc.max_epoch
+        return oc.lr * oc.gamma ** (e // size)
+    if oc.lr_scheduler == "multi_step":
+        return oc.lr * oc.gamma ** bisect.bisect_right(sorted(oc.stepsize), e)
     return oc.lr
 
 
 class RPO(LoopMixin):
     _takes_next_image = True         # run_epoch names the next batch: its patch embedding runs under this step
+    _opt = None                      # optim.OptimState: every optimiser but plain SGD (DESIGN.md section 9k)
     _takes_frozen = True             # test(..., frozen=...): the prompt-row pass alone on a set's cached frozen K / V
 
     def __init__(self, cfg: RPOConfig, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
@@ -71,6 +98,8 @@ class RPO(LoopMixin):
         # gradient holds Inf / NaN is skipped on every rank (the flag is computed after the all-reduce)
         self.amp = amp
         self.optim_cfg = optim or OptimConfig()
+        _optim.validate(self.optim_cfg)
+        self._opt = None                             # optim.OptimState: every optimiser but plain SGD
         # default: joins (or creates) the process group when launched under torchrun; a lone process stays local.
         # Built BEFORE the device is resolved: under a launcher it makes this rank's GPU the current device, and an
         # index-less "cuda" then means that GPU on every rank (not cuda:0 eight times).
@@ -113,6 +142,10 @@ class RPO(LoopMixin):
         self._label = torch.zeros(self.batch_size, dtype=torch.int64, device=self.device)
         if self.sync.enabled:                       # identical prompts on every rank
             self.sync.broadcast(self.engine.params)
+        if not _optim.is_plain_sgd(self.optim_cfg):
+            n = self.engine.params.numel()
+            self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.mom,
+                                          grad_scale=self.sync.grad_scale)
 
     def transform(self, is_train: bool):
         """Device-side counterpart of Dassl's `build_transform(cfg, is_train)` (rpo_amd/input_pipeline.py),
@@ -233,7 +266,9 @@ class RPO(LoopMixin):
         # cost the image forward -- so it is on below 2048 image token rows per step only.  RPO_EARLY_TEXT=1 / =0 force it.
         want = os.environ.get("RPO_EARLY_TEXT")
         small = self.batch_size * (self.cfg.n_frozen + self.cfg.K) < 2048
+        # (nor with a table-driven optimiser: one launch steps the set and advances its counter once)
         self._early_text = ((want == "1" or (want is None and small)) and not self.amp and not self._joint_bwd
+                            and self._opt is None
                             and self._bwd_parts == 1 and (not self.sync.enabled or self._split_collective))
         self._text_fwd_for = -1
         # ONE GRAPH PER STEP (round 6, RPO_ONE_GRAPH=1): text fwd || image fwd -> head -> text bwd (+ its all-reduce) ||
@@ -381,6 +416,8 @@ class RPO(LoopMixin):
         eng, oc = self.engine, self.optim_cfg
         assert torch.cuda.current_device() == self.device.index, "set the trainer's device current (torch.cuda.set_device)"
         assert image.shape[0] == self.batch_size, "graph path needs the configured batch size"
+        if self._opt is not None:
+            self._opt.set_epoch(self.epoch)
         tag = (image.data_ptr(), image._version)
         pending = self.use_graph and self._graph is not None and self._patch_tag is not None
         patch_ready = pending and self._patch_tag == tag
@@ -417,7 +454,8 @@ class RPO(LoopMixin):
         graph per learning rate when the collectives are captured (N > 1 on RCCL), else as plain launches."""
         tail = None
         if self.use_graph and getattr(self, "_graph_collectives", False) and self._steps > 0:
-            key = (self.lr, which)                              # the rate is a kernel argument: one small graph per rate
+            # the rate is a kernel argument of rpo_sgd_step: one small graph per rate (device data with an OptimState)
+            key = (self.lr if getattr(self, "_opt", None) is None else None, which)
             tail = self._tail_graphs.get(key)
             if tail is None:
                 try:
@@ -454,7 +492,9 @@ class RPO(LoopMixin):
                 self.sync.all_reduce_sum(eng.g_img_flat)        # (g_text went out behind the text backward, _replay)
             else:
                 self.sync.all_reduce_sum(eng.grads)
-        if self.amp:
+        if getattr(self, "_opt", None) is not None:
+            self._opt.step(eng.params, eng.grads, self._found_inf if self.amp else None)
+        elif self.amp:
             ops.sgd_step_guarded(eng.params, eng.grads, eng.mom, self.lr, oc.momentum, oc.weight_decay,
                                  self.sync.grad_scale, first_step=(self._steps == 0), found_inf=self._found_inf)
         else:
@@ -464,6 +504,8 @@ class RPO(LoopMixin):
     def update_lr(self) -> None:
         self.epoch += 1
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
+        if getattr(self, "_opt", None) is not None:
+            self._opt.set_epoch(self.epoch)
 
     def check_finite(self) -> None:
         """NaN / Inf scan of the step's outputs (the reference's `set_detect_anomaly(True)`, trainers/rpo.py:288)."""
@@ -546,6 +588,8 @@ class RPO(LoopMixin):
         self._join_side()
         ck = checkpoint_dict(self.model.prompt_learner.state_dict(), epoch, self.engine.mom, self.optim_cfg,
                              self.lr, self._steps, self.cfg.K * self.cfg.d_t, val_result)
+        if getattr(self, "_opt", None) is not None:             # torch's own layout for the kind
+            ck["optimizer"] = self._opt.state_dict(_prompt_shapes(ck["state_dict"]), lr=self.lr)
         return write_checkpoint(directory, ck, epoch, is_best)
 
     def after_epoch_eval(self, directory: str, val_result: float) -> bool:
@@ -575,13 +619,21 @@ class RPO(LoopMixin):
             for name, p in self.model.prompt_learner.named_parameters():
                 if name in sd:
                     p.copy_(sd[name].to(p.dtype))
-        mom = _momentum_from_optimizer_state(ck.get("optimizer"), self.engine.mom.numel())
-        if mom is not None:
-            self.engine.mom.copy_(mom)
-            self._steps = max(1, int(ck.get("steps", 1)))
+        opt = getattr(self, "_opt", None)
+        if opt is not None:                                     # (a file without matching state: weights only)
+            shapes = [tuple(p.shape) for _, p in self.model.prompt_learner.named_parameters()]
+            if opt.load_state_dict(ck.get("optimizer"), shapes, steps=ck.get("steps", 1)):
+                self._steps = max(1, int(ck.get("steps", 1)))
+        else:
+            mom = _momentum_from_optimizer_state(ck.get("optimizer"), self.engine.mom.numel())
+            if mom is not None:
+                self.engine.mom.copy_(mom)
+                self._steps = max(1, int(ck.get("steps", 1)))
         self.engine.params_version += 1
         self.epoch = int(ck.get("epoch", 0))
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
+        if opt is not None:
+            opt.set_epoch(self.epoch)
 
 
 # Names a checkpoint written by the reference's own run may reference (module, qualified name).  Dassl's
@@ -688,6 +740,10 @@ def checkpoint_dict(prompt_state, epoch: int, momentum: Optional[torch.Tensor], 
              "params": [0, 1]}
     return {"state_dict": sd, "epoch": int(epoch), "optimizer": {"state": state, "param_groups": [group]},
             "scheduler": {"last_epoch": int(epoch)}, "val_result": val_result, "steps": int(steps)}
+
+
+def _prompt_shapes(sd) -> list:
+    return [tuple(sd["text_prompt"].shape), tuple(sd["img_prompt"].shape)]
 
 
 def write_checkpoint(directory: str, ck: dict, epoch: int, is_best: bool = False, name: str = "prompt_learner") -> str:
