@@ -30,7 +30,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops, optim as _optim
+from . import optim as _optim
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .engine import Engine, make_engine
@@ -124,7 +124,6 @@ class CoOp(LoopMixin):
     un-vendored, hence explicit: OptimConfig)."""
 
     _reports_acc = True              # forward_backward reports "acc": run_epoch sums it on the device
-    _opt = None                      # optim.OptimState: every optimiser but plain SGD
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int = 16,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",
@@ -151,13 +150,9 @@ class CoOp(LoopMixin):
         self.amp = amp
         self._found_inf = torch.zeros(2, dtype=torch.int32, device=self.device) if amp else None
         self.best_result = -float("inf")
-        # every optimiser but plain SGD: the table-driven kernel on the flat buffer as one set
-        _optim.validate(self.optim_cfg)
-        self._opt = None
-        if not _optim.is_plain_sgd(self.optim_cfg):
-            n = self.engine.coop_params.numel()
-            with torch.cuda.device(self.device):
-                self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.coop_moms)
+        n = self.engine.coop_params.numel()              # the flat buffer as one set
+        with torch.cuda.device(self.device):
+            self._opt = _optim.make_optimizer([self.optim_cfg], n, n, 0, self.device, s0=self.engine.coop_moms)
 
     def _param_shapes(self):
         return [tuple(t.shape) for _, t in self.model.prompt_learner.named_parameters()]
@@ -166,16 +161,9 @@ class CoOp(LoopMixin):
         self.engine.coop_forward_backward(image, label)
 
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
-        eng, oc = self.engine, self.optim_cfg
+        eng = self.engine
         self._forward_backward(image, label)
-        if self._opt is not None:
-            self._opt.step(eng.coop_params, eng.coop_grads, self._found_inf)
-        elif self.amp:
-            ops.sgd_step_guarded(eng.coop_params, eng.coop_grads, eng.coop_moms, self.lr, oc.momentum, oc.weight_decay,
-                                 1.0, first_step=(self._steps == 0), found_inf=self._found_inf)
-        else:
-            ops.sgd_step(eng.coop_params, eng.coop_grads, eng.coop_moms, self.lr, oc.momentum, oc.weight_decay, 1.0,
-                         first_step=(self._steps == 0))
+        self._opt.step(eng.coop_params, eng.coop_grads, self._found_inf, first_step=(self._steps == 0))
 
     @property
     def skipped_steps(self) -> int:
@@ -187,23 +175,11 @@ class CoOp(LoopMixin):
                    val_result: Optional[float] = None) -> str:
         """`<directory>/prompt_learner/model.pth.tar-<epoch>` (+ `model-best.pth.tar`) with `state_dict` (ctx, the
         meta-net for CoCoOp, and the token_prefix / token_suffix buffers the reference's module registers, :100-101),
-        `epoch`, `optimizer` (torch.optim.SGD's state-dict layout, parameters in `named_parameters` order)."""
+        `epoch`, `optimizer` (the torch optimiser's own state-dict layout, parameters in `named_parameters` order)."""
         epoch = self.epoch if epoch is None else epoch
-        pl = self.model.prompt_learner
-        state, off, oc = {}, 0, self.optim_cfg
-        names = [n for n, _ in pl.named_parameters()]
-        if self._steps > 0:
-            m = self.engine.coop_moms.detach().cpu()
-            for i, (_, t) in enumerate(pl.named_parameters()):
-                state[i] = {"momentum_buffer": m[off:off + t.numel()].reshape(t.shape).clone()}
-                off += t.numel()
-        group = {"lr": self.lr, "momentum": oc.momentum, "dampening": 0, "weight_decay": oc.weight_decay, "nesterov": False,
-                 "maximize": False, "foreach": None, "differentiable": False, "fused": None, "initial_lr": oc.lr,
-                 "params": list(range(len(names)))}
-        ck = {"state_dict": pl.state_dict(), "epoch": int(epoch), "optimizer": {"state": state, "param_groups": [group]},
+        optimizer = self._opt.state_dict(self._param_shapes(), lr=self.lr, steps=self._steps)
+        ck = {"state_dict": self.model.prompt_learner.state_dict(), "epoch": int(epoch), "optimizer": optimizer,
               "scheduler": {"last_epoch": int(epoch)}, "val_result": val_result, "steps": int(self._steps)}
-        if self._opt is not None:                                # torch's own layout for the kind
-            ck["optimizer"] = self._opt.state_dict(self._param_shapes(), lr=self.lr)
         return write_checkpoint(directory, ck, epoch, is_best)
 
     def load_model(self, directory: str, epoch: Optional[int] = None) -> Optional[dict]:
@@ -242,54 +218,20 @@ class CoOp(LoopMixin):
         ck = self.load_model(directory, epoch)
         if ck is None:
             raise ValueError("resume_model needs a checkpoint directory (load_model skipped: nothing was loaded)")
-        params = list(self.model.prompt_learner.named_parameters())
-        st = (ck.get("optimizer") or {}).get("state") or {}
-        if self._opt is not None:
-            if st and not self._opt.load_state_dict(ck.get("optimizer"), self._param_shapes(), steps=ck.get("steps", 1)):
-                raise ValueError(f"the checkpoint's optimiser state is not {self.optim_cfg.name}'s for these tensors: it was "
-                                 "written with another optimiser or other context settings")
-            if st:
-                self._steps = max(1, int(ck.get("steps", 1)))
-        elif st:
-            bufs = [st[i]["momentum_buffer"] for i in range(len(params))]
-            flat = torch.cat([torch.as_tensor(b).reshape(-1).float() for b in bufs])
-            if flat.numel() != self.engine.coop_moms.numel():
-                raise ValueError(f"checkpoint momentum has {flat.numel()} elements, the trainer {self.engine.coop_moms.numel()}: "
+        opt_state = ck.get("optimizer")
+        if (opt_state or {}).get("state"):                       # (a file with no state at all: epoch and rate only)
+            if not self._opt.load_state_dict(opt_state, self._param_shapes(), steps=ck.get("steps", 1)):
+                if self._opt.table_driven:
+                    raise ValueError(f"the checkpoint's optimiser state is not {self.optim_cfg.name}'s for these tensors: it "
+                                     "was written with another optimiser or other context settings")
+                n = sum(int(np.prod(sh)) for sh in _optim.state_shapes(self.optim_cfg, opt_state))
+                raise ValueError(f"checkpoint momentum has {n} elements, the trainer {self.engine.coop_moms.numel()}: "
                                  "it was written with other context settings")
-            self.engine.coop_moms.copy_(flat)
             self._steps = max(1, int(ck.get("steps", 1)))
         self.epoch = int(ck.get("epoch", 0))
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
         self._graph = None
         return self.epoch
-
-    def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-        """One optimisation step, nothing synchronised; returns the device loss scalar.  With use_graph the ~250 launches
-        of a step (plain image tower, dense text tower forward + backward, head, SGD) are replayed from ONE HIP graph,
-        captured after the first (eager) step and again whenever the learning rate changes (it is a kernel argument)."""
-        key = self.lr
-        if self._opt is not None:                       # the rate is device data: one capture serves every epoch
-            self._opt.set_epoch(self.epoch)
-            key = None
-        if not self.use_graph or self._steps == 0 or image.shape[0] != self.batch_size:
-            self._enqueue(image, label)
-        else:
-            if self._graph is None or self._graph[1] != key:
-                self._img = torch.empty_like(image)
-                self._lab = torch.empty_like(label)
-                self._img.copy_(image); self._lab.copy_(label)
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._enqueue(self._img, self._lab)
-                self._graph = (g, key)
-                # (capture does not execute: the replay below is this step)
-            if image.data_ptr() != self._img.data_ptr():
-                self._img.copy_(image, non_blocking=True)
-            self._lab.copy_(label, non_blocking=True)
-            self._graph[0].replay()
-        self._steps += 1
-        return self.engine.loss
 
     def parse_batch_train(self, batch):
         img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
@@ -301,19 +243,14 @@ class CoOp(LoopMixin):
         return img, label.to(self.device, dtype=torch.int64, non_blocking=True)
 
     def forward_backward(self, batch) -> Dict[str, float]:
-        eng, oc = self.engine, self.optim_cfg
+        eng = self.engine
         with torch.cuda.device(self.device):
             image, label = self.parse_batch_train(batch)
             self.step_async(image, label)
             logits = eng.logits[:image.shape[0]]
             acc = float((logits.argmax(1) == label).float().mean().item()) * 100.0      # compute_accuracy()[0]
             summary = {"loss": float(eng.loss.item()), "acc": acc}
-        if (self.batch_idx + 1) == self.num_batches:
-            self.epoch += 1
-            self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-            self.batch_idx = 0
-        else:
-            self.batch_idx += 1
+        self._loop_advance()
         return summary
 
     @torch.no_grad()
@@ -410,15 +347,10 @@ class CoCoOp(CoOp):
         self.engine.cocoop_forward_backward(image, label)
 
     def forward_backward(self, batch) -> Dict[str, float]:
-        eng, oc = self.engine, self.optim_cfg
+        eng = self.engine
         with torch.cuda.device(self.device):
             image, label = self.parse_batch_train(batch)
             self.step_async(image, label)
             summary = {"loss": float(eng.loss.item())}
-        if (self.batch_idx + 1) == self.num_batches:
-            self.epoch += 1
-            self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-            self.batch_idx = 0
-        else:
-            self.batch_idx += 1
+        self._loop_advance()
         return summary

@@ -136,8 +136,8 @@ class EvalMixin:
 
 class LoopMixin(EvalMixin):
     """`run_epoch` / `test` / `train` for a trainer that has `step_async`, `batch_size`, `num_batches`, `batch_idx`,
-    `epoch`, `lr`, `optim_cfg`, `cfg`, `device`, `engine` (RPO, CoOp, CoCoOp, LP).  The small `_loop_*` methods are
-    everything the control flow touches on the device."""
+    `epoch`, `lr`, `optim_cfg`, `_opt` (rpo_amd/optim.py), `cfg`, `device`, `engine` (RPO, CoOp, CoCoOp, LP).  The small
+    `_loop_*` methods are everything the control flow touches on the device."""
 
     _takes_next_image = False          # step_async(image, label, next_image=...) (RPO)
     _reports_acc = False               # forward_backward reports "acc" (CoOp, LP)
@@ -174,15 +174,44 @@ class LoopMixin(EvalMixin):
     def _loop_advance(self) -> None:
         """What every `forward_backward` does after its step: the LR / epoch update behind the epoch's last batch."""
         if (self.batch_idx + 1) == self.num_batches:
-            if hasattr(self, "update_lr"):
-                self.update_lr()
-            else:
-                from .trainer import lr_at_epoch
-                self.epoch += 1
-                self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
+            self.update_lr()
             self.batch_idx = 0
         else:
             self.batch_idx += 1
+
+    def update_lr(self) -> None:
+        from .trainer import lr_at_epoch
+        self.epoch += 1
+        self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
+        self._opt.set_epoch(self.epoch)
+
+    # ---- the step of the trainers whose whole step is one graph (CoOp, CoCoOp, LP) -------------------------
+    def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        """One optimisation step (`_enqueue`: forward, backward, the optimiser's step), nothing synchronised; returns the
+        device loss scalar.  With use_graph the launches of a step are replayed from ONE HIP graph, captured after the first
+        (eager) step and again whenever the optimiser's `graph_key` changes (plain SGD: the learning rate, a kernel
+        argument; device data otherwise: one capture serves every epoch)."""
+        self._opt.set_epoch(self.epoch)
+        key = self._opt.graph_key()
+        if not self.use_graph or self._steps == 0 or image.shape[0] != self.batch_size:
+            self._enqueue(image, label)
+        else:
+            if self._graph is None or self._graph[1] != key:
+                self._img = torch.empty_like(image)
+                self._lab = torch.empty_like(label)
+                self._img.copy_(image); self._lab.copy_(label)
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    self._enqueue(self._img, self._lab)
+                self._graph = (g, key)
+                # (capture does not execute: the replay below is this step)
+            if image.data_ptr() != self._img.data_ptr():
+                self._img.copy_(image, non_blocking=True)
+            self._lab.copy_(label, non_blocking=True)
+            self._graph[0].replay()
+        self._steps += 1
+        return self.engine.loss
 
     # ---- the loops -----------------------------------------------------------------------------------------
     def run_epoch(self, image_set, generator: Optional[torch.Generator] = None, plans=None) -> Dict[str, torch.Tensor]:

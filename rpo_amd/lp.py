@@ -21,7 +21,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import ops, optim as _optim
+from . import optim as _optim
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .dist import GradSync
@@ -108,7 +108,6 @@ class LP(LoopMixin):
     (GradSync), grad_scale 1 / world_size in the SGD step."""
 
     _reports_acc = True              # forward_backward reports "acc": run_epoch sums it on the device
-    _opt = None                      # optim.OptimState: every optimiser but plain SGD
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, optim: Optional[OptimConfig] = None,
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float32, batch_size: int = 32,
@@ -137,65 +136,28 @@ class LP(LoopMixin):
         self.amp = amp
         self._found_inf = torch.zeros(2, dtype=torch.int32, device=self.device) if amp else None
         self.best_result = -float("inf")
-        # every optimiser but plain SGD: the table-driven kernel on the flat [W | b] buffer as one set
-        _optim.validate(self.optim_cfg)
-        self._opt = None
-        if not _optim.is_plain_sgd(self.optim_cfg):
-            n = self.engine.lp_params.numel()
-            with torch.cuda.device(self.device):
-                self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.lp_moms,
+        n = self.engine.lp_params.numel()                # the flat [W | b] buffer as one set
+        with torch.cuda.device(self.device):
+            self._opt = _optim.make_optimizer([self.optim_cfg], n, n, 0, self.device, s0=self.engine.lp_moms,
                                               grad_scale=self.sync.grad_scale)
         if self.sync.enabled:                            # identical layer on every rank
             with torch.cuda.device(self.device):
                 self.sync.broadcast(self.engine.lp_params)
 
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
-        eng, oc = self.engine, self.optim_cfg
+        eng = self.engine
         eng.lp_forward_backward(image, label)
         if self.sync.enabled:
             self.sync.all_reduce_sum(eng.lp_grads)
-        gs = self.sync.grad_scale
-        if self._opt is not None:
-            self._opt.step(eng.lp_params, eng.lp_grads, self._found_inf)
-        elif self.amp:
-            ops.sgd_step_guarded(eng.lp_params, eng.lp_grads, eng.lp_moms, self.lr, oc.momentum, oc.weight_decay, gs,
-                                 first_step=(self._steps == 0), found_inf=self._found_inf)
-        else:
-            ops.sgd_step(eng.lp_params, eng.lp_grads, eng.lp_moms, self.lr, oc.momentum, oc.weight_decay, gs,
-                         first_step=(self._steps == 0))
+        self._opt.step(eng.lp_params, eng.lp_grads, self._found_inf, first_step=(self._steps == 0))
+
+    def _param_shapes(self):
+        return [tuple(t.shape) for _, t in self.model.named_parameters()]
 
     @property
     def skipped_steps(self) -> int:
         """amp: steps GradScaler would have skipped so far (a device read)."""
         return int(self._found_inf[1].item()) if self.amp else 0
-
-    def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-        """One optimisation step, nothing synchronised; returns the device loss scalar.  With use_graph the whole step
-        (plain image tower, LP head, SGD) is replayed from ONE HIP graph, captured after the first (eager) step and again
-        whenever the learning rate changes (it is a kernel argument)."""
-        key = self.lr
-        if self._opt is not None:                       # the rate is device data: one capture serves every epoch
-            self._opt.set_epoch(self.epoch)
-            key = None
-        if not self.use_graph or self._steps == 0 or image.shape[0] != self.batch_size:
-            self._enqueue(image, label)
-        else:
-            if self._graph is None or self._graph[1] != key:
-                self._img = torch.empty_like(image)
-                self._lab = torch.empty_like(label)
-                self._img.copy_(image); self._lab.copy_(label)
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._enqueue(self._img, self._lab)
-                self._graph = (g, key)
-                # (capture does not execute: the replay below is this step)
-            if image.data_ptr() != self._img.data_ptr():
-                self._img.copy_(image, non_blocking=True)
-            self._lab.copy_(label, non_blocking=True)
-            self._graph[0].replay()
-        self._steps += 1
-        return self.engine.loss
 
     def parse_batch_train(self, batch):
         img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
@@ -215,12 +177,7 @@ class LP(LoopMixin):
             logits = eng.logits[:image.shape[0]]
             acc = float((logits.argmax(1) == label).float().mean().item()) * 100.0      # compute_accuracy()[0]
             summary = {"loss": float(eng.loss.item()), "acc": acc}
-        if (self.batch_idx + 1) == self.num_batches:
-            self.epoch += 1
-            self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-            self.batch_idx = 0
-        else:
-            self.batch_idx += 1
+        self._loop_advance()
         return summary
 
     @torch.no_grad()
@@ -231,21 +188,9 @@ class LP(LoopMixin):
     # -- checkpoints in Dassl's layout (the reader: trainers/linear_prob.py:193-225) ----------------------------------------
     def checkpoint_dict(self, epoch: Optional[int] = None, val_result: Optional[float] = None) -> dict:
         """The dict Dassl's save_checkpoint pickles: `state_dict` (lp_layer's weight, bias), `epoch`, `optimizer`
-        (torch.optim.SGD's state-dict layout, param 0 = weight, 1 = bias), `scheduler`, `val_result`."""
+        (the torch optimiser's own state-dict layout, param 0 = weight, 1 = bias), `scheduler`, `val_result`."""
         epoch = self.epoch if epoch is None else epoch
-        oc, state = self.optim_cfg, {}
-        params = list(self.model.named_parameters())
-        if self._steps > 0:
-            m, off = self.engine.lp_moms.detach().cpu(), 0
-            for i, (_, t) in enumerate(params):
-                state[i] = {"momentum_buffer": m[off:off + t.numel()].reshape(t.shape).clone()}
-                off += t.numel()
-        group = {"lr": self.lr, "momentum": oc.momentum, "dampening": 0, "weight_decay": oc.weight_decay, "nesterov": False,
-                 "maximize": False, "foreach": None, "differentiable": False, "fused": None, "initial_lr": oc.lr,
-                 "params": list(range(len(params)))}
-        optimizer = {"state": state, "param_groups": [group]}
-        if self._opt is not None:                                # torch's own layout for the kind
-            optimizer = self._opt.state_dict([tuple(t.shape) for _, t in params], lr=self.lr)
+        optimizer = self._opt.state_dict(self._param_shapes(), lr=self.lr, steps=self._steps)
         return {"state_dict": self.model.state_dict(), "epoch": int(epoch),
                 "optimizer": optimizer, "scheduler": {"last_epoch": int(epoch)},
                 "val_result": val_result, "steps": int(self._steps)}
@@ -295,19 +240,14 @@ class LP(LoopMixin):
         sd = ck["state_dict"]
         if any(n not in sd for n, _ in params):
             raise ValueError("checkpoint lacks lp_layer's weight / bias: it was written by another trainer")
-        st = (ck.get("optimizer") or {}).get("state") or {}
-        if self._opt is not None:
-            if st and not self._opt.load_state_dict(ck.get("optimizer"), [tuple(p.shape) for _, p in params],
-                                                    steps=ck.get("steps", 1)):
+        opt_state = ck.get("optimizer")
+        if (opt_state or {}).get("state"):                       # (a file with no state at all: epoch and rate only)
+            if not self._opt.load_state_dict(opt_state, self._param_shapes(), steps=ck.get("steps", 1)):
+                if not self._opt.table_driven:
+                    for (name, p), sh in zip(params, _optim.state_shapes(self.optim_cfg, opt_state)):
+                        if sh != tuple(p.shape):
+                            raise ValueError(f"checkpoint momentum of {name} has shape {sh}, lp_layer {tuple(p.shape)}")
                 raise ValueError(f"the checkpoint's optimiser state is not {self.optim_cfg.name}'s for lp_layer's shapes")
-            if st:
-                self._steps = max(1, int(ck.get("steps", 1)))
-        elif st:
-            bufs = [torch.as_tensor(st[i]["momentum_buffer"]) for i in range(len(params))]
-            for (name, p), b in zip(params, bufs):
-                if tuple(b.shape) != tuple(p.shape):
-                    raise ValueError(f"checkpoint momentum of {name} has shape {tuple(b.shape)}, lp_layer {tuple(p.shape)}")
-            self.engine.lp_moms.copy_(torch.cat([b.reshape(-1).float() for b in bufs]))
             self._steps = max(1, int(ck.get("steps", 1)))
         self.epoch = int(ck.get("epoch", 0))
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)

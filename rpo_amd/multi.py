@@ -20,12 +20,11 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops, optim as _optim
+from . import optim as _optim
 from .config import RPOConfig
 from .custom_clip import init_prompts, refuse_rn
 from .loop import EvalMixin, epoch_indices
-from .trainer import (OptimConfig, _momentum_from_optimizer_state, _prompt_shapes, checkpoint_dict, load_checkpoint_file, lr_at_epoch,
-                      write_checkpoint)
+from .trainer import OptimConfig, checkpoint_dict, load_checkpoint_file, lr_at_epoch, write_checkpoint
 
 
 def _one_of(values, what: str):
@@ -63,16 +62,18 @@ def member_batches(set_sizes: Sequence[int], batch_size: int, generators: Sequen
 
 
 def member_checkpoint(flat_params: torch.Tensor, flat_mom: Optional[torch.Tensor], cfg: RPOConfig, epoch: int,
-                      oc: OptimConfig, lr: float, steps: int, val_result: Optional[float] = None) -> dict:
-    """The dict a standalone ``RPO.save_model`` pickles for a run whose flat [text | img] parameters / momentum are these."""
+                      oc: OptimConfig, lr: float, steps: int, val_result: Optional[float] = None,
+                      optimizer: Optional[dict] = None) -> dict:
+    """The dict a standalone ``RPO.save_model`` pickles for a run whose flat [text | img] parameters / momentum (or
+    `optimizer` entry) are these."""
     nt = cfg.K * cfg.d_t
     p = flat_params.detach().cpu()
     state = {"text_prompt": p[:nt].reshape(cfg.K, cfg.d_t), "img_prompt": p[nt:].reshape(cfg.K, cfg.d_v)}
-    return checkpoint_dict(state, epoch, flat_mom, oc, lr, steps, nt, val_result)
+    return checkpoint_dict(state, epoch, flat_mom, oc, lr, steps, nt, val_result, optimizer)
 
 
 def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig):
-    """(flat params, flat momentum or None, checkpoint dict) of a file ``RPO.save_model`` / ``RPOMulti.save_model`` wrote."""
+    """(flat params, checkpoint dict) of a file ``RPO.save_model`` / ``RPOMulti.save_model`` wrote."""
     model_file = "model-best.pth.tar" if epoch is None else f"model.pth.tar-{epoch}"
     model_path = os.path.join(directory, "prompt_learner", model_file)
     if not os.path.exists(model_path):
@@ -84,11 +85,12 @@ def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig)
         raise ValueError(f"{model_path}: prompts {tuple(tp.shape)} / {tuple(ip.shape)}, this trainer has K = {cfg.K}, "
                          f"widths {cfg.d_t} / {cfg.d_v}")
     flat = torch.cat([tp.reshape(-1), ip.reshape(-1)])
-    return flat, _momentum_from_optimizer_state(ck.get("optimizer"), flat.numel()), ck
+    return flat, ck
 
 
 class RPOMulti(EvalMixin):
-    _opt = None                                         # optim.OptimState: every optimiser but plain SGD
+    _found_inf = None                                   # amp is refused here; `RPOSweep` has one verdict per member
+    _one_counter = " (one step counter covers every member)"     # why a mix of files with and without state is refused
     captures = 0                                        # HIP graphs of the step captured so far (one per distinct learning rate)
 
     def __init__(self, cfg, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None, n_runs: int = 1,
@@ -118,10 +120,9 @@ class RPOMulti(EvalMixin):
         if prompts is None:
             prompts = seeded_prompts(state_dict, cfg, seeds)
         self._build(cfg, state_dict, tokens, S, B, prompts, device, act_dtype, num_batches, use_graph)
-        if not _optim.is_plain_sgd(self.optim_cfg):     # the members share the config: the flat buffer is ONE set
-            n = self.engine.m_params.numel()
-            with torch.cuda.device(self.device):
-                self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.m_mom)
+        n = self.engine.m_params.numel()                # the members share the config: the flat [S, text | img] buffer is ONE
+        with torch.cuda.device(self.device):            # set, one launch (the update is elementwise)
+            self._opt = _optim.make_optimizer([self.optim_cfg], n, n, 0, self.device, s0=self.engine.m_mom)
 
     def _build(self, cfg, state_dict, tokens, S: int, B: int, prompts, device, act_dtype, num_batches: int, use_graph: bool,
                member_K: Optional[Sequence[int]] = None) -> None:
@@ -130,7 +131,7 @@ class RPOMulti(EvalMixin):
         self.cfg, self.n_runs, self.batch_size, self.num_batches = cfg, S, B, num_batches
         self.use_graph = use_graph
         self.epoch = self.batch_idx = self._steps = 0
-        self._graph = None                              # (HIP graph of one step, the `_graph_key` it was captured with)
+        self._graph = None                              # (HIP graph of one step, the optimiser's `graph_key` it was captured with)
         self._warm = False
         self.device = torch.device(device)
         if self.device.index is None:
@@ -162,31 +163,28 @@ class RPOMulti(EvalMixin):
 
     # ------------------------------------------------------------------ the step
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
-        eng, oc = self.engine, self.optim_cfg
+        eng = self.engine
         eng.multi_forward_backward(image, label)
-        if self._opt is not None:
-            self._opt.step(eng.m_params, eng.m_grads)
-            return
-        # one launch over the flat [S, text | img] buffers: the members share the rate, the update is elementwise
-        ops.sgd_step(eng.m_params.view(-1), eng.m_grads.view(-1), eng.m_mom.view(-1), self.lr, oc.momentum, oc.weight_decay,
-                     1.0, first_step=(self._steps == 0))
+        self._opt.step(eng.m_params, eng.m_grads, self._found_inf, first_step=(self._steps == 0))
 
     def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
         """One optimisation step of every member, nothing synchronised: image [S*B, 3, H, W] and label [S*B], member-major
         (member s owns rows [s B, (s+1) B)).  Returns loss [S] on the device.  With use_graph the whole step -- both
         towers, the grouped head, both backward chains, the SGD launch -- is ONE HIP graph, captured after the first
-        (eager) step and again whenever the learning rate changes (it is a kernel argument)."""
+        (eager) step and again whenever the optimiser's `graph_key` changes (plain SGD: the learning rate, a kernel argument)."""
         assert torch.cuda.current_device() == self.device.index, "set the trainer's device current (torch.cuda.set_device)"
         SB = self.n_runs * self.batch_size
         assert image.shape[0] == SB and label.shape == (SB,), f"step_async takes S * B = {SB} images, member-major"
         if image.data_ptr() != self._image.data_ptr():
             self._image.copy_(image, non_blocking=True)
         self._label.copy_(label, non_blocking=True)
+        self._opt.set_epoch(self.epoch)                 # (in front of the step, on its stream; nothing within an epoch)
+        key = self._opt.graph_key()                     # what a captured step has baked in besides addresses
         if not self.use_graph or self._steps == 0:
             self._enqueue(self._image, self._label)
             self._warm = True
         else:
-            if self._graph is None or self._graph[1] != self._graph_key():
+            if self._graph is None or self._graph[1] != key:
                 if not self._warm:                      # (a resumed run: kernel attributes are set by an eager launch, not in
                     self.engine.multi_forward_backward(self._image, self._label)    # a capture; it writes only what the step
                     self._warm = True                                                 # overwrites)
@@ -194,17 +192,13 @@ class RPOMulti(EvalMixin):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._enqueue(self._image, self._label)
-                self._graph = (g, self._graph_key())   # (capture does not execute: the replay below is this step)
+                self._graph = (g, key)                 # (capture does not execute: the replay below is this step)
                 self.captures += 1
             self._graph[0].replay()
         self._steps += 1
         self._eval_member = None
         self.engine.text_f_version = -1
         return self.engine.m_loss
-
-    def _graph_key(self):
-        """What a captured step has baked in besides addresses: the learning rate (a kernel argument of rpo_sgd_step)."""
-        return self.lr if self._opt is None else 0      # (device data with an OptimState: one capture)
 
     def parse_batch_train(self, batches: Sequence[dict]):
         """S Dassl-style batches {"img": float [B, 3, H, W], "label": [B]} -> one member-major device batch."""
@@ -235,8 +229,7 @@ class RPOMulti(EvalMixin):
     def update_lr(self) -> None:
         self.epoch += 1
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-        if self._opt is not None:
-            self._opt.set_epoch(self.epoch)
+        self._opt.set_epoch(self.epoch)
 
     def _loop_advance(self) -> None:
         if (self.batch_idx + 1) == self.num_batches:
@@ -365,15 +358,12 @@ class RPOMulti(EvalMixin):
         if len(directories) != self.n_runs:
             raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
         epoch = self.epoch if epoch is None else epoch
-        p, m = self.engine.m_params.detach().cpu(), self.engine.m_mom.detach().cpu()
-        out = []
+        p = self.engine.m_params.detach().cpu()
+        n, shapes, out = p.shape[1], [(self.cfg.K, self.cfg.d_t), (self.cfg.K, self.cfg.d_v)], []
         for s, d in enumerate(directories):
-            ck = member_checkpoint(p[s], m[s], self.cfg, epoch, self.optim_cfg, self.lr, self._steps,
-                                   None if val_results is None else val_results[s])
-            if self._opt is not None:
-                n = p.shape[1]
-                ck["optimizer"] = self._opt.state_dict(_prompt_shapes(ck["state_dict"]), lr=self.lr,
-                                                       gather=lambda row, s=s: row[s * n:(s + 1) * n])
+            entry = self._opt.state_dict(shapes, lr=self.lr, steps=self._steps, gather=lambda row: row[s * n:(s + 1) * n])
+            ck = member_checkpoint(p[s], None, self.cfg, epoch, self.optim_cfg, self.lr, self._steps,
+                                   None if val_results is None else val_results[s], entry)
             out.append(write_checkpoint(d, ck, epoch, is_best))
         return out
 
@@ -383,33 +373,27 @@ class RPOMulti(EvalMixin):
         if len(directories) != self.n_runs:
             raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
         got = [read_member_checkpoint(d, epoch, self.cfg) for d in directories]
-        epochs = [int(ck.get("epoch", 0)) for _, _, ck in got]
+        epochs = [int(ck.get("epoch", 0)) for _, ck in got]
         if any(e != epochs[0] for e in epochs):
             raise ValueError(f"RPOMulti.load_model: the checkpoints are of epochs {epochs}; the members share one schedule")
-        moms = [m for _, m, _ in got]
-        if any(m is None for m in moms) != all(m is None for m in moms):
-            raise ValueError("RPOMulti.load_model: some checkpoints carry momentum and some do not (one first-step flag "
-                             "covers every member)")
-        eng = self.engine
-        if self._opt is not None:
-            n, shapes = eng.m_params.shape[1], [(self.cfg.K, self.cfg.d_t), (self.cfg.K, self.cfg.d_v)]
-            have = [_optim.rows_from_state_dict(self.optim_cfg, ck.get("optimizer"), shapes) is not None for _, _, ck in got]
-            if any(have) != all(have):
-                raise ValueError("RPOMulti.load_model: some checkpoints carry optimiser state and some do not (one step "
-                                 "counter covers every member)")
-            for s, (_, _, ck) in enumerate(got):
-                self._opt.load_state_dict(ck.get("optimizer"), shapes, steps=ck.get("steps", 1),
-                                          scatter=lambda d, r, s=s: d[s * n:(s + 1) * n].copy_(r))
-            if all(have):
-                self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
-            moms = [None]
-        eng.m_params.copy_(torch.stack([p for p, _, _ in got]))
-        if moms[0] is not None:
-            eng.m_mom.copy_(torch.stack(moms))
-            self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
+        eng, n = self.engine, self.engine.m_params.shape[1]
+        shapes = [(self.cfg.K, self.cfg.d_t), (self.cfg.K, self.cfg.d_v)]
+        self._load_states(got, lambda s: dict(param_shapes=shapes, scatter=lambda d, r: d[s * n:(s + 1) * n].copy_(r)))
+        eng.m_params.copy_(torch.stack([p for p, _ in got]))
         self.epoch = epochs[0]
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-        if self._opt is not None:
-            self._opt.set_epoch(self.epoch)
+        self._opt.set_epoch(self.epoch)
         self._eval_member = None
         eng.text_f_version = -1
+
+    def _load_states(self, got, member_kw) -> None:
+        """The members' optimiser states from their files (`member_kw(s)`: where member s's state goes): every file has
+        one -- then `_steps` is the files' -- or none has; a mix is refused."""
+        have = [self._opt.load_state_dict(ck.get("optimizer"), steps=ck.get("steps", 1), **member_kw(s))
+                for s, (_, ck) in enumerate(got)]
+        if any(have) != all(have):
+            raise ValueError(f"{type(self).__name__}.load_model: some checkpoints carry "
+                             + ("optimiser state and some do not" + self._one_counter if self._opt.table_driven else
+                                "momentum and some do not (one first-step flag covers every member)"))
+        if all(have):
+            self._steps = max(1, max(int(ck.get("steps", 1)) for _, ck in got))

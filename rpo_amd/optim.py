@@ -1,11 +1,14 @@
-"""Dassl's optimisers beyond plain SGD on the HIP engine: the host side of rpo_optim_step_sets.
+"""Every trainer's optimiser on the HIP engine: the host side of rpo_sgd_step* and rpo_optim_step_sets.
 
-``OptimState`` owns what the kernel reads from the device -- `kind` [S], `hyper` [S, 8], `step` [S] -- and the fp32 state
-rows of S sets, and offers the four operations a trainer needs: ``step``, ``set_epoch``, ``state_dict``,
-``load_state_dict``.  A trainer builds one only when its config is NOT plain SGD (``is_plain_sgd``); plain SGD keeps
-calling rpo_sgd_step* exactly as before.
+A trainer holds ONE optimiser object, built by ``make_optimizer`` from its configs: ``PlainSGD`` when every set's config is
+plain SGD (``is_plain_sgd``) -- it issues rpo_sgd_step / rpo_sgd_step_guarded / rpo_sgd_step_sets on the trainer's own
+momentum buffer -- and ``OptimState`` otherwise, which owns what rpo_optim_step_sets reads from the device -- `kind` [S],
+`hyper` [S, 8], `step` [S] -- and the fp32 state rows of S sets.  Both offer the same surface, and nothing outside this
+module knows which kernel steps a buffer: ``step``, ``set_epoch``, ``graph_key`` (what a captured step has baked in
+besides addresses), ``splittable`` (whether ``step`` can update one part of the flat buffer), ``state_dict``,
+``load_state_dict``, and ``table_driven`` (the rate and the step count are device data).
 
-The module-level functions are pure host code (no device): the hyper table, torch.optim's state-dict layout per kind in
+The module-level functions are pure host code (no device): the hyper tables, torch.optim's state-dict layout per kind in
 both directions, and the refusals.  Dassl is not installed here: the names, the defaults and what `OPTIM.NAME` selects are
 Dassl's `build_optimizer` as its source is remembered (dassl/optim/optimizer.py); the update rules are the installed
 torch's.
@@ -64,6 +67,14 @@ def hyper_table(optims: Sequence, epoch: int, grad_scale: float = 1.0) -> torch.
     """float32 [S, 8] of the members' settings at `epoch` (each member's own schedule)."""
     from .trainer import lr_at_epoch
     return torch.tensor([hyper_row(oc, lr_at_epoch(oc, epoch), grad_scale) for oc in optims],
+                        dtype=torch.float64).to(torch.float32)
+
+
+def sgd_hyper_table(optims: Sequence, epoch: int, grad_scale: float = 1.0) -> torch.Tensor:
+    """float32 [S, 4] for rpo_sgd_step_sets: (lr_at_epoch(optim_s, epoch), momentum, weight decay, grad_scale) per member,
+    rounded to float32 as the scalar arguments of rpo_sgd_step are."""
+    from .trainer import lr_at_epoch
+    return torch.tensor([[lr_at_epoch(oc, epoch), oc.momentum, oc.weight_decay, grad_scale] for oc in optims],
                         dtype=torch.float64).to(torch.float32)
 
 
@@ -141,6 +152,8 @@ def rows_from_state_dict(oc, opt_state: Optional[dict], param_shapes: Sequence[t
             for r, nm in zip(rows, names):
                 if nm == "momentum_buffer" and name == "rmsprop" and nm not in e:
                     t = torch.zeros(tuple(shape))
+                elif e[nm] is None:              # torch.optim.SGD with momentum 0 writes `momentum_buffer: None`
+                    return None
                 else:
                     t = torch.as_tensor(e[nm])
                 if tuple(t.shape) != tuple(shape):
@@ -154,11 +167,19 @@ def rows_from_state_dict(oc, opt_state: Optional[dict], param_shapes: Sequence[t
     return [torch.cat(r) for r in rows], step
 
 
-class OptimState:
-    """The device tables and state rows of S sets for rpo_optim_step_sets.
+def state_shapes(oc, opt_state: Optional[dict]) -> List[tuple]:
+    """The shapes of the kind's first state tensor (SGD: `momentum_buffer`) per parameter of a torch-layout `optimizer`
+    entry, as far as the file has them: what a refusal names when `load_state_dict` finds no match."""
+    st, nm = (opt_state or {}).get("state") or {}, state_names(oc)[0]
+    return [tuple(torch.as_tensor(st[i][nm]).shape) for i in sorted(st) if st[i].get(nm) is not None]
 
-    optims: one config per set.  `s0` may be given (a trainer's existing momentum buffer, viewed [S, stride]): SGD sets
-    then keep their momentum where the plain path keeps it.  `used` int32 [S, 2] (device) or None."""
+
+class _Sets:
+    """What both optimisers share: the configs and the geometry of S sets, the first state row `s0` [S, stride], and
+    torch's state-dict layout in both directions over the state rows `_state()` (each [S, stride])."""
+
+    splittable = False             # `step(..., part=slice)` can update one part of the flat buffer
+    table_driven = False           # the rate and the step count are device data: `graph_key()` is constant
 
     def __init__(self, optims: Sequence, set_stride: int, seg0: int, seg1: int, device, s0: Optional[torch.Tensor] = None,
                  used: Optional[torch.Tensor] = None, grad_scale: float = 1.0):
@@ -167,16 +188,122 @@ class OptimState:
         self.optims, self.S = list(optims), len(optims)
         self.stride, self.seg0, self.seg1 = int(set_stride), int(seg0), int(seg1)
         self.device, self.grad_scale, self.used = torch.device(device), float(grad_scale), used
+        self.s0 = torch.zeros(self.S, self.stride, device=self.device) if s0 is None else s0.view(self.S, self.stride)
+        self.epoch = None
+
+    def state_dict(self, param_shapes: Sequence[tuple], s: int = 0, lr: Optional[float] = None,
+                   gather: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, steps: Optional[int] = None) -> dict:
+        """Set s's `optimizer` entry in torch's own layout.  `gather`: row -> the flat vector the shapes slice (a sweep
+        member's own columns); default: the leading sum(numel) floats of the row.  `steps`: the trainer's count of updates,
+        which a plain-SGD set's file carries (the kernels of plain SGD keep no device counter)."""
+        from .trainer import lr_at_epoch
+        oc = self.optims[s]
+        n = sum(int(np.prod(sh)) for sh in param_shapes)
+        rows = [r[s].detach().cpu() for r in self._state()[:len(state_names(oc))]]
+        rows = [gather(r) if gather is not None else r[:n] for r in rows]
+        lr = lr_at_epoch(oc, self.epoch or 0) if lr is None else lr
+        return torch_state_dict(oc, lr, rows, self._count(s, steps), param_shapes)
+
+    def load_state_dict(self, opt_state: Optional[dict], param_shapes: Sequence[tuple], s: int = 0,
+                        scatter: Optional[Callable[[torch.Tensor, torch.Tensor], None]] = None,
+                        steps: Optional[int] = None) -> bool:
+        """Restores set s's state rows (and device counter) from a torch-layout `optimizer` entry; False (nothing touched)
+        when the entry has no state matching this kind and these shapes.  `steps`: the counter for kinds whose state
+        carries none (SGD); `scatter(dst_row, flat)`: writes a file's flat vector into the set's row (default: its leading floats)."""
+        got = rows_from_state_dict(self.optims[s], opt_state, param_shapes)
+        if got is None:
+            return False
+        rows, step = got
+        for dst, r in zip(self._state(), rows):
+            if scatter is not None:
+                scatter(dst[s], r)
+            else:
+                dst[s, :r.numel()].copy_(r)
+        self._restore_count(s, step, steps)
+        return True
+
+
+class PlainSGD(_Sets):
+    """torch.optim.SGD with dampening 0 and no Nesterov on the trainer's own momentum buffer `s0`: rpo_sgd_step over the
+    flat buffer (or one `part` of it), rpo_sgd_step_guarded when the step brings a `found_inf`, and -- with `used`, the
+    sets of a sweep -- rpo_sgd_step_sets.  The first two take the rate as a kernel argument (`graph_key()` is the rate);
+    the sets form reads (lr, momentum, weight decay, grad_scale) from a device table [S, 4]: every epoch's table is
+    uploaded once, and a new epoch's rates are one device-side [S, 4] copy on the current stream."""
+
+    def __init__(self, optims: Sequence, *args, **kw):
+        super().__init__(optims, *args, **kw)
+        self.splittable = self.used is None
+        self.hyper = None
+        if self.used is not None:
+            self.hyper = torch.zeros(self.S, 4, dtype=torch.float32, device=self.device)
+            self._hyper_epochs = torch.stack([sgd_hyper_table(optims, e, self.grad_scale)
+                                              for e in range(optims[0].max_epoch + 1)]).to(self.device)
+        elif self.S != 1:
+            raise ValueError("PlainSGD: sets with their own configs need `used` (the kernel-argument forms step one set)")
+        self.set_epoch(0)
+
+    def _state(self):
+        return (self.s0,)
+
+    def _count(self, s: int, steps: Optional[int]) -> int:
+        return int(steps or 0)
+
+    def _restore_count(self, s: int, step: int, steps: Optional[int]) -> None:
+        pass                                            # (the caller keeps the count: it is `first_step` of its next call)
+
+    def set_epoch(self, epoch: int) -> None:
+        if self.epoch == epoch:
+            return
+        if self.hyper is None:
+            from .trainer import lr_at_epoch
+            self.lr = lr_at_epoch(self.optims[0], epoch)
+        elif 0 <= epoch < self._hyper_epochs.shape[0]:
+            self.hyper.copy_(self._hyper_epochs[epoch])
+        else:                                           # (past the schedule's end: the formula still gives a rate)
+            self.hyper.copy_(sgd_hyper_table(self.optims, epoch, self.grad_scale))
+        self.epoch = epoch
+
+    def graph_key(self):
+        return 0 if self.hyper is not None else self.lr
+
+    def step(self, p: torch.Tensor, g: torch.Tensor, found_inf: Optional[torch.Tensor] = None, first_step: bool = False,
+             part: Optional[slice] = None) -> None:
+        from . import ops
+        oc = self.optims[0]
+        assert part is None or (self.splittable and found_inf is None), "only the ungated elementwise step takes a part"
+        if self.hyper is not None:
+            ops.sgd_step_sets(p, g, self.s0, self.hyper, self.seg0, self.seg1, first_step=first_step, used=self.used,
+                              found_inf=found_inf)
+        elif found_inf is not None:
+            ops.sgd_step_guarded(p.view(-1), g.view(-1), self.s0.view(-1), self.lr, oc.momentum, oc.weight_decay,
+                                 self.grad_scale, first_step=first_step, found_inf=found_inf)
+        else:
+            sl = slice(None) if part is None else part
+            ops.sgd_step(p.view(-1)[sl], g.view(-1)[sl], self.s0.view(-1)[sl], self.lr, oc.momentum, oc.weight_decay,
+                         self.grad_scale, first_step=first_step)
+
+
+class OptimState(_Sets):
+    """The device tables and state rows of S sets for rpo_optim_step_sets.
+
+    optims: one config per set.  `s0` may be given (a trainer's existing momentum buffer, viewed [S, stride]): SGD sets
+    then keep their momentum where the plain path keeps it.  `used` int32 [S, 2] (device) or None."""
+
+    table_driven = True
+
+    def __init__(self, optims: Sequence, *args, **kw):
+        super().__init__(optims, *args, **kw)
         S, dev = self.S, self.device
-        self.s0 = torch.zeros(S, self.stride, device=dev) if s0 is None else s0.view(S, self.stride)
         self.s1 = torch.zeros(S, self.stride, device=dev)
         self.needs_s2 = any(oc.name == "amsgrad" for oc in optims)
         self.s2 = torch.zeros(S, self.stride, device=dev) if self.needs_s2 else None
         self.kind = kind_table(optims).to(dev)
         self.hyper = torch.zeros(S, 8, dtype=torch.float32, device=dev)
         self.counter = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.epoch = None
         self.set_epoch(0)
+
+    def _state(self):
+        return (self.s0, self.s1, self.s2)
 
     def set_epoch(self, epoch: int) -> None:
         """The rates of `epoch` into the device table: one small H2D copy on the current stream (nothing when the table
@@ -185,47 +312,37 @@ class OptimState:
             self.hyper.copy_(hyper_table(self.optims, epoch, self.grad_scale))
             self.epoch = epoch
 
-    def step(self, p: torch.Tensor, g: torch.Tensor, found_inf: Optional[torch.Tensor] = None) -> None:
+    def graph_key(self):
+        return 0
+
+    def step(self, p: torch.Tensor, g: torch.Tensor, found_inf: Optional[torch.Tensor] = None, first_step: bool = False,
+             part: Optional[slice] = None) -> None:
+        """One launch steps every set and advances its counter (`first_step` is the kernel's own business; no `part`)."""
         from . import ops
+        assert part is None, "one launch steps the set and advances its counter once"
         S = self.S
         ops.optim_step_sets(p.view(S, self.stride), g.view(S, self.stride), self.s0, self.s1, self.s2, self.kind, self.hyper,
                             self.counter, self.seg0, self.seg1, used=self.used,
                             found_inf=None if found_inf is None else found_inf.view(S, 2), needs_s2=self.needs_s2)
 
-    def _rows(self, s: int):
-        return [r[s].detach().cpu() for r in (self.s0, self.s1, self.s2)[:len(state_names(self.optims[s]))]]
-
     def steps(self) -> List[int]:
         """Per set, the number of updates applied so far (one D2H read)."""
         return [int(v) for v in self.counter.tolist()]
 
-    def state_dict(self, param_shapes: Sequence[tuple], s: int = 0, lr: Optional[float] = None,
-                   gather: Optional[Callable[[torch.Tensor], torch.Tensor]] = None) -> dict:
-        """Set s's `optimizer` entry in torch's own layout.  `gather`: row -> the flat vector the shapes slice (a sweep
-        member's own columns); default: the leading sum(numel) floats of the row."""
-        from .trainer import lr_at_epoch
-        oc = self.optims[s]
-        n = sum(int(np.prod(sh)) for sh in param_shapes)
-        rows = [gather(r) if gather is not None else r[:n] for r in self._rows(s)]
-        lr = lr_at_epoch(oc, self.epoch or 0) if lr is None else lr
-        return torch_state_dict(oc, lr, rows, self.steps()[s], param_shapes)
+    def _count(self, s: int, steps: Optional[int]) -> int:
+        if steps is not None and is_plain_sgd(self.optims[s]):       # (a sweep's plain-SGD member beside other kinds)
+            return int(steps)
+        return self.steps()[s]
 
-    def load_state_dict(self, opt_state: Optional[dict], param_shapes: Sequence[tuple], s: int = 0,
-                        scatter: Optional[Callable[[torch.Tensor, torch.Tensor], None]] = None,
-                        steps: Optional[int] = None) -> bool:
-        """Restores set s's state rows and device counter from a torch-layout `optimizer` entry; False (nothing touched)
-        when the entry has no state matching this kind and these shapes.  `steps`: the counter for kinds whose state
-        carries none (SGD); `scatter(dst_row, flat)`: writes a file's flat vector into the set's row (default: its leading floats)."""
-        got = rows_from_state_dict(self.optims[s], opt_state, param_shapes)
-        if got is None:
-            return False
-        rows, step = got
+    def _restore_count(self, s: int, step: int, steps: Optional[int]) -> None:
         if self.optims[s].name == "sgd":
             step = max(1, int(steps if steps is not None else 1))
-        for dst, r in zip((self.s0, self.s1, self.s2), rows):
-            if scatter is not None:
-                scatter(dst[s], r)
-            else:
-                dst[s, :r.numel()].copy_(r)
         self.counter[s:s + 1].copy_(torch.tensor([step], dtype=torch.int32))
-        return True
+
+
+def make_optimizer(optims: Sequence, set_stride: int, seg0: int, seg1: int, device, s0: Optional[torch.Tensor] = None,
+                   used: Optional[torch.Tensor] = None, grad_scale: float = 1.0):
+    """The trainer's optimiser: `PlainSGD` when every set's config is plain SGD, else `OptimState` for all of them (a sweep
+    with one other member is table-driven as a whole; its plain-SGD members get the bits of rpo_sgd_step_sets)."""
+    cls = PlainSGD if all(is_plain_sgd(oc) for oc in optims) else OptimState
+    return cls(optims, set_stride, seg0, seg1, device, s0=s0, used=used, grad_scale=grad_scale)

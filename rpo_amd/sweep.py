@@ -9,8 +9,10 @@ first K_s of the engine's K = max K_s rows IS a standalone K_s run as soon as th
 (rpo_head_fwd_bwd_grouped_k) and the optimiser and the checkpoint see those rows only (rpo_sgd_step_sets, the gather /
 scatter below).  The other rows ("inert") are zero, get zero gradients and ride along: a member costs what a K member costs.
 
-The optimiser settings live in a device table [S, 4] = (lr, momentum, weight decay, grad_scale): a new epoch's learning
-rates are one small copy on the step's stream, and the step's HIP graph is captured ONCE (`captures`).
+The optimiser settings live in a device table [S, 4] = (lr, momentum, weight decay, grad_scale) that the members' optimiser
+owns (`optim.PlainSGD` with `used`, `optim.sgd_hyper_table`; [S, 8] in `optim.OptimState` as soon as one member is not plain
+SGD): a new epoch's learning rates are one small copy on the step's stream, and the step's HIP graph is captured ONCE
+(`captures`).
 
 The surface is ``RPOMulti``'s, whose step, epoch loop and shared evaluation this class inherits; evaluation of one member
 goes through the shared prompt-row pass with that member's K, and a member's checkpoint is the file a standalone
@@ -25,10 +27,10 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops, optim as _optim
+from . import optim as _optim
 from .custom_clip import init_prompts, refuse_rn
 from .multi import RPOMulti, member_checkpoint, read_member_checkpoint
-from .trainer import OptimConfig, _prompt_shapes, lr_at_epoch, write_checkpoint
+from .trainer import OptimConfig, lr_at_epoch, write_checkpoint
 
 
 def member_row_to_flat(row: torch.Tensor, K: int, K_s: int, d_t: int, d_v: int) -> torch.Tensor:
@@ -52,13 +54,6 @@ def flat_to_member_row(flat: torch.Tensor, K: int, K_s: int, d_t: int, d_v: int)
 def used_table(member_K: Sequence[int], d_t: int, d_v: int) -> torch.Tensor:
     """int32 [S, 2]: the leading floats of the text / img segment of each member's row that are its own (rpo_sgd_step_sets)."""
     return torch.tensor([[k * d_t, k * d_v] for k in member_K], dtype=torch.int32)
-
-
-def hyper_table(optims: Sequence[OptimConfig], epoch: int, grad_scale: float = 1.0) -> torch.Tensor:
-    """float32 [S, 4]: (lr_at_epoch(optim_s, epoch), momentum, weight decay, grad_scale) per member, rounded to float32 as the
-    scalar arguments of rpo_sgd_step are."""
-    return torch.tensor([[lr_at_epoch(oc, epoch), oc.momentum, oc.weight_decay, grad_scale] for oc in optims],
-                        dtype=torch.float64).to(torch.float32)
 
 
 def sweep_prompts(state_dict: Dict[str, np.ndarray], members: Sequence[dict], d_t: int, d_v: int) -> List[tuple]:
@@ -87,6 +82,8 @@ def _shared(members: Sequence[dict], key: str, default, what: str):
 
 
 class RPOSweep(RPOMulti):
+    _one_counter = ""
+
     def __init__(self, cfg, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
                  members: Sequence[dict] = (), batch_size: int = 4, device: str | torch.device = "cuda:0",
                  act_dtype: torch.dtype = torch.bfloat16, num_batches: int = 1, use_graph: bool = True, amp: bool = False,
@@ -129,25 +126,22 @@ class RPOSweep(RPOMulti):
         self.member_cfgs = [dataclasses.replace(cfg, K=k) for k in self.member_K]
         cfg = dataclasses.replace(cfg, K=max(self.member_K))           # the engine's K: it checks its own limits
         self.lr = [lr_at_epoch(oc, 0) for oc in self.optim_cfgs]
-        self._hyper_epoch = None                                       # the epoch whose rates the device table holds
         self._build(cfg, state_dict, tokens, S, B, sweep_prompts(state_dict, members, cfg.d_t, cfg.d_v), device, act_dtype,
                     num_batches, use_graph, member_K=self.member_K)
         with torch.cuda.device(self.device):
-            self._hyper = torch.zeros(S, 4, dtype=torch.float32, device=self.device)
-            # every epoch's table, uploaded once: a new epoch's rates are then one device-side [S, 4] copy on the step's stream
-            self._hyper_epochs = torch.stack([hyper_table(self.optim_cfgs, e)
-                                              for e in range(self.optim_cfgs[0].max_epoch + 1)]).to(self.device)
             self._used = used_table(self.member_K, cfg.d_t, cfg.d_v).to(self.device)
             self._found_inf = torch.zeros(S, 2, dtype=torch.int32, device=self.device) if self.amp else None
-            # a member that is not plain SGD: every member goes through rpo_optim_step_sets, `kind` and `hyper` per member
-            # (plain-SGD members keep their momentum in m_mom and get the bits of rpo_sgd_step_sets)
-            if not all(_optim.is_plain_sgd(oc) for oc in self.optim_cfgs):
-                self._opt = _optim.OptimState(self.optim_cfgs, self.engine.m_params.stride(0), cfg.K * cfg.d_t,
+            # one set per member: rpo_sgd_step_sets, or -- a member that is not plain SGD -- rpo_optim_step_sets for every
+            # member (plain-SGD members keep their momentum in m_mom and get the bits of rpo_sgd_step_sets)
+            self._opt = _optim.make_optimizer(self.optim_cfgs, self.engine.m_params.stride(0), cfg.K * cfg.d_t,
                                               cfg.K * cfg.d_v, self.device, s0=self.engine.m_mom, used=self._used)
 
     # ------------------------------------------------------------------ members' state
     def _dims(self, s: int):
         return self.cfg.K, self.member_K[s], self.cfg.d_t, self.cfg.d_v
+
+    def _shapes(self, s: int):
+        return [(self.member_K[s], self.cfg.d_t), (self.member_K[s], self.cfg.d_v)]
 
     def set_prompts(self, prompts: Sequence[tuple]) -> None:
         """Member s's (text_prompt [K_s, d_t], img_prompt [K_s, d_v]) into the leading rows of its row; the inert rows zero."""
@@ -164,36 +158,7 @@ class RPOSweep(RPOMulti):
             return [0] * self.n_runs
         return [int(v) for v in self._found_inf[:, 1].tolist()]
 
-    # ------------------------------------------------------------------ the step
-    def _graph_key(self):
-        return 0                                        # the rates are device data: one capture serves every epoch
-
-    def _refresh_hyper(self) -> None:
-        if self._opt is not None:
-            self._opt.set_epoch(self.epoch)
-        elif self._hyper_epoch != self.epoch:
-            if 0 <= self.epoch < self._hyper_epochs.shape[0]:
-                self._hyper.copy_(self._hyper_epochs[self.epoch])
-            else:                                       # (past the schedule's end: the formula still gives a rate)
-                self._hyper.copy_(hyper_table(self.optim_cfgs, self.epoch))
-            self._hyper_epoch = self.epoch
-
-    def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
-        eng, cfg = self.engine, self.cfg
-        eng.multi_forward_backward(image, label)
-        if self._opt is not None:
-            self._opt.step(eng.m_params, eng.m_grads, self._found_inf)
-            return
-        ops.sgd_step_sets(eng.m_params, eng.m_grads, eng.m_mom, self._hyper, cfg.K * cfg.d_t, cfg.K * cfg.d_v,
-                          first_step=(self._steps == 0), used=self._used, found_inf=self._found_inf)
-
-    def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-        """`RPOMulti.step_async` with every member's own rate: the table is refreshed (one [S, 4] copy on the current
-        stream, in front of the step) when the epoch has advanced; the graph is captured once."""
-        assert torch.cuda.current_device() == self.device.index, "set the trainer's device current (torch.cuda.set_device)"
-        self._refresh_hyper()
-        return super().step_async(image, label)
-
+    # ------------------------------------------------------------------ the step: `RPOMulti`'s (the rates are device data)
     def update_lr(self) -> None:
         self.epoch += 1
         self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
@@ -249,15 +214,14 @@ class RPOSweep(RPOMulti):
         if len(directories) != self.n_runs:
             raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
         epoch = self.epoch if epoch is None else epoch
-        p, m = self.engine.m_params.detach().cpu(), self.engine.m_mom.detach().cpu()
+        p = self.engine.m_params.detach().cpu()
         out = []
         for s, d in enumerate(directories):
-            ck = member_checkpoint(member_row_to_flat(p[s], *self._dims(s)), member_row_to_flat(m[s], *self._dims(s)),
-                                   self.member_cfgs[s], epoch, self.optim_cfgs[s], self.lr[s], self._steps,
-                                   None if val_results is None else val_results[s])
-            if self._opt is not None and not _optim.is_plain_sgd(self.optim_cfgs[s]):
-                ck["optimizer"] = self._opt.state_dict(_prompt_shapes(ck["state_dict"]), s=s, lr=self.lr[s],
-                                                       gather=lambda row, s=s: member_row_to_flat(row, *self._dims(s)))
+            entry = self._opt.state_dict(self._shapes(s), s=s, lr=self.lr[s], steps=self._steps,
+                                         gather=lambda row: member_row_to_flat(row, *self._dims(s)))
+            ck = member_checkpoint(member_row_to_flat(p[s], *self._dims(s)), None, self.member_cfgs[s], epoch,
+                                   self.optim_cfgs[s], self.lr[s], self._steps, None if val_results is None else val_results[s],
+                                   entry)
             out.append(write_checkpoint(d, ck, epoch, is_best))
         return out
 
@@ -267,37 +231,16 @@ class RPOSweep(RPOMulti):
         if len(directories) != self.n_runs:
             raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
         got = [read_member_checkpoint(d, epoch, self.member_cfgs[s]) for s, d in enumerate(directories)]
-        epochs = [int(ck.get("epoch", 0)) for _, _, ck in got]
+        epochs = [int(ck.get("epoch", 0)) for _, ck in got]
         if any(e != epochs[0] for e in epochs):
             raise ValueError(f"RPOSweep.load_model: the checkpoints are of epochs {epochs}; one loop runs all members")
-        moms = [m for _, m, _ in got]
-        if self._opt is not None:
-            # per member its own kind's state; a plain-SGD member's momentum is `moms[s]` as before
-            shapes = [[(k, self.cfg.d_t), (k, self.cfg.d_v)] for k in self.member_K]
-            plain = [_optim.is_plain_sgd(oc) for oc in self.optim_cfgs]
-            have = [(moms[s] is not None) if plain[s] else
-                    (_optim.rows_from_state_dict(self.optim_cfgs[s], got[s][2].get("optimizer"), shapes[s]) is not None)
-                    for s in range(self.n_runs)]
-            if any(have) != all(have):
-                raise ValueError("RPOSweep.load_model: some checkpoints carry optimiser state and some do not")
-            if all(have):
-                for s, (_, _, ck) in enumerate(got):
-                    self._opt.load_state_dict(ck.get("optimizer"), shapes[s], s=s, steps=ck.get("steps", 1),
-                                              scatter=lambda d, r, s=s: d.copy_(flat_to_member_row(r, *self._dims(s))))
-                self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
-            self._opt.epoch = None
-            moms = [None] * self.n_runs
-        if any(m is None for m in moms) != all(m is None for m in moms):
-            raise ValueError("RPOSweep.load_model: some checkpoints carry momentum and some do not (one first-step flag "
-                             "covers every member)")
+        self._load_states(got, lambda s: dict(param_shapes=self._shapes(s), s=s,
+                                              scatter=lambda d, r: d.copy_(flat_to_member_row(r, *self._dims(s)))))
         eng = self.engine
-        eng.m_params.copy_(torch.stack([flat_to_member_row(p, *self._dims(s)) for s, (p, _, _) in enumerate(got)]))
-        if moms[0] is not None:
-            eng.m_mom.copy_(torch.stack([flat_to_member_row(m, *self._dims(s)) for s, m in enumerate(moms)]))
-            self._steps = max(1, max(int(ck.get("steps", 1)) for _, _, ck in got))
+        eng.m_params.copy_(torch.stack([flat_to_member_row(p, *self._dims(s)) for s, (p, _) in enumerate(got)]))
         self.epoch = epochs[0]
         self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        self._hyper_epoch = None
-        if getattr(self, "_found_inf", None) is not None:       # the skip counts are the resumed run's own
+        self._opt.set_epoch(self.epoch)
+        if self._found_inf is not None:                         # the skip counts are the resumed run's own
             self._found_inf.zero_()
         eng.text_f_version = -1

@@ -21,7 +21,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops, optim as _optim
+from . import optim as _optim
 from .config import RPOConfig
 from .custom_clip import CustomCLIP
 from .dist import GradSync
@@ -84,7 +84,6 @@ def lr_at_epoch(oc: OptimConfig, epoch: int) -> float:
 
 class RPO(LoopMixin):
     _takes_next_image = True         # run_epoch names the next batch: its patch embedding runs under this step
-    _opt = None                      # optim.OptimState: every optimiser but plain SGD
     _takes_frozen = True             # test(..., frozen=...): the prompt-row pass alone on a set's cached frozen K / V
 
     def __init__(self, cfg: RPOConfig, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
@@ -99,7 +98,6 @@ class RPO(LoopMixin):
         self.amp = amp
         self.optim_cfg = optim or OptimConfig()
         _optim.validate(self.optim_cfg)
-        self._opt = None                             # optim.OptimState: every optimiser but plain SGD
         # default: joins (or creates) the process group when launched under torchrun; a lone process stays local.
         # Built BEFORE the device is resolved: under a launcher it makes this rank's GPU the current device, and an
         # index-less "cuda" then means that GPU on every rank (not cuda:0 eight times).
@@ -142,9 +140,8 @@ class RPO(LoopMixin):
         self._label = torch.zeros(self.batch_size, dtype=torch.int64, device=self.device)
         if self.sync.enabled:                       # identical prompts on every rank
             self.sync.broadcast(self.engine.params)
-        if not _optim.is_plain_sgd(self.optim_cfg):
-            n = self.engine.params.numel()
-            self._opt = _optim.OptimState([self.optim_cfg], n, n, 0, self.device, s0=self.engine.mom,
+        n = self.engine.params.numel()               # the flat [text | img] buffer as one set
+        self._opt = _optim.make_optimizer([self.optim_cfg], n, n, 0, self.device, s0=self.engine.mom,
                                           grad_scale=self.sync.grad_scale)
 
     def transform(self, is_train: bool):
@@ -268,7 +265,7 @@ class RPO(LoopMixin):
         small = self.batch_size * (self.cfg.n_frozen + self.cfg.K) < 2048
         # (nor with a table-driven optimiser: one launch steps the set and advances its counter once)
         self._early_text = ((want == "1" or (want is None and small)) and not self.amp and not self._joint_bwd
-                            and self._opt is None
+                            and self._opt.splittable
                             and self._bwd_parts == 1 and (not self.sync.enabled or self._split_collective))
         self._text_fwd_for = -1
         # ONE GRAPH PER STEP (round 6, RPO_ONE_GRAPH=1): text fwd || image fwd -> head -> text bwd (+ its all-reduce) ||
@@ -400,11 +397,7 @@ class RPO(LoopMixin):
             summary = {"loss": float(loss.item())}              # D2H sync, as the reference (:311)
             if self.detect_anomaly:
                 self.check_finite()
-        if (self.batch_idx + 1) == self.num_batches:
-            self.update_lr()
-            self.batch_idx = 0
-        else:
-            self.batch_idx += 1
+        self._loop_advance()
         return summary
 
     def step_async(self, image: torch.Tensor, label: torch.Tensor, next_image: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -416,8 +409,7 @@ class RPO(LoopMixin):
         eng, oc = self.engine, self.optim_cfg
         assert torch.cuda.current_device() == self.device.index, "set the trainer's device current (torch.cuda.set_device)"
         assert image.shape[0] == self.batch_size, "graph path needs the configured batch size"
-        if self._opt is not None:
-            self._opt.set_epoch(self.epoch)
+        self._opt.set_epoch(self.epoch)
         tag = (image.data_ptr(), image._version)
         pending = self.use_graph and self._graph is not None and self._patch_tag is not None
         patch_ready = pending and self._patch_tag == tag
@@ -455,7 +447,7 @@ class RPO(LoopMixin):
         tail = None
         if self.use_graph and getattr(self, "_graph_collectives", False) and self._steps > 0:
             # the rate is a kernel argument of rpo_sgd_step: one small graph per rate (device data with an OptimState)
-            key = (self.lr if getattr(self, "_opt", None) is None else None, which)
+            key = (self._opt.graph_key(), which)
             tail = self._tail_graphs.get(key)
             if tail is None:
                 try:
@@ -476,36 +468,23 @@ class RPO(LoopMixin):
             self._tail(which)
 
     def _tail(self, which: str = "all") -> None:
-        """What follows the backward chains: the all-reduce of what is still local, then the fused SGD step -- over the
+        """What follows the backward chains: the all-reduce of what is still local, then the optimiser's step -- over the
         whole flat buffer [text | img], or over one half of it (early text: the text half on the side stream behind the
         text backward, whose all-reduce _replay has already issued; the image half on the main stream)."""
-        eng, oc = self.engine, self.optim_cfg
+        eng = self.engine
         nt = eng.g_text_flat.numel()
         if which == "text":
-            sl = slice(0, nt)
+            part = slice(0, nt)
         elif which == "img":
-            sl = slice(nt, None)
+            part = slice(nt, None)
             self.sync.all_reduce_sum(eng.g_img_flat)
         else:
-            sl = slice(None)
+            part = None
             if self.use_graph and self._split_collective and not self._joint_bwd:
                 self.sync.all_reduce_sum(eng.g_img_flat)        # (g_text went out behind the text backward, _replay)
             else:
                 self.sync.all_reduce_sum(eng.grads)
-        if getattr(self, "_opt", None) is not None:
-            self._opt.step(eng.params, eng.grads, self._found_inf if self.amp else None)
-        elif self.amp:
-            ops.sgd_step_guarded(eng.params, eng.grads, eng.mom, self.lr, oc.momentum, oc.weight_decay,
-                                 self.sync.grad_scale, first_step=(self._steps == 0), found_inf=self._found_inf)
-        else:
-            ops.sgd_step(eng.params[sl], eng.grads[sl], eng.mom[sl], self.lr, oc.momentum, oc.weight_decay,
-                         self.sync.grad_scale, first_step=(self._steps == 0))
-
-    def update_lr(self) -> None:
-        self.epoch += 1
-        self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-        if getattr(self, "_opt", None) is not None:
-            self._opt.set_epoch(self.epoch)
+        self._opt.step(eng.params, eng.grads, self._found_inf if self.amp else None, first_step=(self._steps == 0), part=part)
 
     def check_finite(self) -> None:
         """NaN / Inf scan of the step's outputs (the reference's `set_detect_anomaly(True)`, trainers/rpo.py:288)."""
@@ -586,10 +565,9 @@ class RPO(LoopMixin):
         also keeps the numbered file it is a copy of."""
         epoch = self.epoch if epoch is None else epoch
         self._join_side()
-        ck = checkpoint_dict(self.model.prompt_learner.state_dict(), epoch, self.engine.mom, self.optim_cfg,
-                             self.lr, self._steps, self.cfg.K * self.cfg.d_t, val_result)
-        if getattr(self, "_opt", None) is not None:             # torch's own layout for the kind
-            ck["optimizer"] = self._opt.state_dict(_prompt_shapes(ck["state_dict"]), lr=self.lr)
+        sd = self.model.prompt_learner.state_dict()
+        ck = checkpoint_dict(sd, epoch, None, self.optim_cfg, self.lr, self._steps, self.cfg.K * self.cfg.d_t, val_result,
+                             optimizer=self._opt.state_dict(_prompt_shapes(sd), lr=self.lr, steps=self._steps))
         return write_checkpoint(directory, ck, epoch, is_best)
 
     def after_epoch_eval(self, directory: str, val_result: float) -> bool:
@@ -619,21 +597,13 @@ class RPO(LoopMixin):
             for name, p in self.model.prompt_learner.named_parameters():
                 if name in sd:
                     p.copy_(sd[name].to(p.dtype))
-        opt = getattr(self, "_opt", None)
-        if opt is not None:                                     # (a file without matching state: weights only)
-            shapes = [tuple(p.shape) for _, p in self.model.prompt_learner.named_parameters()]
-            if opt.load_state_dict(ck.get("optimizer"), shapes, steps=ck.get("steps", 1)):
-                self._steps = max(1, int(ck.get("steps", 1)))
-        else:
-            mom = _momentum_from_optimizer_state(ck.get("optimizer"), self.engine.mom.numel())
-            if mom is not None:
-                self.engine.mom.copy_(mom)
-                self._steps = max(1, int(ck.get("steps", 1)))
+        shapes = [tuple(p.shape) for _, p in self.model.prompt_learner.named_parameters()]
+        if self._opt.load_state_dict(ck.get("optimizer"), shapes, steps=ck.get("steps", 1)):
+            self._steps = max(1, int(ck.get("steps", 1)))       # (a file without matching state: weights only)
         self.engine.params_version += 1
         self.epoch = int(ck.get("epoch", 0))
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
-        if opt is not None:
-            opt.set_epoch(self.epoch)
+        self._opt.set_epoch(self.epoch)
 
 
 # Names a checkpoint written by the reference's own run may reference (module, qualified name).  Dassl's
@@ -726,19 +696,15 @@ def load_checkpoint_file(path: str) -> dict:
 
 
 def checkpoint_dict(prompt_state, epoch: int, momentum: Optional[torch.Tensor], oc: OptimConfig, lr: float,
-                    steps: int, n_text: int, val_result: Optional[float] = None) -> dict:
+                    steps: int, n_text: int, val_result: Optional[float] = None, optimizer: Optional[dict] = None) -> dict:
     """The dict Dassl's `save_checkpoint` pickles (keys `state_dict`, `epoch`, `optimizer`, `scheduler`,
-    `val_result`); `optimizer` in torch.optim.SGD.state_dict() layout (param 0 = text_prompt, 1 = img_prompt)."""
+    `val_result`).  `optimizer`: the entry a trainer's optimiser wrote (`state_dict` of rpo_amd/optim.py); without one,
+    torch.optim.SGD.state_dict()'s layout for the flat `momentum` (param 0 = text_prompt, 1 = img_prompt)."""
     sd = {k: v.detach().cpu().clone() for k, v in prompt_state.items()}
-    state = {}
-    if momentum is not None and steps > 0:
-        m = momentum.detach().cpu()
-        state = {0: {"momentum_buffer": m[:n_text].reshape(sd["text_prompt"].shape).clone()},
-                 1: {"momentum_buffer": m[n_text:].reshape(sd["img_prompt"].shape).clone()}}
-    group = {"lr": lr, "momentum": oc.momentum, "dampening": 0, "weight_decay": oc.weight_decay, "nesterov": False,
-             "maximize": False, "foreach": None, "differentiable": False, "fused": None, "initial_lr": oc.lr,
-             "params": [0, 1]}
-    return {"state_dict": sd, "epoch": int(epoch), "optimizer": {"state": state, "param_groups": [group]},
+    if optimizer is None:
+        rows = [] if momentum is None else [momentum.detach().cpu()]
+        optimizer = _optim.torch_state_dict(oc, lr, rows, steps if rows else 0, _prompt_shapes(sd))
+    return {"state_dict": sd, "epoch": int(epoch), "optimizer": optimizer,
             "scheduler": {"last_epoch": int(epoch)}, "val_result": val_result, "steps": int(steps)}
 
 
@@ -759,17 +725,3 @@ def write_checkpoint(directory: str, ck: dict, epoch: int, is_best: bool = False
         import shutil
         shutil.copyfile(fn, os.path.join(path, "model-best.pth.tar"))
     return fn
-
-
-def _momentum_from_optimizer_state(opt_state, numel: int) -> Optional[torch.Tensor]:
-    if not opt_state or not opt_state.get("state"):
-        return None
-    st = opt_state["state"]
-    try:
-        bufs = [st[i]["momentum_buffer"] for i in (0, 1)]
-    except (KeyError, TypeError):
-        return None
-    if any(b is None for b in bufs):
-        return None
-    flat = torch.cat([b.reshape(-1).float() for b in bufs])
-    return flat if flat.numel() == numel else None

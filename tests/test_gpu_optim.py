@@ -381,6 +381,7 @@ def test_mixed_sweep_members_equal_their_standalone_runs(tmp_path):
     equals a standalone RPO with its config under the criterion of tests/test_gpu_sweep.py (prompts within SGD_TOL, loss
     within 1e-6 in f32).  ONE graph capture.  Then the checkpoints: a member's file is its standalone run's (each kind in
     torch's layout), and a fresh sweep that loads them continues bit for bit."""
+    from rpo_amd import optim
     from rpo_amd.sweep import RPOSweep
     from rpo_amd.trainer import RPO, OptimConfig
     K, B, S = 8, 2, 4
@@ -396,7 +397,7 @@ def test_mixed_sweep_members_equal_their_standalone_runs(tmp_path):
         return RPOSweep(cfg, sd, toks, members=members, batch_size=B, device=DEV, act_dtype=torch.float32, num_batches=2)
 
     mixed, plain = sweep(ocs), sweep(all_sgd)
-    assert mixed._opt is not None and plain._opt is None
+    assert type(mixed._opt) is optim.OptimState and type(plain._opt) is optim.PlainSGD
     solos = [RPO(cfg, sd, toks, ocs[s], DEV, torch.float32, batch_size=B, num_batches=2, prompts=prompts) for s in range(1, S)]
     lrs = []
     for step in range(3):

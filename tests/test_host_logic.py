@@ -183,7 +183,8 @@ def test_checkpoint_writer_satisfies_the_reference_reader_contract(tmp_path):
     """trainers/rpo.py:325-357 opens <dir>/prompt_learner/model-best.pth.tar (or model.pth.tar-<epoch>), reads
     checkpoint["state_dict"] / ["epoch"], drops token_prefix / token_suffix and load_state_dict(strict=False)s the
     rest into PromptLearner (parameters text_prompt [K, d_t], img_prompt [K, 768])."""
-    from rpo_amd.trainer import OptimConfig, checkpoint_dict, write_checkpoint, _momentum_from_optimizer_state
+    from rpo_amd.optim import rows_from_state_dict
+    from rpo_amd.trainer import OptimConfig, checkpoint_dict, write_checkpoint
     K, dt, dv = 4, 512, 768
     state = {"text_prompt": torch.randn(K, dt), "img_prompt": torch.randn(K, dv)}
     mom = torch.randn(K * dt + K * dv)
@@ -209,8 +210,9 @@ def test_checkpoint_writer_satisfies_the_reference_reader_contract(tmp_path):
         opt = torch.optim.SGD(pl.parameters(), lr=0.1, momentum=0.9)
         opt.load_state_dict(got["optimizer"])
         assert opt.param_groups[0]["lr"] == 0.005 and opt.param_groups[0]["weight_decay"] == 5e-4
-        assert torch.equal(_momentum_from_optimizer_state(got["optimizer"], mom.numel()), mom)
-    assert _momentum_from_optimizer_state({"state": {}, "param_groups": []}, 5) is None
+        rows, _ = rows_from_state_dict(OptimConfig(), got["optimizer"], [(K, dt), (K, dv)])
+        assert len(rows) == 1 and torch.equal(rows[0], mom)
+    assert rows_from_state_dict(OptimConfig(), {"state": {}, "param_groups": []}, [(5,)]) is None
 
 
 def test_committed_reference_checkpoint_fixture_layout():

@@ -11,6 +11,7 @@ from torch.utils.data import DataLoader
 from rpo_amd.evaluator import Classification
 from rpo_amd.input_pipeline import plan_packing
 from rpo_amd.loop import LoopMixin, epoch_indices
+from rpo_amd.optim import make_optimizer
 from rpo_amd.trainer import OptimConfig, lr_at_epoch
 
 
@@ -193,6 +194,7 @@ class _FakeTrainer(LoopMixin):
         self.optim_cfg = OptimConfig()
         self.epoch = self.batch_idx = 0
         self.lr = lr_at_epoch(self.optim_cfg, 0)
+        self._opt = make_optimizer([self.optim_cfg], 1, 1, 0, "cpu")
         self.log, self.lr_updates = [], 0
         self._bufs = [torch.zeros(batch_size, 3, 8, 8) for _ in range(2)]
 

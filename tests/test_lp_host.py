@@ -83,7 +83,7 @@ def test_fp16_precision_is_refused_before_any_device_work(monkeypatch):
 
 def _fake_trainer(steps: int):
     """An LP trainer object without an engine: enough for checkpoint_dict (the host side of save_model)."""
-    from rpo_amd import lp
+    from rpo_amd import lp, optim
     e = 512
     eng = type("E", (), {})()
     eng.lp_params = torch.arange(e * e + e, dtype=torch.float32) * 1e-6
@@ -94,6 +94,7 @@ def _fake_trainer(steps: int):
     tr = lp.LP.__new__(lp.LP)
     tr.model, tr.engine, tr.optim_cfg = model, eng, lp.lp_optim_config()
     tr.epoch, tr.lr, tr._steps = 1, 5e-4, steps
+    tr._opt = optim.make_optimizer([tr.optim_cfg], e * e + e, e * e + e, 0, "cpu", s0=eng.lp_moms)
     return tr
 
 

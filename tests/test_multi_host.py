@@ -84,7 +84,7 @@ def _cfg(K=4, depth=1):
 def test_member_checkpoint_is_a_standalone_rpo_file_in_both_directions(tmp_path):
     """A member's file, from fabricated tensors, through RPO's own reader; a standalone RPO's file through the multi
     trainer's reader.  No engine: the readers are exercised on stand-in objects, as tests/test_lp_host.py does."""
-    from rpo_amd import multi
+    from rpo_amd import multi, optim
     from rpo_amd.trainer import RPO, OptimConfig, checkpoint_dict, load_checkpoint_file, lr_at_epoch, write_checkpoint
     cfg = _cfg()
     nt, ni = cfg.K * cfg.d_t, cfg.K * cfg.d_v
@@ -108,6 +108,7 @@ def test_member_checkpoint_is_a_standalone_rpo_file_in_both_directions(tmp_path)
     tr.engine = type("E", (), {})()
     tr.engine.mom, tr.engine.params_version = torch.zeros(nt + ni), 0
     tr.optim_cfg, tr._graph = oc, None
+    tr._opt = optim.make_optimizer([oc], nt + ni, nt + ni, 0, "cpu", s0=tr.engine.mom)
     tr.load_model(str(tmp_path / "m1"))                                 # model-best
     assert torch.equal(tr.model.prompt_learner.text_prompt.detach().reshape(-1), params[1, :nt])
     assert torch.equal(tr.model.prompt_learner.img_prompt.detach().reshape(-1), params[1, nt:])
@@ -133,6 +134,7 @@ def test_member_checkpoint_is_a_standalone_rpo_file_in_both_directions(tmp_path)
     mt.cfg, mt.n_runs, mt.optim_cfg = cfg, 3, oc
     mt.engine = type("E", (), {})()
     mt.engine.m_params, mt.engine.m_mom = torch.zeros(3, nt + ni), torch.zeros(3, nt + ni)
+    mt._opt = optim.make_optimizer([oc], 3 * (nt + ni), 3 * (nt + ni), 0, "cpu", s0=mt.engine.m_mom)
     mt.load_model(dirs, epoch=3)
     assert torch.equal(mt.engine.m_params, params) and torch.equal(mt.engine.m_mom, mom)
     assert mt.epoch == 3 and mt._steps == 7 and mt.lr == lr_at_epoch(oc, 3) < oc.lr

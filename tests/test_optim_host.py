@@ -218,3 +218,130 @@ def test_hyper_table_carries_the_betas_to_double_precision():
     assert abs((float(t[1, 3]) + float(t[1, 6])) - 0.9) < 1e-15 and abs((float(t[1, 4]) + float(t[1, 7])) - 0.999) < 1e-15
     assert abs((float(t[2, 4]) + float(t[2, 7])) - 0.99) < 1e-15 and t[2, 3] == 0.5 and t[2, 5] == np.float32(1e-8)
     assert abs((float(t[3, 4]) + float(t[3, 7])) - 0.3) < 1e-15
+
+
+# ------------------------------------------------------------------------------ the plain-SGD optimiser: what it launches
+def _recorders(monkeypatch):
+    from rpo_amd import ops
+    calls = []
+    for fn in ("sgd_step", "sgd_step_guarded", "sgd_step_sets"):
+        monkeypatch.setattr(ops, fn, lambda *a, _fn=fn, **k: calls.append((_fn, a, k)))
+    monkeypatch.setattr(ops, "optim_step_sets", lambda *a, **k: pytest.fail("the table-driven kernel from PlainSGD"))
+    return calls
+
+
+def _is(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """The same memory seen the same way: what a kernel launch would get."""
+    return a.data_ptr() == b.data_ptr() and tuple(a.shape) == tuple(b.shape) and a.stride() == b.stride() and a.dtype == b.dtype
+
+
+def test_plain_sgd_issues_the_launches_the_trainers_issued(monkeypatch):
+    """`PlainSGD` calls the ops function the trainers called, with their arguments and slices: rpo_sgd_step over the whole
+    flat buffer [text 8 | img 16] or one half, rpo_sgd_step_guarded with a found_inf, the rate of the epoch as a kernel
+    argument (and as the graph key); with `used`, rpo_sgd_step_sets on a device table [S, 4] and a constant graph key."""
+    from rpo_amd import optim
+    from rpo_amd.trainer import OptimConfig, lr_at_epoch
+    calls = _recorders(monkeypatch)
+    oc = OptimConfig(lr=0.01, momentum=0.8, weight_decay=1e-3, max_epoch=3)
+    nt, n = 8, 24
+    p, g, m = torch.arange(n, dtype=torch.float32), torch.ones(n), torch.zeros(n)
+    opt = optim.make_optimizer([oc], n, n, 0, "cpu", s0=m, grad_scale=0.25)
+    assert type(opt) is optim.PlainSGD and opt.splittable and not opt.table_driven
+    lr0, lr1 = lr_at_epoch(oc, 0), lr_at_epoch(oc, 1)
+    assert lr0 != lr1 and opt.graph_key() == lr0
+    # ---- the whole buffer: the first step, then a later one
+    opt.step(p, g, None, first_step=True)
+    opt.step(p, g, first_step=False)
+    for (fn, a, k), first in zip(calls, (True, False)):
+        assert fn == "sgd_step" and _is(a[0], p) and _is(a[1], g) and _is(a[2], m)
+        assert a[3:] == (lr0, 0.8, 1e-3, 0.25) and k == {"first_step": first}
+    # ---- each half (RPO's early text): [0, nt) and [nt, n) of all three buffers
+    del calls[:]
+    opt.step(p, g, first_step=False, part=slice(0, nt))
+    opt.step(p, g, first_step=False, part=slice(nt, None))
+    for (fn, a, k), sl in zip(calls, (slice(0, nt), slice(nt, None))):
+        assert fn == "sgd_step" and _is(a[0], p[sl]) and _is(a[1], g[sl]) and _is(a[2], m[sl]) and a[0].numel() in (nt, n - nt)
+        assert a[3:] == (lr0, 0.8, 1e-3, 0.25) and k == {"first_step": False}
+    # ---- guarded: a found_inf selects rpo_sgd_step_guarded (never with a part)
+    del calls[:]
+    found = torch.zeros(2, dtype=torch.int32)
+    opt.step(p, g, found, first_step=True)
+    (fn, a, k), = calls
+    assert fn == "sgd_step_guarded" and _is(a[0], p) and _is(a[1], g) and _is(a[2], m) and a[3:] == (lr0, 0.8, 1e-3, 0.25)
+    assert set(k) == {"first_step", "found_inf"} and k["first_step"] is True and k["found_inf"] is found
+    with pytest.raises(AssertionError):
+        opt.step(p, g, found, part=slice(0, nt))
+    # ---- a new epoch: the rate of the next launch and the graph key change; the same epoch again changes nothing
+    del calls[:]
+    opt.set_epoch(1)
+    opt.set_epoch(1)
+    opt.step(p, g, first_step=False)
+    assert calls[0][1][3] == lr1 and opt.graph_key() == lr1 and opt.epoch == 1
+    # ---- a [S, n] buffer with one shared config (RPOMulti): one launch over the flat view, grad_scale 1
+    del calls[:]
+    P, G, M = p.view(2, 12), g.view(2, 12), torch.zeros(2, 12)
+    multi = optim.make_optimizer([oc], n, n, 0, "cpu", s0=M)
+    multi.step(P, G, None, first_step=True)
+    (fn, a, k), = calls
+    assert fn == "sgd_step" and _is(a[0], P.view(-1)) and _is(a[1], G.view(-1)) and _is(a[2], M.view(-1))
+    assert a[3:] == (lr0, 0.8, 1e-3, 1.0) and k == {"first_step": True}
+    # ---- the sets form: 2 sets with their own configs, `used` shorter than the segments
+    del calls[:]
+    ocs = [oc, OptimConfig(lr=0.02, momentum=0.9, weight_decay=5e-4, max_epoch=3, warmup_epoch=2)]
+    used = torch.tensor([[3, 5], [4, 8]], dtype=torch.int32)
+    sets = optim.make_optimizer(ocs, 12, 4, 8, "cpu", s0=M, used=used)
+    assert type(sets) is optim.PlainSGD and not sets.splittable and not sets.table_driven and sets.graph_key() == 0
+    found2 = torch.zeros(2, 2, dtype=torch.int32)
+    sets.step(P, G, None, first_step=True)
+    sets.step(P, G, found2, first_step=False)
+    for (fn, a, k), fi, first in zip(calls, (None, found2), (True, False)):
+        assert fn == "sgd_step_sets" and _is(a[0], P) and _is(a[1], G) and _is(a[2], M) and a[3] is sets.hyper and a[4:] == (4, 8)
+        assert set(k) == {"first_step", "used", "found_inf"} and k["first_step"] is first and k["used"] is used and k["found_inf"] is fi
+    assert torch.equal(sets.hyper, optim.sgd_hyper_table(ocs, 0)) and tuple(sets.hyper.shape) == (2, 4)
+    table = sets.hyper
+    for epoch in (1, 2, 7):                             # (7: past the schedule's end, the formula still gives a rate)
+        sets.set_epoch(epoch)
+        assert sets.hyper is table and torch.equal(table, optim.sgd_hyper_table(ocs, epoch)) and sets.graph_key() == 0
+    assert not torch.equal(optim.sgd_hyper_table(ocs, 1), optim.sgd_hyper_table(ocs, 2))
+    with pytest.raises(AssertionError):
+        sets.step(P, G, None, part=slice(0, 4))
+    # ---- one member that is not plain SGD: the table-driven optimiser for all of them
+    assert not optim.is_plain_sgd(OptimConfig(sgd_nesterov=True)) and not optim.is_plain_sgd(OptimConfig(name="adam"))
+
+
+@pytest.mark.parametrize("steps", [0, 3])
+def test_plain_sgd_state_dict_is_torch_optim_sgds_layout_and_loads_back(steps):
+    """The `optimizer` entry of a plain-SGD trainer, key order included, against the literal dict (the layout the LP and
+    host-logic tests pin against the reference's file); `load_state_dict` restores the momentum row from it."""
+    from rpo_amd import optim
+    from rpo_amd.trainer import OptimConfig
+    oc = OptimConfig(lr=0.01, momentum=0.8, weight_decay=1e-3)
+    shapes = [(2, 4), (2, 8)]
+    m = torch.arange(24, dtype=torch.float32) * 0.5 - 3.0
+    opt = optim.make_optimizer([oc], 24, 24, 0, "cpu", s0=m.clone())
+    got = opt.state_dict(shapes, lr=0.004, steps=steps)
+    state = {} if steps == 0 else {0: {"momentum_buffer": m[:8].reshape(2, 4)}, 1: {"momentum_buffer": m[8:].reshape(2, 8)}}
+    want = {"state": state,
+            "param_groups": [{"lr": 0.004, "momentum": 0.8, "dampening": 0, "weight_decay": 1e-3, "nesterov": False,
+                              "maximize": False, "foreach": None, "differentiable": False, "fused": None, "initial_lr": 0.01,
+                              "params": [0, 1]}]}
+    assert list(got) == list(want) and list(got["state"]) == list(want["state"])
+    (gg,), (wg,) = got["param_groups"], want["param_groups"]
+    assert list(gg.items()) == list(wg.items()) and all(type(gg[k]) is type(wg[k]) for k in wg)
+    for i in want["state"]:
+        assert list(got["state"][i]) == ["momentum_buffer"]
+        a, b = got["state"][i]["momentum_buffer"], want["state"][i]["momentum_buffer"]
+        assert a.dtype == torch.float32 and tuple(a.shape) == tuple(b.shape) and torch.equal(a, b)
+        assert a.data_ptr() != opt.s0.data_ptr()                      # a copy, not a view of the live buffer
+    if steps:                                                         # torch.optim.SGD itself takes it
+        params = [torch.nn.Parameter(torch.zeros(sh)) for sh in shapes]
+        topt = torch.optim.SGD(params, lr=0.1, momentum=0.9)
+        topt.load_state_dict(got)
+        assert torch.equal(topt.state[params[1]]["momentum_buffer"], m[8:].reshape(2, 8))
+    # ---- and back: a fresh optimiser's momentum row
+    fresh_m = torch.zeros(24)
+    fresh = optim.make_optimizer([oc], 24, 24, 0, "cpu", s0=fresh_m)
+    assert fresh.load_state_dict(want, shapes, steps=steps) is (steps > 0)
+    assert torch.equal(fresh_m, m if steps else torch.zeros(24))
+    assert not fresh.load_state_dict(want, [(2, 4), (4, 4)]) and not fresh.load_state_dict(None, shapes)
+    assert optim.state_shapes(oc, want) == ([] if steps == 0 else shapes)

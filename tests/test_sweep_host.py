@@ -112,20 +112,24 @@ def test_gather_scatter_between_a_member_row_and_a_standalone_flat_vector():
 
 def _stand_in(cfg, member_K, optims):
     """An RPOSweep without an engine: the checkpoint code paths on stand-in buffers (as tests/test_multi_host.py)."""
-    from rpo_amd import sweep
+    from rpo_amd import optim, sweep
     from rpo_amd.trainer import lr_at_epoch
     S, n = len(member_K), cfg.K * (cfg.d_t + cfg.d_v)
     tr = sweep.RPOSweep.__new__(sweep.RPOSweep)
     tr.cfg, tr.n_runs, tr.member_K, tr.optim_cfgs = cfg, S, list(member_K), list(optims)
     tr.member_cfgs = [dataclasses.replace(cfg, K=k) for k in member_K]
-    tr.epoch, tr._steps, tr._hyper_epoch = 2, 5, 2
+    tr.epoch, tr._steps = 2, 5
     tr.lr = [lr_at_epoch(oc, 2) for oc in optims]
     tr.engine = type("E", (), {})()
     tr.engine.m_params, tr.engine.m_mom = torch.zeros(S, n), torch.zeros(S, n)
+    tr._opt = optim.make_optimizer(optims, n, cfg.K * cfg.d_t, cfg.K * cfg.d_v, "cpu", s0=tr.engine.m_mom,
+                                   used=sweep.used_table(member_K, cfg.d_t, cfg.d_v))
+    tr._opt.set_epoch(2)
     return tr
 
 
 def test_member_checkpoint_is_a_standalone_rpo_file_of_its_own_K_in_both_directions(tmp_path):
+    from rpo_amd import optim
     from rpo_amd.sweep import flat_to_member_row, member_row_to_flat
     from rpo_amd.trainer import RPO, OptimConfig, checkpoint_dict, load_checkpoint_file, lr_at_epoch, write_checkpoint
     cfg = _cfg(K=8)
@@ -164,6 +168,7 @@ def test_member_checkpoint_is_a_standalone_rpo_file_of_its_own_K_in_both_directi
         solo.engine = type("E", (), {})()
         solo.engine.mom, solo.engine.params_version = torch.zeros(k * (dt + dv)), 0
         solo.optim_cfg, solo._graph = optims[s], None
+        solo._opt = optim.make_optimizer([optims[s]], k * (dt + dv), k * (dt + dv), 0, "cpu", s0=solo.engine.mom)
         solo.load_model(dirs[s])
         want_p, want_m = member_row_to_flat(tr.engine.m_params[s], K, k, dt, dv), member_row_to_flat(tr.engine.m_mom[s], K, k, dt, dv)
         got_p = torch.cat([solo.model.prompt_learner.text_prompt.detach().reshape(-1),
@@ -186,7 +191,8 @@ def test_member_checkpoint_is_a_standalone_rpo_file_of_its_own_K_in_both_directi
     for s in range(2):
         assert torch.equal(tr.engine.m_params[s], want_rows[s][0]) and torch.equal(tr.engine.m_mom[s], want_rows[s][1])
     assert not tr.engine.m_params[1, 3 * dt:K * dt].any() and not tr.engine.m_mom[1, K * dt + 3 * dv:].any()
-    assert tr.epoch == 3 and tr._steps == 7 and tr.lr == [lr_at_epoch(oc, 3) for oc in optims] and tr._hyper_epoch is None
+    assert tr.epoch == 3 and tr._steps == 7 and tr.lr == [lr_at_epoch(oc, 3) for oc in optims]
+    assert tr._opt.epoch == 3 and torch.equal(tr._opt.hyper, optim.sgd_hyper_table(optims, 3))   # the table holds epoch 3's rates
     # a file of another K is refused by name; so are files of different epochs
     with pytest.raises(ValueError, match="this trainer has K = 8"):
         tr.load_model([solo_dirs[1], solo_dirs[1]], epoch=3)
@@ -194,6 +200,28 @@ def test_member_checkpoint_is_a_standalone_rpo_file_of_its_own_K_in_both_directi
                                                    None, optims[1], 0.01, 0, 3 * dt), 3)
     with pytest.raises(ValueError, match="one loop runs all members"):
         tr.load_model(solo_dirs, epoch=3)
+
+
+@pytest.mark.parametrize("second", ["sgd", "adam"])
+def test_a_mix_of_files_with_and_without_optimiser_state_is_refused(tmp_path, second):
+    """One first-step flag (plain SGD) / one loop (table-driven) covers every member: member 0's file has momentum, member 1's
+    was written before its first step.  The wording is the trainer's own per optimiser family."""
+    from rpo_amd.trainer import OptimConfig, checkpoint_dict, write_checkpoint
+    cfg = _cfg(K=8)
+    dt, dv = cfg.d_t, cfg.d_v
+    optims = [OptimConfig(lr=0.01), OptimConfig(lr=0.02) if second == "sgd" else OptimConfig(name="adam", lr=1e-3)]
+    tr = _stand_in(cfg, [8, 3], optims)
+    dirs = []
+    for s, k in enumerate([8, 3]):
+        mom, steps = (torch.ones(k * (dt + dv)), 7) if s == 0 else (None, 0)
+        ck = checkpoint_dict({"text_prompt": torch.zeros(k, dt), "img_prompt": torch.zeros(k, dv)}, 3, mom, optims[0], 0.01, steps, k * dt)
+        write_checkpoint(str(tmp_path / f"m{s}"), ck, 3)
+        dirs.append(str(tmp_path / f"m{s}"))
+    want = ("RPOSweep.load_model: some checkpoints carry momentum and some do not (one first-step flag covers every member)"
+            if second == "sgd" else "RPOSweep.load_model: some checkpoints carry optimiser state and some do not")
+    with pytest.raises(ValueError) as err:
+        tr.load_model(dirs, epoch=3)
+    assert str(err.value) == want and tr.epoch == 2 and tr._steps == 5
 
 
 def test_seeded_members_draw_rpo_initial_prompts_at_their_own_K():
@@ -215,7 +243,7 @@ def test_seeded_members_draw_rpo_initial_prompts_at_their_own_K():
 
 
 def test_lr_table_follows_each_members_own_schedule():
-    from rpo_amd.sweep import hyper_table
+    from rpo_amd.optim import sgd_hyper_table as hyper_table
     from rpo_amd.trainer import OptimConfig, lr_at_epoch
     ocs = [OptimConfig(lr=0.01, warmup_epoch=1, weight_decay=5e-4, momentum=0.9, max_epoch=4),
            OptimConfig(lr=0.035, warmup_epoch=2, warmup_cons_lr=3e-5, weight_decay=1e-3, momentum=0.8, max_epoch=4)]
