@@ -1,6 +1,7 @@
 """Host-side logic of the CLIP ResNet tower: config inference from a state dict, the BatchNorm fold, the FLOP count and
 the reference-pinned fixtures (tests/golden/ref_rn_*.npz, tools/make_golden_rn.py).  No GPU needed."""
 import json
+import math
 import os
 import sys
 
@@ -131,3 +132,67 @@ def test_unsupported_resnets_are_named_at_load():
         assert rn_unsupported(rn_clip((3, 4, 23, 3), 64, 512), dt) is None
         assert rn_unsupported(rn_clip((4, 6, 10, 6), 80, 640, image_size=288), dt) is not None
         assert rn_unsupported(rn_clip((6, 8, 18, 8), 96, 768, image_size=384), dt) is not None
+
+
+def test_bn_fold_at_trained_statistics():
+    """fold_bn against float64 F.batch_norm(F.conv2d(...)) at a trained BatchNorm's statistics: running_var log-uniform
+    in [1e-6, 1e3] plus exact zeros (the fold's gain is then 1 / sqrt(eps) = 316), gammas of both signs plus exact zeros
+    (dead channels: W' = 0, b' = beta), means up to +-50.  Every element within 1e-12 of |x| (*) |W'| + |b'|: both sides
+    are float64 (unit roundoff 1.1e-16) sums of at most 9 * 64 + 2 terms of that magnitude."""
+    from helpers import assert_within
+    from rpo_amd.engine_rn import fold_bn
+    g = torch.Generator().manual_seed(3)
+    u = lambda n: torch.rand(n, generator=g, dtype=torch.float64)
+    for cin, cout, k in ((16, 40, 3), (64, 24, 1)):
+        x = torch.randn(2, cin, 7, 9, generator=g, dtype=torch.float64)
+        w = torch.randn(cout, cin, k, k, generator=g, dtype=torch.float64)
+        var = torch.exp(math.log(1e-6) + u(cout) * math.log(1e3 / 1e-6))
+        var[::7] = 0.0
+        gamma = torch.randn(cout, generator=g, dtype=torch.float64)
+        gamma[3::5] = 0.0
+        beta = torch.randn(cout, generator=g, dtype=torch.float64)
+        mean = (2 * u(cout) - 1) * 50.0
+        assert var.min() == 0 and var[var > 0].min() < 1e-4 and var.max() > 10 and (gamma > 0).any() and (gamma < 0).any()
+        assert (gamma == 0).any() and mean.abs().max() > 25
+        ref = F.batch_norm(F.conv2d(x, w, padding=k // 2), mean, var, gamma, beta, False, 0.0, 1e-5)
+        wf, b = fold_bn(w.numpy(), gamma.numpy(), beta.numpy(), mean.numpy(), var.numpy())
+        assert wf.shape == (cout, k, k, cin) and wf.dtype == np.float64 and b.dtype == np.float64
+        wt, bt = torch.from_numpy(wf).permute(0, 3, 1, 2), torch.from_numpy(b)[None, :, None, None]
+        got = F.conv2d(x, wt, padding=k // 2) + bt
+        mag = F.conv2d(x.abs(), wt.abs(), padding=k // 2) + bt.abs()
+        assert_within(got, ref, 1e-12 * mag, f"fold_bn {cin}->{cout} k{k}")
+        dead = gamma == 0
+        assert bool((got[:, dead] == beta[dead][None, :, None, None]).all())
+
+
+def _contract_refuses(layers, width, image_size, f32):
+    """The kernel contract (include/rpo_amd.h), written out against ModifiedResNet's layer table (clip/model.py:94-152):
+    rpo_conv_stem takes Cout % 8 == 0 up to 128; rpo_conv2d_nhwc Cin % 16 (f32) / % 32 (16-bit) == 0 and Cout % 32 == 0;
+    the attention pool at most 256 tokens."""
+    ck = 16 if f32 else 32
+    stem = width // 2
+    bad = stem % 8 != 0 or stem > 128
+    convs = [(stem, stem), (stem, width)]
+    inpl = width
+    for s, n in enumerate(layers):
+        p = width * 2 ** s
+        for i in range(n):
+            convs += [(inpl, p), (p, p), (p, 4 * p)]
+            if i == 0:
+                convs.append((inpl, 4 * p))                 # the downsample branch (stride > 1 or inplanes != 4 planes)
+            inpl = 4 * p
+    bad = bad or any(ci % ck or co % 32 for ci, co in convs)
+    return bad or (image_size // 32) ** 2 + 1 > 256
+
+
+@pytest.mark.parametrize("width,layers,image_size", [(64, (3, 4, 6, 3), 224), (80, (4, 6, 10, 6), 288),
+                                                     (96, (6, 8, 18, 8), 384), (128, (3, 15, 36, 10), 448),
+                                                     (64, (1, 1, 1, 1), 480), (64, (1, 1, 1, 1), 512)])
+def test_rn_unsupported_follows_the_kernel_contract(width, layers, image_size):
+    from rpo_amd.engine_rn import rn_unsupported
+    cfg = rn_clip(layers, width, 1024, image_size=image_size)
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        want = _contract_refuses(layers, width, image_size, dt == torch.float32)
+        assert (rn_unsupported(cfg, dt) is not None) == want, (width, image_size, dt)
+    # widths 64 and 128 run, 80 (stem 40) and 96 (stem 48: Cout % 32) do not; 512 px gives 257 tokens
+    assert _contract_refuses(layers, width, image_size, True) == (width in (80, 96) or image_size == 512)
