@@ -290,13 +290,16 @@ int rpo_reduce_groups_sets(const float* src, int64_t ld, float* out, int64_t out
  * three column slices of one packed [R, 3d] in-proj output).  Every query row (frozen and
  * prompt) reads ONLY the N frozen keys of its own image: the additive mask of
  * trainers/rpo.py:154-156 is -inf on the prompt columns for all rows, so those columns are
- * skipped, not computed.  out[R, ldo] act dtype.  N <= 288.
+ * skipped, not computed.  out[R, ldo] act dtype.  N <= 1025: up to 288 keys an image's K / V sit
+ * in LDS at once; above that the keys are walked in chunks of 256 under an online softmax
+ * (ViT-L/14 at 336 px: N = 577), and N > 1025 returns RPO_E_SHAPE with nothing launched.
  * Replaces F.scaled_dot_product_attention inside nn.MultiheadAttention (clip/model.py:186). */
 int rpo_attn_readonly_fwd(const void* q, const void* k, const void* v, int64_t ld,
                           void* out, int64_t ldo, int dtype, int B, int H, int N, int Kp,
                           float scale, void* stream);
 /* Same, computing only the queries q_first .. N+Kp-1 of every image (earlier rows of `out` are left untouched).  The
- * last block of the image tower needs the prompt queries only: ln_post reads nothing else (trainers/rpo.py:210). */
+ * last block of the image tower needs the prompt queries only: ln_post reads nothing else (trainers/rpo.py:210).
+ * N <= 1025, as above; a query's bits do not depend on q_first. */
 int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const void* v, int64_t ld,
                                void* out, int64_t ldo, int dtype, int B, int H, int N, int Kp, float scale,
                                int q_first, void* stream);
@@ -318,7 +321,8 @@ int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* k, const vo
 
 /* Backward of the above for the prompt rows only: dq[B*Kp, lddq] given da[B*Kp, ldda].
  * q_rows points at the first PROMPT row of q; k, v at the first frozen row.  dK/dV are not
- * produced: keys/values belong to frozen tokens.  Kp <= 128, N <= 288. */
+ * produced: keys/values belong to frozen tokens.  Kp <= 128, N <= 1025 (N > 288: the keys in chunks of 256, one pass for
+ * the row statistics and one for delta and dS.K; fixed summation order, no atomics). */
 int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
                           const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
                           int B, int H, int N, int Kp, float scale, void* stream);

@@ -104,6 +104,35 @@ def vit_l14(**kw) -> RPOConfig:
     return RPOConfig(**base)
 
 
+def vit_b32(**kw) -> RPOConfig:
+    """ViT-B/32 (clip/clip.py:34; configs/trainers/CoOp/vit_b32.yaml): ViT-B/16's widths on a 7 x 7 grid -- 50 frozen
+    tokens, patch rows of 3 * 32 * 32 = 3072."""
+    base = dict(name="ViT-B/32", patch=32)
+    base.update(kw)
+    return RPOConfig(**base)
+
+
+def vit_l14_336(**kw) -> RPOConfig:
+    """ViT-L/14@336px (clip/clip.py:38): ViT-L/14's widths on a 24 x 24 grid -- 577 frozen tokens, which the image
+    tower's attention walks in chunks (ATTN_LDS_TOKENS)."""
+    return vit_l14(**{**dict(name="ViT-L/14@336px", image_size=336), **kw})
+
+
+# Frozen tokens of an image whose K / V the attention kernels hold in LDS at once (include/rpo_amd.h).  Above it
+# rpo_attn_readonly_fwd / _fwd_rows / _bwd walk the keys in chunks (up to ATTN_MAX_TOKENS); rpo_attn_prompt_fwd (the
+# shared-frozen-rows evaluation, FrozenImageKV) and rpo_attn_readonly_bwd_proj (the fused d out-proj) do not.
+ATTN_LDS_TOKENS = 288
+ATTN_MAX_TOKENS = 1025
+
+
+def refuse_long_grid(cfg: RPOConfig, what: str) -> None:
+    """The paths built on rpo_attn_prompt_fwd stop at its 288-token limit: refused where they are set up, not mid-pass."""
+    if not cfg.is_rn and cfg.n_frozen > ATTN_LDS_TOKENS:
+        raise NotImplementedError(f"{what}: {cfg.name} has {cfg.n_frozen} frozen tokens per image, above the "
+                                  f"{ATTN_LDS_TOKENS}-token limit of rpo_attn_prompt_fwd (the prompt-row pass on shared or "
+                                  "cached frozen K / V); evaluate through the whole image pass instead")
+
+
 def rn_clip(layers=(3, 4, 6, 3), width: int = 64, embed: int = 1024, image_size: int = 224, **kw) -> RPOConfig:
     """CLIP ResNet (clip/model.py:94-152, built by :412-419): RN50 = (3, 4, 6, 3) / width 64 / embed 1024, RN101 =
     (3, 4, 23, 3) / 64 / 512; text tower as ViT-B/16's (512 wide, 12 layers) unless given."""

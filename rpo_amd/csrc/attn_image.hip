@@ -8,7 +8,8 @@
 // skipped instead of computed-and-masked.
 //
 // One workgroup per (image, head).  K and V of the N frozen tokens are staged ONCE into
-// LDS (N <= 288, head_dim 64: <= 78 KB in bf16, <= 150 KB in f32) and every wave takes a
+// LDS (N <= 288, head_dim 64: <= 78 KB in bf16, <= 150 KB in f32; above 288 keys the *_long kernels below walk them in
+// chunks of 256 with the same per-tile arithmetic) and every wave takes a
 // 32-query tile.  The score tile is computed transposed, S^T = K . Q^T, so that by the
 // 32x32 C/D map (col = lane&31, row = (reg&3)+8*(reg>>2)+4*(lane>>5)) a lane holds ONE
 // query's scores in registers: the softmax row-reduce is an in-register reduction plus a
@@ -1337,6 +1338,325 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair_kernel(const AttnBwdProb
   }
 }
 
+// ---- long sequences (288 < N <= ATTN_LONG_MAX_N): the keys in chunks ------------------------------------------------------
+// ViT-L/14 at 336 px has a 24 x 24 grid, N = 577: neither all keys of an image in LDS (about 165 KB of K rows and V^T
+// fragments in the 16-bit modes) nor all score tiles of a query in registers fit.  These two kernels walk the keys in
+// chunks of C = 32 LONG_NT = 256: a chunk is staged exactly as the kernels above stage all keys (16-bit: K rows padded
+// to 144 B + V^T fragments transposed on the matrix core, 68 KB; f32: row-major [256][65] twice, 130 KB), consumed by every
+// wave, and overwritten by the next one behind a barrier.  Keys past N inside the last chunk are staged as zeros and masked
+// to -inf before the exponential: they contribute exact zeros.  Per query the arithmetic of a key tile is that of
+// attn_fwd_kernel / attn_bwd_body; a lane holds one query, so a query's bits do not depend on its neighbours in the tile,
+// on q_first or on the batch.
+constexpr int LONG_NT = 8;
+constexpr int ATTN_LONG_MAX_N = 1025;              // ViT-L/14 at 448 px (32 x 32 grid + CLS)
+
+// Forward.  One workgroup per (image, head, group of 8 query tiles); a wave keeps ONE 32-query tile for the whole walk:
+// its q fragment, running maximum, running sum and the fp32 output tile stay in registers across the chunks (online
+// softmax), so nothing but K / V passes through LDS.  Each workgroup of an (image, head) stages the keys itself.
+template <typename T>
+__global__ __launch_bounds__(512, 4) void attn_fwd_long_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                            const T* __restrict__ v, int64_t ld, T* out, int64_t ldo,
+                                                            int B, int H, int N, int Kp, float scale, int q_first,
+                                                            int groups) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NT = LONG_NT, C = 32 * NT;
+  using L = AL<T, NT>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int unit = (int)blockIdx.x / groups, grp = (int)blockIdx.x - unit * groups;
+  const int b = unit / H, h = unit % H;
+  const T* kb = k + (int64_t)b * N * ld + h * 64;
+  const T* vb = v + (int64_t)b * N * ld + h * 64;
+  char* ks = smem;
+  char* vs = smem + L::K_BYTES;
+  const int S = N + Kp;
+  // whole 32-query tiles before q_first are skipped, the leading queries of the first computed tile are not stored
+  const int qt = (q_first >> 5) + 8 * grp + wave;
+  const bool active = qt < ((S + 31) >> 5);        // wave-uniform; an idle wave still stages and meets the barriers
+  const int s = qt * 32 + l31;
+  const int sc_ = min(s, S - 1);
+  const int64_t grow = sc_ < N ? (int64_t)b * N + sc_ : (int64_t)B * N + (int64_t)b * Kp + (sc_ - N);
+  RowFrag<T> qf;
+  qf.load(q + grow * ld + h * 64, half);
+  float m = -INFINITY, l = 0.f;
+  f32x16_t o[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+#pragma unroll 1
+  for (int c0 = 0; c0 < N; c0 += C) {
+    const int Nc = min(N - c0, C);                 // keys of this chunk
+    const T* kc = kb + (int64_t)c0 * ld;
+    const T* vc = vb + (int64_t)c0 * ld;
+    if (c0 > 0) __syncthreads();                   // the previous chunk has been consumed
+    // (opaque copies: otherwise the staging addresses of every load are hoisted out of the chunk loop, kept live across
+    //  the key loop and spilled)
+    int tidv = tid, lanev = lane;
+    asm volatile("" : "+v"(tidv), "+v"(lanev));
+    const int l31s = lanev & 31, halfs = lanev >> 5;
+    if constexpr (sizeof(T) == 2) {
+      // K first, then V: with the query's state (q fragment, output tile) live across the chunks, both batches of loads
+      // in flight at once do not fit 128 VGPRs
+      stage_rows_bf16<NT, 512>(ks, reinterpret_cast<const bf16_t*>(kc), ld, Nc, tidv);
+      asm volatile("" ::: "memory");
+      bf16x8_t vrows[4];                           // wave w transposes key tile w of the chunk
+      const int key = 32 * wave + l31s;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        uint4 z = make_uint4(0, 0, 0, 0);
+        if (key < Nc) z = *reinterpret_cast<const uint4*>(vc + (int64_t)key * ld + kk * 16 + halfs * 8);
+        vrows[kk] = __builtin_bit_cast(bf16x8_t, z);
+      }
+      const bf16x8_t i0 = ident_frag<T>(0, l31s, halfs), i1 = ident_frag<T>(1, l31s, halfs);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) {
+        bf16x8_t fr[2];
+        transpose_tile<T>(vrows, dt, i0, i1, fr);
+#pragma unroll
+        for (int g2 = 0; g2 < 2; ++g2)
+          *reinterpret_cast<bf16x8_t*>(vs + (((wave * 2 + dt) * 2 + g2) * 64 + lanev) * 16) = fr[g2];
+      }
+    } else {
+      stage_rows_f32<NT, 512>(reinterpret_cast<float*>(ks), kc, ld, Nc, tidv);
+      stage_rows_f32<NT, 512>(reinterpret_cast<float*>(vs), vc, ld, Nc, tidv);
+    }
+    __syncthreads();
+    if (active) {
+      int l31v = l31;                              // (keeps the K / V reads of the key loop inside it: see attn_fwd_kernel)
+      asm volatile("" : "+v"(l31v));
+      if constexpr (sizeof(T) == 2) {
+        const int nfull = Nc >> 5, rem = Nc - 32 * nfull;
+#pragma unroll 1
+        for (int t = 0; t < nfull; ++t) {
+          f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
+          float tm = sc[0];
+#pragma unroll
+          for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
+          tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+          const float alpha = move_max<T>(tm, scale, m, o);
+          l = l * alpha + exp_tile<T>(sc, m, scale);
+          contract_keys<T, NT>(vs, t, sc, o, l31v, half);
+        }
+        if (rem > 0) fwd_tile_tail<T, NT>(ks, vs, nfull, rem, qf, scale, m, l, o, l31v, half);   // (rem > 0: nfull < NT)
+      } else {
+#pragma unroll 1
+        for (int t = 0; 32 * t < Nc; ++t) {        // every tile visited holds a key: the maximum is finite
+          f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
+          const float mn = fmaxf(m, mask_and_max(sc, t, Nc, half));
+          const float alpha = exp_scalar<T>(m - mn, scale);        // first tile: exp(-inf) = 0
+          l = l * alpha + exp_tile<T>(sc, mn, scale);
+#pragma unroll
+          for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+          contract_keys<T, NT>(vs, t, sc, o, l31v, half);
+          m = mn;
+        }
+      }
+    }
+  }
+  l += __shfl_xor(l, 32, 64);
+  const float inv = 1.0f / l;
+  if (active && s < S && s >= q_first) {
+    T* orow = out + grow * ldo + h * 64;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
+                      o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
+  }
+}
+
+// Backward for the prompt rows (dq; K and V are frozen).  One workgroup per (image, head, 32-query tile), the four waves
+// sharing the tile as in attn_bwd_body: wave w owns key tiles w, w + 4 of EVERY chunk.  Pass 1 walks the chunks (K only)
+// for the row maximum and sum -- per wave online over its tiles, merged once through LDS; pass 2 walks them again (K and V)
+// and accumulates U, W and delta in registers across the chunks; the four waves' partials are summed through LDS in a
+// fixed order.  No atomics: two calls give the same bits.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void attn_bwd_long_kernel(const T* qr, int64_t ldq, const T* k, const T* v,
+                                                            int64_t ldkv, const T* da, int64_t ldda, T* dq,
+                                                            int64_t lddq, int B, int H, int N, int Kp, float scale,
+                                                            int nqt) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NT = LONG_NT, C = 32 * NT;
+  using L = AL<T, NT>;
+  constexpr int stat_off = L::BWD_BYTES;           // the launcher allocates stat_off + 2048
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, l31 = lane & 31;
+  const int pair_id = (int)blockIdx.x / nqt, qt = (int)blockIdx.x - pair_id * nqt;
+  const int b = pair_id / H, h = pair_id % H;
+  const T* kb = k + (int64_t)b * N * ldkv + h * 64;
+  const T* vb = v + (int64_t)b * N * ldkv + h * 64;
+  char* ks = smem;
+  char* vs = smem + L::K_BYTES;
+  float4* part_u = reinterpret_cast<float4*>(smem);                 // [4 waves][8 groups][64 lanes]
+  float4* part_w = part_u + 4 * 8 * 64;
+  float* part_d = reinterpret_cast<float*>(part_w + 4 * 8 * 64);    // [4 waves][64 lanes]
+  bf16x8_t i0, i1;
+  if constexpr (sizeof(T) == 2) { i0 = ident_frag<T>(0, l31, half); i1 = ident_frag<T>(1, l31, half); }
+  const int i = qt * 32 + l31;
+  const int64_t prow = (int64_t)b * Kp + min(i, Kp - 1);
+  RowFrag<T> qf, df;
+  qf.load(qr + prow * ldq + h * 64, half);
+  df.load(da + prow * ldda + h * 64, half);
+
+  // pass 1: row maximum and sum
+  float m = -INFINITY, l = 0.f;
+#pragma unroll 1
+  for (int c0 = 0; c0 < N; c0 += C) {
+    const int Nc = min(N - c0, C);
+    if (c0 > 0) __syncthreads();
+    if constexpr (sizeof(T) == 2)
+      stage_rows_bf16<NT, 256>(ks, reinterpret_cast<const bf16_t*>(kb + (int64_t)c0 * ldkv), ldkv, Nc, tid);
+    else
+      stage_rows_f32<NT, 256>(reinterpret_cast<float*>(ks), kb + (int64_t)c0 * ldkv, ldkv, Nc, tid);
+    __syncthreads();
+    int l31v = l31;
+    asm volatile("" : "+v"(l31v));
+#pragma unroll 1
+    for (int t = wave; 32 * t < Nc; t += 4) {      // every tile visited holds a key: mn is finite
+      f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
+      const float mn = fmaxf(m, mask_and_max(sc, t, Nc, half));
+      l = l * exp_scalar<T>(m - mn, scale) + exp_tile<T>(sc, mn, scale);
+      m = mn;
+    }
+  }
+  l += __shfl_xor(l, 32, 64);
+  float2* rowstat = reinterpret_cast<float2*>(smem + stat_off);     // [4 waves][64 lanes], behind the staging area
+  rowstat[wave * 64 + lane] = make_float2(m, l);
+  __syncthreads();                                 // also: everybody is done with the last chunk of pass 1
+  {
+    const float2 s0 = rowstat[lane], s1 = rowstat[64 + lane], s2 = rowstat[128 + lane], s3 = rowstat[192 + lane];
+    m = fmaxf(fmaxf(s0.x, s1.x), fmaxf(s2.x, s3.x));                // N > 288: every wave has seen keys
+    l = (s0.y * exp_scalar<T>(s0.x - m, scale) + s1.y * exp_scalar<T>(s1.x - m, scale)) +
+        (s2.y * exp_scalar<T>(s2.x - m, scale) + s3.y * exp_scalar<T>(s3.x - m, scale));
+  }
+  const float inv = 1.0f / l;
+
+  // pass 2: dP, delta, U = sum (p dp) K, W = sum p K
+  f32x16_t u[2], w[2];
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { u[dt][r] = 0.f; w[dt][r] = 0.f; }
+  float delta = 0.f;
+#pragma unroll 1
+  for (int c0 = 0; c0 < N; c0 += C) {
+    const int Nc = min(N - c0, C);
+    if (c0 > 0) __syncthreads();
+    if constexpr (sizeof(T) == 2) {
+      stage2_bf16<NT, 256>(ks, vs, reinterpret_cast<const bf16_t*>(kb + (int64_t)c0 * ldkv),
+                           reinterpret_cast<const bf16_t*>(vb + (int64_t)c0 * ldkv), ldkv, Nc, tid);
+    } else {
+      stage_rows_f32<NT, 256>(reinterpret_cast<float*>(ks), kb + (int64_t)c0 * ldkv, ldkv, Nc, tid);
+      stage_rows_f32<NT, 256>(reinterpret_cast<float*>(vs), vb + (int64_t)c0 * ldkv, ldkv, Nc, tid);
+    }
+    __syncthreads();
+    int l31v = l31;
+    asm volatile("" : "+v"(l31v));
+#pragma unroll 1
+    for (int t = wave; 32 * t < Nc; t += 4) {      // wave-uniform trip count
+      f32x16_t pt = tile_times_frag<T>(ks, t, qf, l31v, half);
+      (void)mask_and_max(pt, t, Nc, half);
+      (void)exp_tile<T>(pt, m, scale);
+      f32x16_t dp = tile_times_frag<T>(vs, t, df, l31v, half);
+      if constexpr (sizeof(T) == 2) {
+        const char* krow = ks + (32 * t + l31v) * 144 + half * 16;
+        bf16x8_t krows[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) krows[kk] = *reinterpret_cast<const bf16x8_t*>(krow + kk * 32);
+        float pw[16], pp[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          pp[r] = pt[r] * inv;
+          pw[r] = dp[r] * pp[r];                   // P * dP  (P = 0 on padded keys)
+          delta += pw[r];
+        }
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          bf16x8_t ktf[2];
+          transpose_tile<T>(krows, dt, i0, i1, ktf);
+#pragma unroll
+          for (int g2 = 0; g2 < 2; ++g2) {
+            u[dt] = mfma16<T>(ktf[g2], pack8<T>(pw + 8 * g2), u[dt]);
+            w[dt] = mfma16<T>(ktf[g2], pack8<T>(pp + 8 * g2), w[dt]);
+          }
+        }
+      } else {
+        f32x16_t pn;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          pn[r] = pt[r] * inv;
+          dp[r] *= pn[r];
+          delta += dp[r];
+        }
+        contract_keys<T, NT>(ks, t, dp, u, l31v, half);
+        contract_keys<T, NT>(ks, t, pn, w, l31v, half);
+      }
+    }
+  }
+  delta += __shfl_xor(delta, 32, 64);
+  __syncthreads();                                 // everybody is done with the staged K / V
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      part_u[(wave * 8 + dt * 4 + g) * 64 + lane] = make_float4(u[dt][4 * g], u[dt][4 * g + 1], u[dt][4 * g + 2], u[dt][4 * g + 3]);
+      part_w[(wave * 8 + dt * 4 + g) * 64 + lane] = make_float4(w[dt][4 * g], w[dt][4 * g + 1], w[dt][4 * g + 2], w[dt][4 * g + 3]);
+    }
+  part_d[wave * 64 + lane] = delta;
+  __syncthreads();
+  const float dl = (part_d[lane] + part_d[64 + lane]) + (part_d[128 + lane] + part_d[192 + lane]);
+  if (i < Kp) {
+    T* orow = dq + prow * lddq + h * 64;
+#pragma unroll
+    for (int gg = 0; gg < 2; ++gg) {
+      const int gi = wave * 2 + gg, dt = gi >> 2, g = gi & 3;
+      float4 us = make_float4(0.f, 0.f, 0.f, 0.f), ws = us;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) {
+        const float4 a = part_u[(wv * 8 + gi) * 64 + lane], c = part_w[(wv * 8 + gi) * 64 + lane];
+        us.x += a.x; us.y += a.y; us.z += a.z; us.w += a.w;
+        ws.x += c.x; ws.y += c.y; ws.z += c.z; ws.w += c.w;
+      }
+      ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, scale * (us.x - dl * ws.x), scale * (us.y - dl * ws.y),
+                    scale * (us.z - dl * ws.z), scale * (us.w - dl * ws.w));
+    }
+  }
+}
+
+template <typename T>
+int launch_fwd_long(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo, int B, int H,
+                    int N, int Kp, float scale, int q_first, hipStream_t s) {
+  static rpo_lds_mask_t lds_ok{0};
+  auto kern = attn_fwd_long_kernel<T>;
+  constexpr int bytes = AL<T, LONG_NT>::FWD_BYTES;
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
+  const int tiles = ((N + Kp + 31) >> 5) - (q_first >> 5), groups = (tiles + 7) / 8;
+  if ((int64_t)B * H * groups > INT32_MAX) return RPO_E_SHAPE;
+  hipLaunchKernelGGL(kern, dim3(B * H * groups), dim3(512), bytes, s, static_cast<const T*>(q), static_cast<const T*>(k),
+                     static_cast<const T*>(v), ld, static_cast<T*>(out), ldo, B, H, N, Kp, scale, q_first, groups);
+  return rpo_launch_status();
+}
+
+template <typename T>
+int launch_bwd_long(const void* qr, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* da,
+                    int64_t ldda, void* dq, int64_t lddq, int B, int H, int N, int Kp, float scale, hipStream_t s) {
+  static rpo_lds_mask_t lds_ok{0};
+  auto kern = attn_bwd_long_kernel<T>;
+  constexpr int bytes = AL<T, LONG_NT>::BWD_BYTES + 2048;
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
+  const int nqt = (Kp + 31) / 32;
+  if ((int64_t)B * H * nqt > INT32_MAX) return RPO_E_SHAPE;
+  hipLaunchKernelGGL(kern, dim3(B * H * nqt), dim3(256), bytes, s, static_cast<const T*>(qr), ldq,
+                     static_cast<const T*>(k), static_cast<const T*>(v), ldkv, static_cast<const T*>(da), ldda,
+                     static_cast<T*>(dq), lddq, B, H, N, Kp, scale, nqt);
+  return rpo_launch_status();
+}
+
 template <typename T, int NT>
 int launch_fwd2(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo, int B, int H,
                 int N, int Kp, float scale, int q_first, hipStream_t s) {
@@ -1814,12 +2134,17 @@ extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const vo
                                           int q_first, void* stream) {
   if (!q || !k || !v || !out || B <= 0 || H <= 0 || N <= 0 || Kp < 0 || q_first < 0 || q_first >= N + Kp)
     return RPO_E_BADARG;
-  if (N > 288) return RPO_E_SHAPE;
+  if (N > ATTN_LONG_MAX_N) return RPO_E_SHAPE;
   if (dtype != RPO_F32 && dtype != RPO_BF16 && dtype != RPO_F16) return RPO_E_DTYPE;
   const int esz = dtype == RPO_F32 ? 4 : 2;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !ok_ld(ld, esz) ||
       reinterpret_cast<uintptr_t>(out) % (4 * esz) || (ldo * esz) % (4 * esz)) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (N > 288) {                                   // the keys in chunks (attn_fwd_long_kernel)
+    if (dtype == RPO_BF16) return launch_fwd_long<bf16_t>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
+    if (dtype == RPO_F16) return launch_fwd_long<f16_t>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
+    return launch_fwd_long<float>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
+  }
   if (dtype == RPO_BF16) {
     if (N <= 224) return launch_fwd<bf16_t, 7>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
     return launch_fwd<bf16_t, 9>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
@@ -1859,13 +2184,18 @@ extern "C" int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void
                                      int64_t ldkv, const void* da, int64_t ldda, void* dq, int64_t lddq,
                                      int dtype, int B, int H, int N, int Kp, float scale, void* stream) {
   if (!q_rows || !k || !v || !da || !dq || B <= 0 || H <= 0 || N <= 0 || Kp <= 0) return RPO_E_BADARG;
-  if (N > 288 || Kp > 128) return RPO_E_SHAPE;
+  if (N > ATTN_LONG_MAX_N || Kp > 128) return RPO_E_SHAPE;
   if (dtype != RPO_F32 && dtype != RPO_BF16 && dtype != RPO_F16) return RPO_E_DTYPE;
   const int esz = dtype == RPO_F32 ? 4 : 2;
   if (!aligned16(q_rows) || !aligned16(k) || !aligned16(v) || !aligned16(da) || !ok_ld(ldq, esz) ||
       !ok_ld(ldkv, esz) || !ok_ld(ldda, esz) || reinterpret_cast<uintptr_t>(dq) % (4 * esz) ||
       (lddq * esz) % (4 * esz)) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (N > 288) {                                   // the keys in chunks (attn_bwd_long_kernel)
+    if (dtype == RPO_BF16) return launch_bwd_long<bf16_t>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
+    if (dtype == RPO_F16) return launch_bwd_long<f16_t>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
+    return launch_bwd_long<float>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
+  }
   if (dtype == RPO_BF16) {
     if (N <= 224) return launch_bwd<bf16_t, 7>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
     return launch_bwd<bf16_t, 9>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);

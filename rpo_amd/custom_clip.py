@@ -82,6 +82,8 @@ def config_from_state_dict(sd, K: int, n_cls: int, name: Optional[str] = None) -
     layers_t = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks.")})
     if name is None:
         name = {(768, 16): "ViT-B/16", (768, 32): "ViT-B/32", (1024, 14): "ViT-L/14"}.get((d_v, patch), f"ViT-{d_v}/{patch}")
+        if (d_v, patch, grid) == (1024, 14, 24):
+            name = "ViT-L/14@336px"
     return RPOConfig(name=name, image_size=grid * patch, patch=patch, d_v=d_v, layers_v=layers_v, d_t=d_t,
                      layers_t=layers_t, context=context, vocab=vocab, embed=embed, K=K, n_cls=n_cls)
 

@@ -30,7 +30,7 @@ import os
 
 from ._lib import (EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_NONE, EPI_PATCH,
                    EPI_QGELU_BWD)
-from .config import RPOConfig
+from .config import ATTN_LDS_TOKENS, RPOConfig
 from .engine_coop import CoopEngineMixin
 from .engine_lp import LpEngineMixin
 from .engine_multi import MultiEngineMixin
@@ -504,11 +504,13 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         # Rows never mix inside a GEMM, so results are those of the whole-stream launches up to the tile shapes' summation
         # order.  Measured 3 % SLOWER at K = 48 (profiles/r04_ab_split_k48.txt); never taken by this class (_split_rows).
         split = self._split_rows(B)
+        # N + K rows above the row-unit kernels' 288 (ViT-L/14 at 336 px: 601): no hint, the GEMMs choose by shape
+        long_grid = N > ATTN_LDS_TOKENS
         # small batches: every "wide" launch is a small-M GEMM and goes to rpo_gemm_ws (no row units, 64-column statistics)
         # (measured, tools/ab_env.py --extra "--batch B": B = 4 step 1.509 vs 1.554 ms, B = 8 1.958 vs 1.723 ms -- from
         #  1024 rows on the 64x128 / 128x128 tiles win; the unmasked towers (full_last: zero-shot / CoOp) keep rpo_gemm_nt)
         small = self.ws_small and R < 1024 and not split and not full_last
-        if small:
+        if small or long_grid:
             units = None
         Mw = Rf if split else R                                       # rows of the whole-batch ("wide") launches
         if split:
@@ -763,7 +765,9 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         # 16-bit modes, K <= 64, d = 512 / 768 / 1024: the d out-proj GEMM runs inside the attention backward kernel
         # (round 4: d = 1024 -- ViT-L/14 -- and K in (32, 64] -- one workgroup per 32-query tile)
         kmax, widths = self._bwd_fold_limits()
-        fold_out = (self.act != torch.float32 and K <= kmax and dv in widths and os.environ.get("RPO_NO_BWD_FOLD") != "1")
+        # (rpo_attn_readonly_bwd_proj stages all keys of an image at once: above 288 frozen tokens the two launches)
+        fold_out = (self.act != torch.float32 and K <= kmax and dv in widths and N <= ATTN_LDS_TOKENS
+                    and os.environ.get("RPO_NO_BWD_FOLD") != "1")
 
         def attn_bwd(l, da, dq):
             qkv = self.qkv[l]

@@ -22,6 +22,7 @@ from typing import List, Optional
 import torch
 
 from . import ops
+from .config import refuse_long_grid
 from ._lib import EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_NONE
 
 SCALE = 0.125                       # 1 / sqrt(head_dim = 64)
@@ -54,6 +55,7 @@ class PromptRowsEngineMixin:
         """Buffers of the prompt-row pass for S prompt sets and chunks of up to B images.  Allocates nothing the existing
         paths use and changes none of their buffers; a second call with a smaller or equal problem keeps what is there."""
         self._refuse_rn("prompt_rows_setup")
+        refuse_long_grid(self.cfg, "Engine.prompt_rows_setup")
         if S < 1 or B < 1:
             raise ValueError(f"prompt_rows_setup: S = {S}, B = {B}: both must be >= 1")
         cfg, dev, act = self.cfg, self.dev, self.act

@@ -52,6 +52,8 @@ class ExperimentalEngine(Engine):
         mode = _xenv("RPO_SPLIT", "0")          # "1": where the whole rows do not fit; "force": wherever the frozen rows do
         if self.act == torch.float32 or not self.fold_ln or mode not in ("1", "force") or cfg.K == 0:
             return False
+        if cfg.n_frozen > 288:                  # no row-unit kernel takes an image's rows: nothing to split for
+            return False
         key = ("split", B)
         if key not in self._stats_group:
             N, K, dv = cfg.n_frozen, cfg.K, cfg.d_v
@@ -74,6 +76,8 @@ class ExperimentalEngine(Engine):
         cfg = self.cfg
         if tower == "v":
             if _xenv("RPO_CHAIN_IMAGE", "1") == "0":     # (text tower alone: RPO_CHAIN=1 RPO_CHAIN_TEXT=1 RPO_CHAIN_IMAGE=0)
+                return False
+            if cfg.n_frozen > 288:                       # the chain kernel stages all keys of an image at once
                 return False
             return ops.chain_bwd_ok(cfg.layers_v, units, cfg.K, cfg.d_v, cfg.heads_v, cfg.n_frozen, self.act)
         if _xenv("RPO_CHAIN_TEXT", "0") != "1" or self.Lmax > 96:

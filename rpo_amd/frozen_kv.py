@@ -13,6 +13,7 @@ from typing import Optional
 
 import torch
 
+from .config import refuse_long_grid
 from .engine_prompt_rows import PromptKV
 
 
@@ -44,6 +45,7 @@ class FrozenImageKV:
         min(batch_size, engine.max_batch), the last one ragged -- `EvalMixin.test`'s) and keeps every block's K / V.
         Over `budget_bytes`: ValueError naming both byte counts, before anything is allocated."""
         cfg, act = engine.cfg, engine.act
+        refuse_long_grid(cfg, "FrozenImageKV.build")
         n = len(image_set)
         need = cls.bytes_needed(cfg, n, act)
         if budget_bytes is not None and need > budget_bytes:

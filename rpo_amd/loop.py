@@ -19,6 +19,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import ops
+from .config import refuse_long_grid
 from .evaluator import Classification
 
 
@@ -94,6 +95,7 @@ class EvalMixin:
         its slice of the logits; one read-back.  `sides()` -> (img_prompts [S, K, d_v], text_f [S * n_cls * K, e], k_used), called once
         with the device current; k_used is None, or int32 [S] on the device for sets that average over their own number
         of pairs (`RPOSweep`).  `hook(b0, logits [S, B, n_cls])` sees each chunk's logits (the engine's buffer)."""
+        refuse_long_grid(self.cfg, f"{type(self).__name__}: evaluation on shared frozen image rows (test_all, test(frozen=...))")
         eng, n, C = self.engine, len(image_set), self.cfg.n_cls
         if frozen is not None:
             frozen.check(eng, image_set)
@@ -267,6 +269,8 @@ class LoopMixin(EvalMixin):
         if val_frozen is not None and not self._takes_frozen:
             raise NotImplementedError(f"{type(self).__name__}.train: val_frozen is RPO's (its frozen image rows never read a "
                                       "prompt); this trainer evaluates through its own image pass")
+        if val_frozen is not None:
+            refuse_long_grid(self.cfg, f"{type(self).__name__}.train(val_frozen=...)")
         val_kw = {} if val_frozen is None else {"frozen": val_frozen}
         history = []
         while self.epoch < max_epoch:

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import optim as _optim
-from .config import RPOConfig
+from .config import RPOConfig, refuse_long_grid
 from .custom_clip import init_prompts, refuse_rn
 from .loop import EvalMixin, epoch_indices
 from .trainer import OptimConfig, checkpoint_dict, load_checkpoint_file, lr_at_epoch, write_checkpoint
@@ -348,6 +348,7 @@ class RPOMulti(EvalMixin):
         """Dassl's `test()` for EVERY member in one pass over the set: per chunk one frozen image pass (none with `frozen`,
         a `FrozenImageKV` of this set) and one prompt-row pass for all S members.  Returns, per member, the dict
         `test(image_set, member=s)` returns."""
+        refuse_long_grid(self.cfg, f"{type(self).__name__}.test_all")
         return self._test_shared(image_set, self.n_runs, self._shared_sides, batch_size, frozen, verbose, per_class_result,
                                  hook)
 

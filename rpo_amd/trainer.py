@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import optim as _optim
-from .config import RPOConfig
+from .config import RPOConfig, refuse_long_grid
 from .custom_clip import CustomCLIP
 from .dist import GradSync
 from .loop import LoopMixin
@@ -548,6 +548,7 @@ class RPO(LoopMixin):
         pass is run at all, only the K prompt rows per image on the cached frozen K / V (rpo_amd/frozen_kv.py)."""
         if frozen is None:
             return super().test(image_set, batch_size, verbose, per_class_result)
+        refuse_long_grid(self.cfg, "RPO.test(frozen=...)")
         self._join_side()
         return self._test_shared(image_set, 1, self._shared_sides, batch_size, frozen, verbose, per_class_result, hook)[0]
 
