@@ -171,15 +171,42 @@ __device__ __forceinline__ void ln_bwd_row(const TDY* __restrict__ dy, int64_t l
   const int nv4 = d >> 2;
   const float* xr = x + (int64_t)row * ldx;
   const TDY* dyr = dy + (int64_t)row * lddy;
-  // every global load of the row (x, dy slabs, gamma) is issued before the first reduction: the row's
-  // lifetime is then ONE memory round trip plus four wave reductions (these launches are latency-bound)
+  // every global load of the row (x, gamma, the first four dy slabs, dres) is issued before the first use of any of them:
+  // the row's lifetime is then ONE memory round trip plus four wave reductions (these launches are latency-bound).
+  // The loads of ALL column chunks stand in a loop of their own, in front of the arithmetic: written chunk by chunk (loads
+  // and slab sums of chunk i together; -DRPO_LN_BWD_CHUNKED keeps that form for A/B) the run-time slab loop below kept hipcc
+  // from hoisting chunk i + 1's loads over chunk i's sums, and dres was requested behind the last of them: NV + 1 round
+  // trips (read in the ISA: a vmcnt wait per chunk).  Same values, same order of every sum: the same bits.
+  // Step: -1.4 % same-box (2.831-2.840 -> 2.796-2.802 ms, profiles/r07_ab_ln_bwd_batched.txt).
   float4 v[NV], g[NV];
+#ifndef RPO_LN_BWD_CHUNKED
+  float4 wv[NV], tv0[NV], tsv[NV][3], rr[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = lane + 64 * i;
+    rr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < nv4) {
+      if (dres != nullptr) rr[i] = *reinterpret_cast<const float4*>(dres + (int64_t)row * lddres + 4 * c);
+      v[i] = *reinterpret_cast<const float4*>(xr + 4 * c);
+      wv[i] = *reinterpret_cast<const float4*>(gamma + 4 * c);
+      tv0[i] = load4f<TDY>(dyr + 4 * c);
+      // (split-K slabs 1-3: fetched unconditionally with a clamped index and added under a mask below)
+#pragma unroll
+      for (int sp = 1; sp < 4; ++sp) tsv[i][sp - 1] = load4f<TDY>(dyr + (int64_t)min(sp, splits - 1) * split_stride + 4 * c);
+    }
+  }
+#endif
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = lane + 64 * i;
+#ifdef RPO_LN_BWD_CHUNKED
     v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#else
+    if (c >= nv4) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
     g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (c < nv4) {
+#ifdef RPO_LN_BWD_CHUNKED
       v[i] = *reinterpret_cast<const float4*>(xr + 4 * c);
       const float4 w = *reinterpret_cast<const float4*>(gamma + 4 * c);
       // split-K slabs, summed in fixed order.  The first four are fetched unconditionally (clamped index, masked add):
@@ -188,6 +215,11 @@ __device__ __forceinline__ void ln_bwd_row(const TDY* __restrict__ dy, int64_t l
       float4 ts[3];
 #pragma unroll
       for (int sp = 1; sp < 4; ++sp) ts[sp - 1] = load4f<TDY>(dyr + (int64_t)min(sp, splits - 1) * split_stride + 4 * c);
+#else
+      const float4 w = wv[i];
+      float4 t = tv0[i];
+      float4 ts[3] = {tsv[i][0], tsv[i][1], tsv[i][2]};
+#endif
 #pragma unroll
       for (int sp = 1; sp < 4; ++sp) {
         const float m = sp < splits ? 1.0f : 0.0f;
@@ -201,6 +233,7 @@ __device__ __forceinline__ void ln_bwd_row(const TDY* __restrict__ dy, int64_t l
       g[i] = make_float4(t.x * w.x, t.y * w.y, t.z * w.z, t.w * w.w);
     }
   }
+#ifdef RPO_LN_BWD_CHUNKED
   float4 rr[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -208,6 +241,7 @@ __device__ __forceinline__ void ln_bwd_row(const TDY* __restrict__ dy, int64_t l
     rr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (dres != nullptr && c < nv4) rr[i] = *reinterpret_cast<const float4*>(dres + (int64_t)row * lddres + 4 * c);
   }
+#endif
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);

@@ -717,13 +717,16 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
             # (measured and dropped, same-box: a second hint range for what the backward re-reads from the forward pass --
             #  the frozen rows' K / V of the block, 29 MB, named by this GEMM for the attention backward two kernels on:
             #  step 1.8 % SLOWER, 3.045 vs 2.992 ms; the saved QuickGELU operand u[l-1], named by the d q-proj GEMM: no
-            #  effect, 2.875 vs 2.871 ms)
+            #  effect, 2.875 vs 2.871 ms.  The same K / V, 19 MB of K and V columns only, touched ONE launch ahead by the ln_2
+            #  backward below, or V requested earlier in the attention kernel's own prologue: +0.27 % / inside the noise,
+            #  DESIGN.md 11f, profiles/r07_ab_kv_touch.txt -- every host is measured, none pays)
             self._gemm(a_in, blk.w_proj_t, du, EPI_QGELU_BWD, aux=u[l], prefetch=blk.w_fc_t if pf else None, **tc("dproj"))  # d c_proj, d QuickGELU
             dyf = dy[0] if s_fc == 1 else dy[:s_fc]
             self._gemm(du, blk.w_fc_t, dyf, EPI_NONE, split_k=s_fc,
                        prefetch=self._oq_hint(blk, fold_out, ws) if pf else None, **tc("dfc"))    # d c_fc
-            ops.layernorm_bwd(dyf, xm[l], blk.ln2_w, dxa, dxb,
-                              None if self.act == torch.float32 else dxc)
+            with self._timed("ln2_bwd") if blocks is self.vis else _NO_PROBE:         # (tools/probe_ln2_bwd.py)
+                ops.layernorm_bwd(dyf, xm[l], blk.ln2_w, dxa, dxb,
+                                  None if self.act == torch.float32 else dxc)
             a_in = dxb if self.act == torch.float32 else dxc
             if fold_out:
                 attn_bwd(l, a_in, dq)                                             # d out_proj inside the attention kernel

@@ -21,6 +21,7 @@ for r in range(rounds):
         try:
             line = json.loads(out.stdout.strip().splitlines()[-1])
             res[name].append(line["ms_per_step"])
+            print(f"round {r} {name:40s} {line['ms_per_step']:.4f}", flush=True)     # (as it goes: a long A/B shows life)
         except Exception:
             print(name, "FAILED", out.stderr[-800:])
 for name, _ in arms:
