@@ -285,6 +285,20 @@ int rpo_broadcast_rows_sets(const float* src, int64_t src_set_stride, float* dst
 int rpo_reduce_groups_sets(const float* src, int64_t ld, float* out, int64_t out_set_stride, int sets, int groups, int rows,
                            int d, void* stream);
 
+/* (ABI 8 addition) Input rows of a text pass, gathered on the device (make_prompts, trainers/rpo.py:135-136; CoOp's context
+ * slots, trainers/coop.py:136-183): for c < n, p < L
+ *   out[c * L + p, :] = table[ids[c * ld_ids + p], :] + pos[p, :]      for an id >= 0
+ *   out[c * L + p, :] = ctx[-1 - id, :] + pos[p, :]                    for an id < 0 (context slot -1 - id)
+ * ids int32 [n, ld_ids] (only the first L of a row are read), table [vocab, d], pos [>= L, d], ctx [n_ctx, d] or NULL when
+ * n_ctx == 0, out [n * L, d] contiguous; all fp32 device memory, row indices 64-bit.  One fp32 add per element: the bits
+ * of the host expression.  The caller validates ids; the kernel clamps an id into [0, vocab) / a slot into [0, n_ctx)
+ * (a negative id with n_ctx == 0 reads row 0 of table), so no id reads outside the arguments.
+ * A null pointer, n < 1, L < 1, vocab < 1, n_ctx < 0: RPO_E_BADARG; d % 4 != 0 or L > ld_ids: RPO_E_SHAPE; table, pos, ctx
+ * or out not 16-byte aligned: RPO_E_ALIGN -- all with nothing launched.  One launch on `stream`, no allocation,
+ * capturable in a HIP graph. */
+int rpo_text_embed(const int32_t* ids, int64_t ld_ids, const float* table, int vocab, const float* pos, const float* ctx,
+                   int n_ctx, float* out, int n, int L, int d, void* stream);
+
 /* Read-only masked attention of the image tower, all heads (head_dim 64), all B images.
  * q, k, v: act-dtype matrices in the row layout above with leading dimension ld (typically
  * three column slices of one packed [R, 3d] in-proj output).  Every query row (frozen and

@@ -254,8 +254,20 @@ class CoOp(LoopMixin):
         return summary
 
     @torch.no_grad()
-    def model_inference(self, image: torch.Tensor) -> torch.Tensor:
-        return self.model(image)
+    def model_inference(self, image: torch.Tensor, classes=None) -> torch.Tensor:
+        """logits [B, n_cls]; `classes`: a `ClassSet` (`class_set(tokens)`) -- logits [B, n'] against it."""
+        if classes is None:
+            return self.model(image)
+        with torch.cuda.device(self.device):
+            image = image.to(device=self.device, dtype=torch.float32).contiguous()
+            return self._class_logits(image, classes).clone()
+
+    def _class_logits(self, image: torch.Tensor, classes) -> torch.Tensor:
+        """The plain towers against a class set whose prompts carry the CURRENT generic context, placed by the layout rule
+        of the trainer's class-token position (Engine.class_plain_features)."""
+        eng = self.engine
+        text_f = eng.class_plain_features(classes, eng.coop_ctx, eng.coop_position)
+        return eng._cs_forward_plain(image, classes, text_f)
 
 
 class CoCoOpPromptLearner(CoOpPromptLearner):

@@ -87,6 +87,30 @@ __global__ void broadcast_rows_kernel(const float* __restrict__ src, float* dst,
   for (int i = threadIdx.x; i < d; i += blockDim.x) o[i] = s[i];
 }
 
+// Token embedding + positional embedding of a text pass's input rows (make_prompts, trainers/rpo.py:135-136; CoOp's
+// context slots, trainers/coop.py:136-183), gathered on the device: pure byte work, 2 reads + 1 write of rows * d floats.
+// One workgroup per row under a grid-stride loop: the row's id is one load at a workgroup-uniform address, every lane
+// moves 16 bytes per access, no LDS.  An id is clamped into its table, so no id reads outside the arguments.
+__global__ __launch_bounds__(128) void text_embed_kernel(const int32_t* __restrict__ ids, int64_t ld_ids,
+                                                         const float4* __restrict__ table, int vocab,
+                                                         const float4* __restrict__ pos, const float4* __restrict__ ctx,
+                                                         int n_ctx, float4* __restrict__ out, int64_t rows, int L, int d4) {
+  for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int64_t c = r / L;
+    const int p = (int)(r - c * L);
+    const int id = ids[c * ld_ids + p];
+    const float4* src;
+    if (id < 0 && n_ctx > 0) src = ctx + (int64_t)min(-1 - id, n_ctx - 1) * d4;
+    else src = table + (int64_t)min(max(id, 0), vocab - 1) * d4;
+    const float4* pe = pos + (int64_t)p * d4;
+    float4* o = out + r * d4;
+    for (int i = threadIdx.x; i < d4; i += 128) {
+      const float4 a = src[i], b = pe[i];
+      o[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+  }
+}
+
 __global__ void reduce_groups_kernel(const float* __restrict__ src, int64_t ld, float* out, int groups, int rows,
                                      int d, int64_t out_stride) {
   src += (int64_t)blockIdx.y * groups * rows * ld;                  // blockIdx.y: the set (rpo_reduce_groups_sets)
@@ -938,6 +962,20 @@ extern "C" int rpo_broadcast_rows_sets(const float* src, int64_t src_set_stride,
   if ((int64_t)sets * groups * rows >= (1ll << 31)) return RPO_E_SHAPE;
   hipLaunchKernelGGL(broadcast_rows_kernel, dim3(sets * groups * rows), dim3(256), 0, static_cast<hipStream_t>(stream),
                      src, dst, ld, rows, d, groups * rows, src_set_stride);
+  return rpo_launch_status();
+}
+
+extern "C" int rpo_text_embed(const int32_t* ids, int64_t ld_ids, const float* table, int vocab, const float* pos,
+                              const float* ctx, int n_ctx, float* out, int n, int L, int d, void* stream) {
+  if (!ids || !table || !pos || !out || n < 1 || L < 1 || vocab < 1 || n_ctx < 0 || (n_ctx > 0 && !ctx)) return RPO_E_BADARG;
+  if (d < 4 || d % 4 != 0 || L > ld_ids) return RPO_E_SHAPE;
+  if (!aligned16(table) || !aligned16(pos) || !aligned16(out) || (n_ctx > 0 && !aligned16(ctx))) return RPO_E_ALIGN;
+  const int64_t rows = (int64_t)n * L;
+  const int grid = (int)(rows < 4096 ? rows : 4096);            // 16 workgroups of two waves per CU, then the stride loop
+  hipLaunchKernelGGL(text_embed_kernel, dim3(grid), dim3(128), 0, static_cast<hipStream_t>(stream), ids, ld_ids,
+                     reinterpret_cast<const float4*>(table), vocab, reinterpret_cast<const float4*>(pos),
+                     reinterpret_cast<const float4*>(n_ctx > 0 ? ctx : nullptr), n_ctx, reinterpret_cast<float4*>(out), rows, L,
+                     d / 4);
   return rpo_launch_status();
 }
 

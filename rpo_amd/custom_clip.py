@@ -176,13 +176,16 @@ class CustomCLIP(nn.Module):
             act_dtype = act_dtype_for_prec(prec)
         return rcfg, sd, toks, act_dtype
 
-    def forward(self, image: torch.Tensor, label: Optional[torch.Tensor] = None):
+    def forward(self, image: torch.Tensor, label: Optional[torch.Tensor] = None, classes=None):
         with torch.cuda.device(self.engine.dev):
-            return self._forward(image, label)
+            return self._forward(image, label, classes)
 
-    def _forward(self, image: torch.Tensor, label: Optional[torch.Tensor] = None):
+    def _forward(self, image: torch.Tensor, label: Optional[torch.Tensor] = None, classes=None):
         image = image.to(device=self.engine.dev, dtype=torch.float32).contiguous()
         if self.prompt_learner.training:
+            if classes is not None:
+                raise NotImplementedError("CustomCLIP: training on another class set is out of scope; a ClassSet is for "
+                                          "evaluation (prompt_learner.eval())")
             if label is None:
                 raise ValueError("training forward needs labels (trainers/rpo.py:229-230)")
             if not label.is_cuda and label.numel() and (int(label.min()) < 0 or int(label.max()) >= self.cfg.n_cls):
@@ -190,14 +193,15 @@ class CustomCLIP(nn.Module):
             label = label.to(device=self.engine.dev, dtype=torch.int64)
             tp, ip = self.prompt_learner()
             return _StepFunction.apply(tp, ip, self.engine, image, label)
-        return self.eval_logits(image).clone()
+        return self.eval_logits(image, classes).clone()
 
-    def eval_logits(self, image: torch.Tensor) -> torch.Tensor:
-        """The eval forward's logits as the engine's own buffer (valid until the next forward); `forward` clones it."""
+    def eval_logits(self, image: torch.Tensor, classes=None) -> torch.Tensor:
+        """The eval forward's logits as the engine's own buffer (valid until the next forward); `forward` clones it.
+        `classes`: a `ClassSet` of the engine -- its logits buffer."""
         with torch.no_grad():
             # prompts may have been edited through the nn.Parameter views: a cheap version key
             ver = (self.prompt_learner.text_prompt._version, self.prompt_learner.img_prompt._version)
             if ver != getattr(self, "_seen_version", None):
                 self.engine.params_version += 1
                 self._seen_version = ver
-            return self.engine.forward_eval(image)
+            return self.engine.forward_eval(image, classes=classes)

@@ -30,6 +30,7 @@ import os
 
 from ._lib import (EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_NONE, EPI_PATCH,
                    EPI_QGELU_BWD)
+from .class_set import ClassSetEngineMixin
 from .config import ATTN_LDS_TOKENS, RPOConfig
 from .engine_coop import CoopEngineMixin
 from .engine_lp import LpEngineMixin
@@ -72,7 +73,8 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin):
+class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin,
+             ClassSetEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under
@@ -838,10 +840,13 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
                                    self.da_t, self.dq_t, self.dy_t, attn_bwd, fold_out=False, tt=self._text_tiles)
 
     # ------------------------------------------------------------------ public
-    def forward_eval(self, image: torch.Tensor, use_graph: bool = True) -> torch.Tensor:
+    def forward_eval(self, image: torch.Tensor, use_graph: bool = True, classes=None) -> torch.Tensor:
         """logits[B, n_cls] (trainers/rpo.py:232).  The image tower + head of a batch size are captured in a HIP graph
         on first use and replayed afterwards: launched eagerly the ~100 kernels of this path are launch-bound
-        (round 1: 6.4 ms per 100 images)."""
+        (round 1: 6.4 ms per 100 images).  `classes`: a `ClassSet` of this engine -- logits [B, n'] against ITS classes,
+        in its own buffer (rpo_amd/class_set.py); nothing of the built-in classes is read or written."""
+        if classes is not None:
+            return self._cs_forward_eval(image, classes, use_graph)
         self._refuse_rn("forward_eval")
         B = self._check(image)
         main = torch.cuda.current_stream()
@@ -898,13 +903,18 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         self.text_cache_ready = False
         self.plain_text_f = None
         self.text_f_version = -1
+        self._plain_ctx = c.clone()                 # (class sets follow the context: rpo_amd/class_set.py)
+        self.ctx_version += 1
 
-    def forward_plain(self, image: torch.Tensor) -> torch.Tensor:
+    def forward_plain(self, image: torch.Tensor, classes=None) -> torch.Tensor:
         """Plain CLIP inference, logits[B, n_cls] = CLIP.forward(image, tokens) (clip/model.py:344-372): what
         trainers/zsclip.py:58-63 computes, and the towers the sibling trainers call (trainers/coop.py:196-208).
         No token reads a prompt (section 2 of DESIGN.md), so the frozen rows of this engine ARE the unmasked towers:
         the image feature is ln_post + proj of the CLS row of a complete last block, the text feature the EOT row of the
-        frozen-token pass that fills the K / V cache.  The prompts play no part."""
+        frozen-token pass that fills the K / V cache.  The prompts play no part.  `classes`: a `ClassSet` of this engine
+        -- logits [B, n'] against its classes, in its own buffer."""
+        if classes is not None:
+            return self._cs_forward_plain(image, classes)
         cfg = self.cfg
         B = self._check(image)
         N, dv, e, n = cfg.n_frozen, cfg.d_v, cfg.embed, cfg.n_cls

@@ -17,6 +17,34 @@ SCALE = 0.125                       # 1 / sqrt(head_dim = 64)
 SPLIT_FC, SPLIT_Q = 3, 2            # split-K factors of the two fp32-output dX GEMMs on rpo_gemm_nt (engine.py)
 
 
+def coop_layout_of(lengths, n_ctx: int, class_token_position: str = "end", L: Optional[int] = None):
+    """The layout rule of `CoopEngineMixin.coop_layout` as a pure function of the prompts' lengths (SOS .. EOT, one per
+    class), n_ctx and the class-token position: (src [n, L], ctx_pos [n, n_ctx]) over the first L positions (default:
+    the longest prompt).  Used for the engine's own classes and for any other class set (rpo_amd/class_set.py)."""
+    assert class_token_position in ("end", "middle", "front"), class_token_position    # `else: raise ValueError`, :185
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    n = lengths.shape[0]
+    L = int(lengths.max()) if L is None else int(L)
+    src = np.tile(np.arange(L, dtype=np.int64), (n, 1))
+    ctx_pos = np.zeros((n, n_ctx), dtype=np.int64)
+    half = n_ctx // 2
+    for c in range(n):
+        nl = int(lengths[c]) - n_ctx - 3
+        assert nl >= 1, "tokens must be the ids of the 'X X .. name.' prompts with n_ctx placeholders"
+        name = np.arange(1 + n_ctx, 1 + n_ctx + nl)
+        if class_token_position == "end":
+            cp = np.arange(1, 1 + n_ctx)
+        elif class_token_position == "middle":
+            cp = np.concatenate([np.arange(1, 1 + half), np.arange(1 + half + nl, 1 + n_ctx + nl)])
+            src[c, 1 + half:1 + half + nl] = name
+        else:
+            cp = np.arange(1 + nl, 1 + nl + n_ctx)
+            src[c, 1:1 + nl] = name
+        src[c, cp] = -1
+        ctx_pos[c] = cp
+    return src, ctx_pos
+
+
 class CoopEngineMixin:
     # ------------------------------------------------------------------ CoOp / CoCoOp: training context vectors
     def coop_layout(self, n_ctx: int, class_token_position: str = "end"):
@@ -26,25 +54,7 @@ class CoopEngineMixin:
         "middle": [SOS | ctx[:n/2] | name | ctx[n/2:] | . EOT]; "front": [SOS | name | ctx | . EOT].  name_len of a class
         = its prompt length - n_ctx - 3 (SOS, '.', EOT), i.e. `len(_tokenizer.encode(name))` (:99)."""
         assert class_token_position in ("end", "middle", "front"), class_token_position    # `else: raise ValueError`, :185
-        n, L = self.cfg.n_cls, self.Lmax
-        src = np.tile(np.arange(L, dtype=np.int64), (n, 1))
-        ctx_pos = np.zeros((n, n_ctx), dtype=np.int64)
-        half = n_ctx // 2
-        for c in range(n):
-            nl = int(self.len_np[c]) - n_ctx - 3
-            assert nl >= 1, "tokens must be the ids of the 'X X .. name.' prompts with n_ctx placeholders"
-            name = np.arange(1 + n_ctx, 1 + n_ctx + nl)
-            if class_token_position == "end":
-                cp = np.arange(1, 1 + n_ctx)
-            elif class_token_position == "middle":
-                cp = np.concatenate([np.arange(1, 1 + half), np.arange(1 + half + nl, 1 + n_ctx + nl)])
-                src[c, 1 + half:1 + half + nl] = name
-            else:
-                cp = np.arange(1 + nl, 1 + nl + n_ctx)
-                src[c, 1:1 + nl] = name
-            src[c, cp] = -1
-            ctx_pos[c] = cp
-        return src, ctx_pos
+        return coop_layout_of(self.len_np, n_ctx, class_token_position, self.Lmax)
 
     def coop_setup(self, n_ctx: int, replicas: int = 1, meta_hidden: int = 0, csc: bool = False,
                    class_token_position: str = "end") -> None:

@@ -151,18 +151,55 @@ class PromptRowsEngineMixin:
         self._gemm(self.pr_y_post[:R], self.img_proj_t, self.pr_img_f[:R], EPI_NONE)
         return self.pr_img_f[:R]
 
-    def _prompt_rows_body(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor, k_used=None) -> None:
-        S, K, e, n = img_prompts.shape[0], self.cfg.K, self.cfg.embed, self.cfg.n_cls
+    def _prompt_rows_body(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor, k_used=None,
+                          n: Optional[int] = None, logits: Optional[torch.Tensor] = None, head_ws=None) -> None:
+        """n / logits / head_ws: a class set's count and buffers (shared_eval_logits(classes=...)); default: the built-in's."""
+        S, K, e = img_prompts.shape[0], self.cfg.K, self.cfg.embed
+        n = self.cfg.n_cls if n is None else n
+        logits, head_ws = (self.pr_logits, self.pr_head_ws) if logits is None else (logits, head_ws)
         img_f = self.image_prompt_rows(B, kv, img_prompts)
         ops.head_fwd_bwd_grouped(img_f.view(S * B, K, e), text_f.view(S * n, K, e), None, self.logit_scale_exp,
-                                 self.pr_logits[:S * B], None, None, None, self.pr_head_ws, S, k_used=k_used)
+                                 logits[:S * B], None, None, None, head_ws, S, k_used=k_used)
+
+    def _shared_eval_logits_cs(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor, use_graph: bool,
+                               cs) -> torch.Tensor:
+        """`shared_eval_logits` against a class set: the prompt-row pass is the engine's own, the grouped head reads the
+        set's features and writes the set's logits.  Graphs are keyed per (S, B, K / V source) and live on the class set
+        (with the K / V source they read, so neither outlives the other's addresses)."""
+        self._cs_check(cs)
+        S, n = img_prompts.shape[0], cs.n
+        assert text_f.shape[0] == S * n * self.cfg.K and text_f.is_contiguous()
+        if B > self.pr_B or S > self.pr_S:
+            raise RuntimeError(f"shared_eval_logits: S = {S}, B = {B}; prompt_rows_setup({self.pr_S}, {self.pr_B})")
+        sh = cs.shared_buffers(S, B)
+        body = lambda: self._prompt_rows_body(B, kv, img_prompts, text_f, None, n, sh["logits"], sh["head_ws"])
+        if not use_graph or os.environ.get("RPO_NO_EVAL_GRAPH") == "1":
+            body()
+            return sh["logits"][:S * B].view(S, B, n)
+        key = ("shared", id(kv), self.pr_gen, sh["gen"], S, B, img_prompts.data_ptr(), img_prompts.stride(0), text_f.data_ptr())
+        entry = cs.graphs.get(key)
+        if entry is None:
+            body()                                                             # eager warm-up: sets kernel attributes
+            torch.cuda.synchronize(self.dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                body()
+            entry = cs.graphs[key] = (g, kv)
+        entry[0].replay()
+        return sh["logits"][:S * B].view(S, B, n)
 
     def shared_eval_logits(self, B: int, kv: PromptKV, img_prompts: torch.Tensor, text_f: torch.Tensor,
-                           use_graph: bool = True, k_used: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           use_graph: bool = True, k_used: Optional[torch.Tensor] = None, classes=None) -> torch.Tensor:
         """logits [S, B, n_cls] (the engine's own buffer, valid until the next call) of the S prompt sets for the chunk `kv`
         names: the prompt-row pass and the grouped head, ONE HIP graph per (S, B) and K / V source on the current
         stream -- eager warm-up first, then capture, as `forward_eval`.  text_f [S * n_cls * K, e]: the sets' text features.
-        k_used: int32 [S] on the device -- set s averages over its first k_used[s] pairs (rpo_head_fwd_bwd_grouped_k)."""
+        k_used: int32 [S] on the device -- set s averages over its first k_used[s] pairs (rpo_head_fwd_bwd_grouped_k).
+        classes: a `ClassSet` of this engine -- logits [S, B, n'] in its buffer, text_f [S * n' * K, e] its features."""
+        if classes is not None:
+            if k_used is not None:
+                raise NotImplementedError("shared_eval_logits(classes=...) with k_used: members that use fewer than the "
+                                          "engine's K pairs (RPOSweep) are not built for class sets")
+            return self._shared_eval_logits_cs(B, kv, img_prompts, text_f, use_graph, classes)
         S, n = img_prompts.shape[0], self.cfg.n_cls
         assert text_f.shape[0] == S * n * self.cfg.K and text_f.is_contiguous()
         if S * B > self.pr_logits.shape[0] or B > self.pr_B or S > self.pr_S:

@@ -5,6 +5,7 @@ DESIGN.md 9j) is built on it."""
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional
 
 import numpy as np
@@ -50,6 +51,15 @@ class TextEncodeEngineMixin:
         ops.layernorm_fwd(eot, self.ln_final[0], self.ln_final[1], y)
         return ops.gemm_nt(y, self.text_proj_t, out, EPI_NONE)
 
+    def _text_tables(self):
+        """(token_embedding.weight [vocab, d_t], positional_embedding [context, d_t]) as fp32 device tensors for
+        rpo_text_embed: uploaded on the first call that needs them (101 MB at CLIP's vocabulary) and kept; attributes of
+        the engine, so `hbm_bytes()` counts them."""
+        if getattr(self, "_tok_emb_dev", None) is None:
+            self._tok_emb_dev = self._f32(np.asarray(self._tok_emb_host))
+            self._pos_dev = self._f32(np.asarray(self._pos_host))
+        return self._tok_emb_dev, self._pos_dev
+
     # prompts per pass of encode_text: bounds its workspace to TEXT_CHUNK * 77 rows of [fp32 x 2 | act x 9] d_t-wide
     # buffers -- 0.26 GB in the 16-bit modes and 0.44 GB in f32 at d_t = 512 if every prompt filled the context; a chunk
     # allocates for its own longest prompt (class-name prompts: 10-20 tokens, a quarter of that).  Measured at 7 000 and
@@ -67,7 +77,9 @@ class TextEncodeEngineMixin:
         see the note at TEXT_CHUNK); each pass runs the positions up to ITS longest prompt -- what follows a prompt's
         EOT cannot reach the EOT row under the causal mask -- through the block sequence of `cache_text_kv`, keeps no
         K / V, and ends in ln_final + text_projection of the EOT rows as `forward_plain` does.  The token embeddings of
-        a chunk are gathered on the host from the state dict's table (held by reference, never copied) and uploaded."""
+        a chunk are gathered on the device (rpo_text_embed: the pass uploads its int32 ids; the fp32 table and the
+        positional embedding are uploaded once, on the first call that needs them); RPO_TEXT_EMBED_HOST=1 gathers them on
+        the host from the state dict's table (held by reference, never copied) and uploads the rows -- the same bits."""
         cfg = self.cfg
         tokens = np.asarray(tokens)
         assert tokens.ndim == 2 and tokens.shape[1] == cfg.context and tokens.shape[0] >= 1, \
@@ -79,17 +91,27 @@ class TextEncodeEngineMixin:
         chunk = self.TEXT_CHUNK if chunk is None else int(chunk)
         assert chunk >= 1, "chunk: prompts per pass, >= 1"
         lens = tokens.argmax(-1) + 1                                   # EOT has the highest id (clip/model.py:354)
-        # host tensors over the state dict's own memory (no copy of the table): torch's embedding gathers a pass's rows on
-        # the host's threads, numpy's fancy index on one (7 000 prompts: 68 -> 50 ms)
-        table, pos = torch.as_tensor(np.asarray(self._tok_emb_host)), torch.as_tensor(np.asarray(self._pos_host))
-        ids = torch.from_numpy(np.ascontiguousarray(tokens))
+        host = os.environ.get("RPO_TEXT_EMBED_HOST") == "1"
+        if host:
+            # host tensors over the state dict's own memory (no copy of the table): torch's embedding gathers a pass's rows
+            # on the host's threads, numpy's fancy index on one (7 000 prompts: 68 -> 50 ms)
+            table, pos = torch.as_tensor(np.asarray(self._tok_emb_host)), torch.as_tensor(np.asarray(self._pos_host))
+            ids = torch.from_numpy(np.ascontiguousarray(tokens))
+        else:
+            ids = torch.from_numpy(np.ascontiguousarray(tokens.astype(np.int32)))
         with torch.cuda.device(self.dev):
+            if not host:
+                table, pos = self._text_tables()
             out = torch.empty(P, cfg.embed, dtype=torch.float32, device=self.dev)
             for p0 in range(0, P, chunk):
                 p1 = min(P, p0 + chunk)
                 n, L = p1 - p0, int(lens[p0:p1].max())
-                emb = torch.nn.functional.embedding(ids[p0:p1, :L], table) + pos[None, :L]
-                x = emb.reshape(n * L, cfg.d_t).to(device=self.dev, dtype=torch.float32)
+                if host:
+                    emb = torch.nn.functional.embedding(ids[p0:p1, :L], table) + pos[None, :L]
+                    x = emb.reshape(n * L, cfg.d_t).to(device=self.dev, dtype=torch.float32)
+                else:
+                    x = torch.empty(n * L, cfg.d_t, dtype=torch.float32, device=self.dev)
+                    ops.text_embed(ids[p0:p1].to(self.dev), table, pos, x, L)
                 len_i32 = torch.tensor(lens[p0:p1], dtype=torch.int32, device=self.dev)
                 self._text_blocks_plain(x, len_i32, n, L)
                 self._text_eot_features(x, len_i32, n, L, out[p0:p1])

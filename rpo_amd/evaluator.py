@@ -96,3 +96,29 @@ class Classification:
                     print(f"* class: {c} ({name})\ttotal: {n:,}\tcorrect: {int(self.cmat[c, c]):,}\tacc: {a:.1f}%")
                 print(f"* average: {res['mean_perclass_accuracy']:.1f}%")
         return res
+
+
+def harmonic_mean(base: float, new: float) -> float:
+    """The H of the base-to-new tables: 2 b n / (b + n) of the base and new accuracies; 0 where either is 0 (the limit,
+    and what a model that fails one half deserves -- the bare formula divides by zero when both are)."""
+    base, new = float(base), float(new)
+    if base < 0 or new < 0:
+        raise ValueError(f"harmonic_mean: accuracies must be >= 0, got {base}, {new}")
+    if base == 0.0 or new == 0.0:
+        return 0.0
+    return 2.0 * base * new / (base + new)
+
+
+def base_to_new(trainer, base_set, new_set, new_classes, **test_kw) -> dict:
+    """The base-to-new protocol on ONE trained model (scripts/rpo/base2new_test.sh with SUB=base, then SUB=new, in the
+    reference two processes that rebuild CLIP): `trainer.test(base_set)` on the classes it was built with,
+    `trainer.test(new_set, classes=...)` on the new half, and their harmonic mean.  `new_classes`: a `ClassSet` of the
+    trainer's engine, or the new classes' token ids [n', 77] (the set is then built here).  `test_kw` goes to both calls.
+    -> {"base": accuracy, "new": accuracy, "H": harmonic_mean, "base_result": .., "new_result": ..}."""
+    from .class_set import ClassSet
+    if not isinstance(new_classes, ClassSet):
+        new_classes = trainer.class_set(new_classes)
+    base = trainer.test(base_set, **test_kw)
+    new = trainer.test(new_set, classes=new_classes, **test_kw)
+    return {"base": base["accuracy"], "new": new["accuracy"], "H": harmonic_mean(base["accuracy"], new["accuracy"]),
+            "base_result": base, "new_result": new}

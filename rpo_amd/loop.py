@@ -55,16 +55,36 @@ class EvalMixin:
             tfs[key] = DeviceTransform(icfg, is_train, self.device, max_batch, max_image_bytes=16)
         return tfs[key]
 
-    def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
-        """What `model_inference` computes, as the engine's own logits buffer (no clone): valid until the next forward."""
-        return self.model(image)
+    def _eval_logits(self, image: torch.Tensor, classes=None) -> torch.Tensor:
+        """What `model_inference` computes, as the engine's own logits buffer (no clone): valid until the next forward.
+        `classes`: against that `ClassSet` (its own buffer), through the trainer's `_class_logits`."""
+        return self.model(image) if classes is None else self._class_logits(image, classes)
+
+    def _class_logits(self, image: torch.Tensor, classes) -> torch.Tensor:
+        raise NotImplementedError(f"{type(self).__name__}: evaluation on another class set (classes=...) is not built")
+
+    def class_set(self, tokens, chunk=None):
+        """A `ClassSet` (rpo_amd/class_set.py) of int ids [n', 77] for `model_inference` / `test(..., classes=)`: classes
+        the model was not built with -- the new half of a base-to-new split, another dataset's names."""
+        with torch.cuda.device(self.device):
+            return self.engine.class_set(tokens, chunk)
+
+    def _n_classes(self, image_set, classes) -> int:
+        """The class count an evaluation is sized by; with a class set, the set's labels are checked against it (the
+        evaluator kernel indexes the confusion matrix by the label)."""
+        if classes is None:
+            return self.cfg.n_cls
+        self.engine._cs_check(classes)
+        image_set.check_labels(classes.n)
+        return classes.n
 
     @torch.no_grad()
-    def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False):
+    def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, classes=None):
         """Dassl's `test()`: eval transform (resize + center crop) from the resident set, the eval forward,
         `rpo_eval_accumulate` on the same stream, one read-back, `Classification.evaluate()` -> its dict
-        (+ "confusion_matrix").  Runs chunks of min(batch_size, engine.max_batch), the last one ragged."""
-        n, C = len(image_set), self.cfg.n_cls
+        (+ "confusion_matrix").  Runs chunks of min(batch_size, engine.max_batch), the last one ragged.
+        `classes`: a `ClassSet` -- the evaluator and the confusion matrix are sized by ITS class count."""
+        n, C = len(image_set), self._n_classes(image_set, classes)
         chunk = max(1, min(batch_size, self.engine.max_batch))
         ev = Classification(C, per_class_result)
         with torch.cuda.device(self.device):
@@ -78,7 +98,7 @@ class EvalMixin:
             for b0 in range(0, n, chunk):
                 B = min(chunk, n - b0)
                 image = tf.from_set(image_set, range(b0, b0 + B), out=bufs[chunk][:B])
-                logits = self._eval_logits(image)
+                logits = self._eval_logits(image) if classes is None else self._eval_logits(image, classes=classes)
                 ops.eval_accumulate(logits, image_set.labels_dev[b0:b0 + B], counts, cmat)
             ev.process_counts(counts.cpu().numpy(), cmat.cpu().numpy())         # the one read-back
         res = ev.evaluate(verbose=verbose)
@@ -88,15 +108,16 @@ class EvalMixin:
 
     @torch.no_grad()
     def _test_shared(self, image_set, S: int, sides, batch_size: int = 100, frozen=None, verbose: bool = True,
-                     per_class_result: bool = False, hook=None) -> List[dict]:
+                     per_class_result: bool = False, hook=None, classes=None) -> List[dict]:
         """`test` for S prompt sets at once on the shared frozen image rows (rpo_amd/engine_prompt_rows.py): per chunk
         (those of `test`) one frozen pass -- none with `frozen`, a `FrozenImageKV` of this set -- and ONE prompt-row pass +
         grouped head for all sets; every set has its own counts / confusion matrix, filled by `rpo_eval_accumulate` on
         its slice of the logits; one read-back.  `sides()` -> (img_prompts [S, K, d_v], text_f [S * n_cls * K, e], k_used), called once
         with the device current; k_used is None, or int32 [S] on the device for sets that average over their own number
-        of pairs (`RPOSweep`).  `hook(b0, logits [S, B, n_cls])` sees each chunk's logits (the engine's buffer)."""
+        of pairs (`RPOSweep`).  `hook(b0, logits [S, B, n_cls])` sees each chunk's logits (the engine's buffer).
+        `classes`: a `ClassSet` -- `sides()` then returns ITS text features [S * n' * K, e]; everything is sized by n'."""
         refuse_long_grid(self.cfg, f"{type(self).__name__}: evaluation on shared frozen image rows (test_all, test(frozen=...))")
-        eng, n, C = self.engine, len(image_set), self.cfg.n_cls
+        eng, n, C = self.engine, len(image_set), self._n_classes(image_set, classes)
         if frozen is not None:
             frozen.check(eng, image_set)
         chunk = max(1, min(batch_size, eng.max_batch))
@@ -121,7 +142,7 @@ class EvalMixin:
                 else:
                     kv = frozen.kv
                     kv.set_first(b0, B)
-                logits = eng.shared_eval_logits(B, kv, img_prompts, text_f, k_used=k_used)
+                logits = eng.shared_eval_logits(B, kv, img_prompts, text_f, k_used=k_used, classes=classes)
                 if hook is not None:
                     hook(b0, logits)
                 for s in range(S):

@@ -181,9 +181,18 @@ class LP(LoopMixin):
         return summary
 
     @torch.no_grad()
-    def model_inference(self, image: torch.Tensor) -> torch.Tensor:
-        """logits [B, n_cls] for a test batch (up to max_batch images: the yaml's 100)."""
-        return self.model(image)
+    def model_inference(self, image: torch.Tensor, classes=None) -> torch.Tensor:
+        """logits [B, n_cls] for a test batch (up to max_batch images: the yaml's 100); `classes`: a `ClassSet`
+        (`class_set(tokens)`) -- logits [B, n'] against it."""
+        if classes is None:
+            return self.model(image)
+        with torch.cuda.device(self.device):
+            image = image.to(device=self.device, dtype=torch.float32).contiguous()
+            return self._class_logits(image, classes).clone()
+
+    def _class_logits(self, image: torch.Tensor, classes) -> torch.Tensor:
+        """lp_layer on the image feature, then the class set's normalised text features (Engine._cs_lp_forward)."""
+        return self.engine._cs_lp_forward(image, classes)
 
     # -- checkpoints in Dassl's layout (the reader: trainers/linear_prob.py:193-225) ----------------------------------------
     def checkpoint_dict(self, epoch: Optional[int] = None, val_result: Optional[float] = None) -> dict:

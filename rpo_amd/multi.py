@@ -299,28 +299,39 @@ class RPOMulti(EvalMixin):
             self._eval_member = member
 
     @torch.no_grad()
-    def model_inference(self, image: torch.Tensor, member: int = 0) -> torch.Tensor:
-        """logits [B, n_cls] of member `member` (trainers/rpo.py:229-232 eval branch, through `Engine.forward_eval`)."""
+    def model_inference(self, image: torch.Tensor, member: int = 0, classes=None) -> torch.Tensor:
+        """logits [B, n_cls] of member `member` (trainers/rpo.py:229-232 eval branch, through `Engine.forward_eval`);
+        `classes`: a `ClassSet` (`class_set(tokens)`) -- logits [B, n'] against it."""
         with torch.cuda.device(self.device):
             self._select(member)
             image = image.to(device=self.device, dtype=torch.float32).contiguous()
-            return self.engine.forward_eval(image).clone()
+            return self.engine.forward_eval(image, classes=classes).clone()
 
-    def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
-        return self.engine.forward_eval(image)
+    def _eval_logits(self, image: torch.Tensor, classes=None) -> torch.Tensor:
+        return self.engine.forward_eval(image, classes=classes)
 
-    def test(self, image_set, member: int = 0, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False):
-        """Dassl's `test()` for member `member` (loop.EvalMixin.test)."""
+    def test(self, image_set, member: int = 0, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False,
+             classes=None):
+        """Dassl's `test()` for member `member` (loop.EvalMixin.test); `classes`: against that `ClassSet`."""
         with torch.cuda.device(self.device):
             self._select(member)
-        return super().test(image_set, batch_size, verbose, per_class_result)
+        return super().test(image_set, batch_size, verbose, per_class_result, classes=classes)
 
     # ------------------------------------------------------------------ evaluation: all members per frozen image pass
-    def _shared_sides(self):
+    def _shared_sides(self, classes=None):
         """(img_prompts [S, K, d_v], text_f [S * n_cls * K, e], k_used): k_used is None here -- every member averages over
-        all K pairs; `RPOSweep` returns its members' own K as int32 [S] on the device."""
+        all K pairs; `RPOSweep` returns its members' own K as int32 [S] on the device.  `classes`: the members' text
+        features of that `ClassSet`, computed one member after the other through the single-run parameters."""
         eng = self.engine
-        return eng.m_img_prompt, eng.multi_text_features(), None
+        if classes is None:
+            return eng.m_img_prompt, eng.multi_text_features(), None
+        S, rows = self.n_runs, classes.n * self.cfg.K
+        text_f = classes.shared_buffers(S, 1)["text_f"][:S * rows]
+        for s in range(S):
+            eng.multi_load_member(s)
+            eng.class_text_features(classes, out=text_f[s * rows:(s + 1) * rows])
+        self._eval_member = S - 1                    # (whose prompts the single-run parameters now hold)
+        return eng.m_img_prompt, text_f, None
 
     @torch.no_grad()
     def _sides_logits(self, image: torch.Tensor, sides) -> torch.Tensor:
@@ -344,13 +355,13 @@ class RPOMulti(EvalMixin):
         return self._sides_logits(image, self._shared_sides)
 
     def test_all(self, image_set, batch_size: int = 100, frozen=None, verbose: bool = True, per_class_result: bool = False,
-                 hook=None) -> List[dict]:
+                 hook=None, classes=None) -> List[dict]:
         """Dassl's `test()` for EVERY member in one pass over the set: per chunk one frozen image pass (none with `frozen`,
         a `FrozenImageKV` of this set) and one prompt-row pass for all S members.  Returns, per member, the dict
-        `test(image_set, member=s)` returns."""
+        `test(image_set, member=s)` returns.  `classes`: against that `ClassSet`."""
         refuse_long_grid(self.cfg, f"{type(self).__name__}.test_all")
-        return self._test_shared(image_set, self.n_runs, self._shared_sides, batch_size, frozen, verbose, per_class_result,
-                                 hook)
+        return self._test_shared(image_set, self.n_runs, lambda: self._shared_sides(classes), batch_size, frozen, verbose,
+                                 per_class_result, hook, classes=classes)
 
     # ------------------------------------------------------------------ checkpoints: per member, a standalone RPO's files
     def save_model(self, directories: Sequence[str], epoch: Optional[int] = None, is_best: bool = False,

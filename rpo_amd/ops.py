@@ -368,6 +368,21 @@ def reduce_groups(src: torch.Tensor, out: torch.Tensor, groups: int) -> torch.Te
     return out
 
 
+def text_embed(ids: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, L: int,
+               ctx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[c * L + p] = table[ids[c, p]] + pos[p] (an id < 0: ctx[-1 - id] + pos[p]) for p < L (rpo_text_embed): ids int32
+    [n, ld_ids] on the device, table [vocab, d], pos [>= L, d], ctx [n_ctx, d] or None, out [n * L, d], all fp32."""
+    n, (vocab, d) = ids.shape[0], table.shape
+    assert ids.dtype == torch.int32 and ids.dim() == 2 and ids.stride(1) == 1 and ids.is_cuda
+    assert table.dtype == pos.dtype == out.dtype == torch.float32 and table.is_contiguous() and pos.is_contiguous()
+    assert out.is_contiguous() and pos.shape[0] >= L and pos.shape[1] == d and out.numel() == n * L * d
+    n_ctx = 0 if ctx is None else ctx.shape[0]
+    assert ctx is None or (ctx.dtype == torch.float32 and ctx.is_contiguous() and ctx.shape[1] == d)
+    check(_lib.load().rpo_text_embed(ids.data_ptr(), ids.stride(0), table.data_ptr(), vocab, pos.data_ptr(), _p(ctx), n_ctx,
+                                     out.data_ptr(), n, L, d, _stream()), "rpo_text_embed")
+    return out
+
+
 def broadcast_rows_sets(src: torch.Tensor, dst: torch.Tensor, groups: int) -> torch.Tensor:
     """dst[(s*groups + g)*rows + i] = src[s, i] for src [sets, rows, d], sets possibly strided (rpo_broadcast_rows_sets)."""
     sets, rows, d = src.shape

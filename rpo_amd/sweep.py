@@ -184,6 +184,11 @@ class RPOSweep(RPOMulti):
         raise RuntimeError("RPOSweep evaluates a member through the shared prompt-row path with the member's own K "
                            "(model_inference / test); the single-run eval path averages over the engine's K")
 
+    def class_set(self, tokens, chunk=None):
+        raise NotImplementedError("RPOSweep.class_set: evaluation on another class set is not built for members with their "
+                                  "own K -- a class set's text features would be averaged over the engine's K, not the "
+                                  "member's K_s; train the member as an RPO / RPOMulti run, or load its checkpoint into one")
+
     def _member_sides(self, member: int):
         if not 0 <= member < self.n_runs:
             raise IndexError(f"member {member} of {self.n_runs}")
@@ -191,18 +196,30 @@ class RPOSweep(RPOMulti):
         text_f = eng.multi_text_features()[member * rows:(member + 1) * rows]
         return eng.m_img_prompt[member:member + 1], text_f, eng.m_k_used[member:member + 1]
 
-    def _shared_sides(self):
+    def _shared_sides(self, classes=None):
+        if classes is not None:
+            self.class_set(None)                      # (test_all(classes=...): refuses, by name and with the reason)
         eng = self.engine
         return eng.m_img_prompt, eng.multi_text_features(), eng.m_k_used
 
+    def test_all(self, image_set, batch_size: int = 100, frozen=None, verbose: bool = True, per_class_result: bool = False,
+                 hook=None, classes=None) -> List[dict]:
+        if classes is not None:
+            self.class_set(None)                      # (refuses, by name and with the reason)
+        return super().test_all(image_set, batch_size, frozen, verbose, per_class_result, hook)
+
     @torch.no_grad()
-    def model_inference(self, image: torch.Tensor, member: int = 0) -> torch.Tensor:
+    def model_inference(self, image: torch.Tensor, member: int = 0, classes=None) -> torch.Tensor:
         """logits [B, n_cls] of member `member`, averaged over its own K_s pairs."""
+        if classes is not None:
+            self.class_set(None)                      # (refuses, by name and with the reason)
         return self._sides_logits(image, lambda: self._member_sides(member))[0]
 
     def test(self, image_set, member: int = 0, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False,
-             frozen=None):
+             frozen=None, classes=None):
         """Dassl's `test()` for member `member` (loop.EvalMixin._test_shared with that member alone)."""
+        if classes is not None:
+            self.class_set(None)                      # (refuses, by name and with the reason)
         return self._test_shared(image_set, 1, lambda: self._member_sides(member), batch_size, frozen, verbose,
                                  per_class_result)[0]
 

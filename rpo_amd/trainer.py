@@ -517,40 +517,46 @@ class RPO(LoopMixin):
             self._patch_tag = None
 
     @torch.no_grad()
-    def model_inference(self, image) -> torch.Tensor:
+    def model_inference(self, image, classes=None) -> torch.Tensor:
+        """logits [B, n_cls] of the eval branch; `classes`: a `ClassSet` (`class_set(tokens)`) -- logits [B, n'] against it."""
         self._join_side()
         with torch.cuda.device(self.device):
             if isinstance(image, (list, tuple)):                # decoded uint8 images: resize + center crop + normalize
                 image = self.transform(False)(image)
             self.model.prompt_learner.eval()
             try:
-                return self.model(image)
+                return self.model(image) if classes is None else self.model(image, classes=classes)
             finally:
                 self.model.prompt_learner.train()
 
-    def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
+    def _eval_logits(self, image: torch.Tensor, classes=None) -> torch.Tensor:
         """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
         self._join_side()
-        return self.model.eval_logits(image)
+        return self.model.eval_logits(image, classes)
 
-    def _shared_sides(self):
-        """(img_prompts [1, K, d_v], text_f, k_used = None) of the current prompts for the prompt-row pass."""
+    def _shared_sides(self, classes=None):
+        """(img_prompts [1, K, d_v], text_f, k_used = None) of the current prompts for the prompt-row pass; `classes`: the
+        text features of that `ClassSet`."""
         eng, pl = self.engine, self.model.prompt_learner
         ver = (pl.text_prompt._version, pl.img_prompt._version)       # (edits through the nn.Parameter views: eval_logits)
         if ver != getattr(self.model, "_seen_version", None):
             eng.params_version += 1
             self.model._seen_version = ver
-        return eng.img_prompt.unsqueeze(0), eng.eval_text_features(), None
+        text_f = eng.eval_text_features() if classes is None else eng.class_text_features(classes)
+        return eng.img_prompt.unsqueeze(0), text_f, None
 
     def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, frozen=None,
-             hook=None):
+             hook=None, classes=None):
         """Dassl's `test()` (loop.EvalMixin.test).  `frozen`: a `FrozenImageKV` built for this engine and set -- no image
-        pass is run at all, only the K prompt rows per image on the cached frozen K / V (rpo_amd/frozen_kv.py)."""
+        pass is run at all, only the K prompt rows per image on the cached frozen K / V (rpo_amd/frozen_kv.py).
+        `classes`: a `ClassSet` -- the evaluation runs against its classes; a `FrozenImageKV` does not depend on the
+        classes, so one cache serves every class set."""
         if frozen is None:
-            return super().test(image_set, batch_size, verbose, per_class_result)
+            return super().test(image_set, batch_size, verbose, per_class_result, classes=classes)
         refuse_long_grid(self.cfg, "RPO.test(frozen=...)")
         self._join_side()
-        return self._test_shared(image_set, 1, self._shared_sides, batch_size, frozen, verbose, per_class_result, hook)[0]
+        return self._test_shared(image_set, 1, lambda: self._shared_sides(classes), batch_size, frozen, verbose,
+                                 per_class_result, hook, classes=classes)[0]
 
     # -- checkpoints: Dassl layout <dir>/prompt_learner/{model.pth.tar-<epoch>, model-best.pth.tar} ----------
     def save_model(self, directory: str, epoch: Optional[int] = None, is_best: bool = False,

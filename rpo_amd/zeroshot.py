@@ -61,18 +61,19 @@ class ZeroshotCLIP(EvalMixin):
             self.engine.set_plain_text_features(features)
 
     @torch.no_grad()
-    def model_inference(self, image: torch.Tensor) -> torch.Tensor:
-        """trainers/zsclip.py:58-63 -> logits [B, n_cls] (fp32, on the device)."""
+    def model_inference(self, image: torch.Tensor, classes=None) -> torch.Tensor:
+        """trainers/zsclip.py:58-63 -> logits [B, n_cls] (fp32, on the device); `classes`: a `ClassSet`
+        (`class_set(tokens)`) -- logits [B, n'] against it."""
         eng = self.engine
         with torch.cuda.device(eng.dev):
             image = image.to(device=eng.dev, dtype=torch.float32).contiguous()
-            return eng.forward_plain(image).clone()
+            return eng.forward_plain(image, classes=classes).clone()
 
     __call__ = model_inference
 
-    def _eval_logits(self, image: torch.Tensor) -> torch.Tensor:
+    def _eval_logits(self, image: torch.Tensor, classes=None) -> torch.Tensor:
         """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
-        return self.engine.forward_plain(image)
+        return self.engine.forward_plain(image, classes=classes)
 
 
 class ZeroshotCLIP2(ZeroshotCLIP):
@@ -104,3 +105,22 @@ class ZeroshotCLIP2(ZeroshotCLIP):
 
     def set_context(self, ctx) -> None:
         raise NotImplementedError("ZeroshotCLIP2.set_context: a learned context belongs to one template, the ensemble has T")
+
+    @torch.no_grad()
+    def class_set(self, tokens, chunk: Optional[int] = None):
+        """tokens [T, n', 77], template-major: the class set's classifier is the ensemble over ITS T templates (the
+        existing rpo_text_ensemble_* kernels on `encode_text`'s features); [n', 77]: one template."""
+        tokens = np.asarray(tokens)
+        if tokens.ndim == 2:
+            tokens = tokens[None]
+        if tokens.ndim != 3 or tokens.shape[2] != self.cfg.context or tokens.shape[0] < 1 or tokens.shape[1] < 1:
+            raise ValueError(f"ZeroshotCLIP2.class_set: tokens must be [T, n, {self.cfg.context}] (one block of class "
+                             f"prompts per template), got {tuple(tokens.shape)}")
+        with torch.cuda.device(self.engine.dev):
+            cs = self.engine.class_set(tokens[0], chunk)
+            T, n, _ = tokens.shape
+            feats = self.engine.encode_text(tokens.reshape(T * n, tokens.shape[2]), chunk)
+            acc = torch.empty(n, self.cfg.embed, dtype=torch.float32, device=self.device)
+            ops.text_ensemble_accumulate(feats, n, acc, first=True)
+            cs.plain_f, cs.plain_fixed = ops.text_ensemble_finish(acc, T), True
+        return cs
