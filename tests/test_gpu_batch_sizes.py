@@ -11,6 +11,9 @@ lo halves).  This module
   past this batch's R would otherwise read the previous batch's plausible rows), against the CPU oracle run image by image;
 * checks that batch composition does not change an image's result: bit for bit in f32, and between any two batch sizes
   whose image-tower GEMMs run the same plans in the 16-bit modes.
+
+The sweeps cover ViT-B/16 and ViT-L/14 at 224 px and the two other patch grids: ViT-B/32, whose 74-row
+units sit in 224-row (B = 26 .. 32) and 288-row (B = 18 .. 21) tiles, and ViT-L/14 at 336 px, which offers no units.
 """
 import ctypes
 import functools
@@ -139,16 +142,40 @@ def _plan_cases():
         ("bench_out_proj", R32, 768, 768, L.EPI_BIAS_RESID, "bf16", dict(units=u32, ln_group=96, hilo=True), 11),
         ("bench_c_proj", R32, 768, 3072, L.EPI_BIAS_RESID, "bf16", dict(units=u32, ln_group=96, hilo=True), 11),
     ]
+    # the engine's own calls at the other patch grids.  ViT-B/32 (50 + 24 rows per image, max_batch 32):
+    # row units a third of a 224-row tile high, 96-column statistics, hi / lo stream; in-proj gets no units and at
+    # 2368 x 2304 fills neither 256x256 nor 224x384 rounds
+    for B, tag in ((32, "b32_b32"), (28, "b32_b28_partial")):
+        Rb, ub = r(NB32, 24, B), _units(NB32, 24, B)
+        cases += [
+            (f"{tag}_in_proj", Rb, 2304, 768, L.EPI_LN_BIAS, "bf16", dict(ln_group=96, skip=(B * NB32, 768)), 2),
+            (f"{tag}_c_fc", Rb, 3072, 768, L.EPI_LN_BIAS_QGELU, "bf16", dict(units=ub, ln_group=96, aux_rows=B * 24), 10),
+            (f"{tag}_out_proj", Rb, 768, 768, L.EPI_BIAS_RESID, "f16", dict(units=ub, ln_group=96, hilo=True), 11),
+            (f"{tag}_c_proj", Rb, 768, 3072, L.EPI_BIAS_RESID, "bf16", dict(units=ub, ln_group=96, hilo=True), 11),
+        ]
+    # ViT-L/14 at 336 px (577 + 24 rows per image, max_batch 16): no units, the GEMMs choose by shape -- c_fc takes the
+    # 288x256 geometry in equal-height contiguous tiles at B = 7 and 14, the residual GEMMs the 128x128 tiles from 8192 rows
+    for B, (c_in, c_fc, c_res) in ((7, (8, 10, 6)), (8, (8, 2, 6)), (14, (2, 10, 2)), (16, (8, 2, 2))):
+        Rl = r(NL336, 24, B)
+        cases += [
+            (f"l336_b{B}_in_proj", Rl, 3072, 1024, L.EPI_LN_BIAS, "bf16", dict(skip=(B * NL336, 1024)), c_in),
+            (f"l336_b{B}_c_fc", Rl, 4096, 1024, L.EPI_LN_BIAS_QGELU, "bf16", dict(aux_rows=B * 24), c_fc),
+            (f"l336_b{B}_out_proj", Rl, 1024, 1024, L.EPI_BIAS_RESID, "f16", {}, c_res),
+            (f"l336_b{B}_c_proj", Rl, 1024, 4096, L.EPI_BIAS_RESID, "bf16", {}, c_res),
+        ]
     return cases
 
 
+NB32, NL336 = 50, 577     # ... ViT-B/32, ViT-L/14 at 336 px
+_GRID_PLAN_IDS = [f"{t}_{g}" for t in ("b32_b32", "b32_b28_partial", "l336_b7", "l336_b8", "l336_b14", "l336_b16")
+                  for g in ("in_proj", "c_fc", "out_proj", "c_proj")]
 _PLAN_IDS =["b4_out_proj_64x64", "b8_c_fc_64x128", "b12_c_proj_64x128", "b12_in_proj_128x128", "b14_c_fc_256x256",
              "b26_c_fc_224x384_partial", "b27_out_proj_224x96_partial_hilo", "k48_b32_out_proj_256x96",
              "l14_b16_c_fc_288x256", "l14_b13_out_proj_288x64_partial_hilo", "f32_b4_out_proj_64x64",
              "f32_b8_c_fc_64x128", "f32_b12_c_fc_128x128", "bench_in_proj", "bench_c_fc", "bench_out_proj", "bench_c_proj"]
 
 
-@pytest.mark.parametrize("case", _PLAN_IDS)
+@pytest.mark.parametrize("case", _PLAN_IDS + _GRID_PLAN_IDS)
 def test_gemm_nt_plan_names_the_launch_it_makes(case):
     """For one shape per tile family the heuristic picks (row-unit hints, 96-column statistics, hi / lo arguments and the
     bench's B = 32 shapes included): the query returns the family's code, and a launch forced to that code gives the bits
@@ -276,10 +303,14 @@ SWEEPS = {                       # id -> (model, K, max_batch)
     "b16_k4_mb32": ("ViT-B/16", 4, 32),
     "b16_k48_mb32": ("ViT-B/16", 48, 32),
     "l14_k24_mb16": ("ViT-L/14", 24, 16),
+    "b32_k24_mb32": ("ViT-B/32", 24, 32),
+    "l14_336_k24_mb16": ("ViT-L/14@336px", 24, 16),
 }
 SWEEP_CASES = [("b16_k24_mb32", "f32"), ("b16_k24_mb32", "bf16"), ("b16_k24_mb32", "f16"),
                ("b16_k24_mb4", "bf16"), ("b16_k24_mb4", "f16"), ("b16_k4_mb32", "bf16"), ("b16_k48_mb32", "bf16"),
-               ("l14_k24_mb16", "bf16"), ("l14_k24_mb16", "f16")]
+               ("l14_k24_mb16", "bf16"), ("l14_k24_mb16", "f16"),
+               ("b32_k24_mb32", "f32"), ("b32_k24_mb32", "bf16"), ("b32_k24_mb32", "f16"),
+               ("l14_336_k24_mb16", "bf16"), ("l14_336_k24_mb16", "f16")]
 BOUNDS = {"f32": (TOL_F32, TOL_F32), "bf16": (BF16_LOGIT_ATOL, BF16_GRAD_REL), "f16": (F16_LOGIT_ATOL, F16_GRAD_REL)}
 
 # Per-step image-side buffers: everything a step writes before it reads it.  Persistent state -- parameters, gradients,
@@ -290,8 +321,9 @@ STEP_BUFFERS = ("x_pre", "x", "xm", "h", "h_lo", "ln_stats", "qkv", "att", "g", 
 
 @functools.lru_cache(maxsize=None)
 def _workload(model, K):
-    from rpo_amd.config import vit_b16, vit_l14
-    cfg = (vit_b16 if model == "ViT-B/16" else vit_l14)(layers_v=2, layers_t=2, K=K)
+    from rpo_amd.config import vit_b16, vit_b32, vit_l14, vit_l14_336
+    make = {"ViT-B/16": vit_b16, "ViT-L/14": vit_l14, "ViT-B/32": vit_b32, "ViT-L/14@336px": vit_l14_336}[model]
+    cfg = make(layers_v=2, layers_t=2, K=K)
     toks = synth.oxford_pets_base_tokens()
     sd = synth.clip_state_dict(cfg, seed=0, token_rows=np.unique(toks).tolist() + [49407])
     tp, ip = synth.prompts(cfg, sd, seed=7)
@@ -331,7 +363,7 @@ class _PlanLog:
     """Records the plan of every GEMM the image forward issues: ("nt", tile_config, ln_group) / ("ws", code)."""
     def __init__(self, monkeypatch, eng):
         o = ops()
-        self.want, self.active, self.log = False, False, []
+        self.want, self.active, self.log, self.ws_rows = False, False, [], []
         real_nt, real_ws, real_fwd = o.gemm_nt, o.gemm_ws_try, eng._image_forward
 
         def gemm_nt(a, w, out, epilogue=0, **kw):
@@ -344,6 +376,7 @@ class _PlanLog:
                 code = o.gemm_ws_plan(a, w, out, epilogue, **kw)
                 if code > 0:                       # (RPO_E_SHAPE: the engine sends the call to gemm_nt, recorded there)
                     self.log.append(("ws", code))
+                    self.ws_rows.append(a.shape[0])
             return real_ws(a, w, out, epilogue, **kw)
 
         def image_forward(*args, **kw):
@@ -479,6 +512,18 @@ def _sweep(eng, sweep, mode, monkeypatch, t0):
         assert row_unit_partial, "no batch size below 16 runs the 288-row kernels in a partial round"
     if sweep == "b16_k24_mb4":
         assert all(any(c[0] == "ws" for c in plans[B]) for B in plans)
+    if sweep == "b32_k24_mb32" and mode != "f32":
+        # (74-row units in 224-row tiles: both one-round kernels, below B = 32 in a partial round, the split-k one with its
+        #  96-column statistics)
+        assert {10, 11} <= nt_codes, sorted(nt_codes)
+        assert row_unit_partial, "no batch size below 32 runs the row-unit kernels in a partial round"
+        assert all(any(c[:2] == ("nt", 11) and c[2] == 96 for c in plans[B]) for B in row_unit_partial + [mb])
+    if sweep == "l14_336_k24_mb16":
+        # (601 rows per image: no row units; c_fc on the 288x256 geometry in contiguous tiles, 64-column statistics
+        #  throughout, rpo_gemm_ws for the prompt rows only)
+        assert {2, 8, 10} <= nt_codes and 11 not in nt_codes, sorted(nt_codes)
+        assert all(c[2] == 64 for p in plans.values() for c in p if c[0] == "nt")
+        assert all(n <= 1024 for n in rec.ws_rows), f"rpo_gemm_ws at {max(rec.ws_rows)} rows"
     print(f"\n[{sweep} {mode}] plan table (tile_config[/96-column statistics] of the image-forward GEMMs):\n{_regimes(plans)}")
     print(f"[{sweep} {mode}] worst vs oracle: logits {worst['logits']:.3e} loss {worst['loss']:.3e} "
           f"g_text {worst['g_text']:.3e} g_img {worst['g_img']:.3e}; {pairs} bit-identity pairs; {time.time() - t0:.1f} s")

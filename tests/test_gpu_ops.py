@@ -540,15 +540,34 @@ def test_gemm_one_round_288x64_split_k(mode, n0, n1, units, K):
 
 
 @pytest.mark.parametrize("mode", ["bf16", "f16"])
-@pytest.mark.parametrize("M,d,N", [(300, 768, 3072), (4200, 768, 2304), (1000, 1024, 4096), (7072, 768, 3072)])
-def test_gemm_layernorm_fold(mode, M, d, N):
+@pytest.mark.parametrize("M,d,N,Kp", [(300, 768, 3072, 0), (4200, 768, 2304, 0), (1000, 1024, 4096, 0), (7072, 768, 3072, 0),
+                                      # ViT-L/14 at 336 px (601 rows per image, no row units), B = 8: the in-proj shape
+                                      # on the 256x256 kernel with K = 16 x 64, its admission edge; B = 14: the residual
+                                      # producers (out-proj K = 1024, c_proj K = 4096) on the 128x128 tiles from 8192 rows
+                                      (4808, 1024, 3072, 0), (8414, 1024, 4096, 1024), (8414, 1024, 4096, 4096)],
+                         ids=["300-768-3072", "4200-768-2304", "1000-1024-4096", "7072-768-3072", "4808-1024-3072",
+                              "8414-1024-4096-K1024", "8414-1024-4096-K4096"])
+def test_gemm_layernorm_fold(mode, M, d, N, Kp):
     """LayerNorm folded into the GEMM around it (include/rpo_amd.h RPO_EPI_LN_*): the producer (BIAS_RESID) leaves the
     act-dtype copy of its result and per-row 64-column partial statistics; the consumer takes that copy as A, the
     gamma-scaled weight and s / b' and must reproduce  quickgelu(LN(x) W^T + b)  (clip/model.py:156-159 feeding
-    :174-175) to the tolerance of the unfolded path.  Every tile shape of the consumer gives the same bits."""
+    :174-175) to the tolerance of the unfolded path.  Every tile shape of the consumer gives the same bits.
+    Kp: the producer's contraction length (0: d).  The d = 1024 cases from 4800 rows on take the float64 references on a
+    row subset -- the first and last row of every 64-row step (the edges of the 64-, 128- and 256-row tiles), of every
+    equal-height 288-row-geometry tile, 256 seeded rows and the saved rows -- and every output must be finite everywhere."""
     from rpo_amd import _lib as L
     o = ops()
-    att, w_out, b_out = rnd((M, d), 1, 0.5), rnd((d, d), 2, d ** -0.5), rnd((d,), 3)
+    Kp = Kp or d
+    big = M >= 4800 and d == 1024
+    if big:
+        tm = (M + 287) // 288
+        h = (M + tm - 1) // tm
+        sel = torch.tensor(sorted(set([r for r in range(M) if r % 64 in (0, 63)] + list(range(M - 100, M))
+                                      + [r for t in range(tm) for r in (t * h, min((t + 1) * h, M) - 1)]
+                                      + torch.randperm(M, generator=torch.Generator().manual_seed(M))[:256].tolist())))
+    else:
+        sel = torch.arange(M)
+    att, w_out, b_out = rnd((M, Kp), 1, 0.5), rnd((d, Kp), 2, Kp ** -0.5), rnd((d,), 3)
     resid = rnd((M, d), 4, 2.0) + 0.4
     w, b = rnd((N, d), 5, d ** -0.5), rnd((N,), 6)
     gamma, beta = rnd((d,), 7, 0.1) + 1.0, rnd((d,), 8, 0.05)
@@ -556,10 +575,17 @@ def test_gemm_layernorm_fold(mode, M, d, N):
     xm = torch.full((M, d), float("nan"), device=dev())
     xb = torch.full((M, d), float("nan"), dtype=dt, device=dev())
     stats = torch.full((M, d // 64, 2), float("nan"), device=dev())
+    if big:
+        want = 2 if M >= 8192 else 6
+        got = o.gemm_nt_plan(att.to(dev(), dt), w_out.to(dev(), dt), xm, L.EPI_BIAS_RESID, bias=b_out.to(dev()),
+                             resid=resid.to(dev()), out2=xb, ln_stats=stats)
+        assert got == want, f"producer plan {got}, expected {want}"
     o.gemm_nt(att.to(dev(), dt), w_out.to(dev(), dt), xm, L.EPI_BIAS_RESID, bias=b_out.to(dev()), resid=resid.to(dev()),
               out2=xb, ln_stats=stats)
     xm64 = xm.double().cpu()
-    close(xm, q(att, mode) @ q(w_out, mode).t() + b_out.double() + resid.double(), "f32", "producer result", tol=1e-4)
+    assert torch.isfinite(xm).all() and torch.isfinite(stats).all()
+    close(xm[sel], q(att, mode)[sel] @ q(w_out, mode).t() + b_out.double() + resid.double()[sel], "f32", "producer result",
+          tol=1e-4)
     assert torch.equal(xb.cpu(), xm.cpu().to(dt)), "out2 must be the RNE act-dtype copy of C"
     grp = xm64.reshape(M, d // 64, 64)
     ref_stats = torch.stack([grp.mean(-1), ((grp - grp.mean(-1, keepdim=True)) ** 2).sum(-1)], -1)
@@ -568,9 +594,10 @@ def test_gemm_layernorm_fold(mode, M, d, N):
     wq = (w.double() * gamma.double()[None, :]).float().to(dt)
     s = wq.double().sum(1).float()
     bq = (b.double() + w.double() @ beta.double()).float()
-    mu = xm64.mean(1, keepdim=True)
-    rstd = (xm64.var(1, unbiased=False, keepdim=True) + 1e-5).rsqrt()
-    pre = ((xm64 - mu) * rstd * gamma.double() + beta.double()) @ w.double().t() + b.double()
+    xs = xm64[sel]                                  # (sel ends with the saved rows [row0, M))
+    mu = xs.mean(1, keepdim=True)
+    rstd = (xs.var(1, unbiased=False, keepdim=True) + 1e-5).rsqrt()
+    pre = ((xs - mu) * rstd * gamma.double() + beta.double()) @ w.double().t() + b.double()
     row0 = M - 100
     outs = {}
     one_round = (M, N) == (7072, 3072)
@@ -579,11 +606,16 @@ def test_gemm_layernorm_fold(mode, M, d, N):
         y = torch.full((M, N), float("nan"), dtype=dt, device=dev())
         aux = torch.full((M - row0, N), float("nan"), device=dev())
         hint = dict(tile_config=10, row_units=(197, 24, 6304)) if cfg == "units" else dict(tile_config=cfg)
+        if big and cfg == 0:                        # (what the heuristic runs: the kernel under test)
+            got = o.gemm_nt_plan(xb, wq.to(dev()), y, L.EPI_LN_BIAS_QGELU, bias=bq.to(dev()), aux=aux, aux_row0=row0,
+                                 ln_stats=stats, ln_colsum=s.to(dev()))
+            assert got == (8 if N == 3072 else 10), f"consumer plan {got}"
         o.gemm_nt(xb, wq.to(dev()), y, L.EPI_LN_BIAS_QGELU, bias=bq.to(dev()), aux=aux, aux_row0=row0,
                   ln_stats=stats, ln_colsum=s.to(dev()), **hint)
+        assert torch.isfinite(y).all() and torch.isfinite(aux).all(), f"tile_config {cfg}"
         outs[cfg] = (y, aux)
-    close(outs[0][0], R.qgelu(pre), mode, "LN-folded c_fc", tol=1.5 * TOL[mode])
-    close(outs[0][1], pre[row0:], mode, "LN-folded saved u", tol=1.5 * TOL[mode])
+    close(outs[0][0][sel], R.qgelu(pre), mode, "LN-folded c_fc", tol=1.5 * TOL[mode])
+    close(outs[0][1], pre[-100:], mode, "LN-folded saved u", tol=1.5 * TOL[mode])
     for cfg in cfgs[1:]:
         assert torch.equal(outs[cfg][0], outs[0][0]) and torch.equal(outs[cfg][1], outs[0][1]), f"tile_config {cfg}"
     # the form the engine's 16-bit modes save: d quickgelu / du in the act dtype (the 224x384 kernel forms it in its block
@@ -599,12 +631,13 @@ def test_gemm_layernorm_fold(mode, M, d, N):
                       ln_stats=stats, ln_colsum=s.to(dev()), **hint)
             assert torch.equal(y, outs[0][0]), f"tile_config {cfg}, aux16 pad {pad}"
             d16[cfg, pad] = aux16
-    close(d16[0, 0], R.qgelu_grad(pre[row0:]), mode, "LN-folded saved derivative", tol=1.5 * TOL[mode])
+    close(d16[0, 0], R.qgelu_grad(pre[-100:]), mode, "LN-folded saved derivative", tol=1.5 * TOL[mode])
     for key, v in d16.items():
         assert torch.equal(v, d16[0, 0]), f"saved derivative, tile_config / pad {key}"
     y = torch.full((M, N), float("nan"), dtype=dt, device=dev())
     o.gemm_nt(xb, wq.to(dev()), y, L.EPI_LN_BIAS, bias=bq.to(dev()), ln_stats=stats, ln_colsum=s.to(dev()))
-    close(y, pre, mode, "LN-folded in-proj", tol=1.5 * TOL[mode])
+    assert torch.isfinite(y).all()
+    close(y[sel], pre, mode, "LN-folded in-proj", tol=1.5 * TOL[mode])
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "f16"])
@@ -626,7 +659,7 @@ def test_gemm_split_k_feeds_layernorm_bwd(mode):
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "f16"])
-@pytest.mark.parametrize("patch,size", [(16, 64), (14, 56)])
+@pytest.mark.parametrize("patch,size", [(16, 64), (14, 56), (32, 96)])     # (32, 96): ViT-B/32's patch rows of K = 3072
 def test_patch_embed_matches_conv(mode, patch, size):
     from rpo_amd import _lib as L
     o = ops()
