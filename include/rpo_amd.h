@@ -497,6 +497,27 @@ int rpo_text_ensemble_finish(const float* acc, int n_cls, int e, int T_total, fl
 int rpo_eval_accumulate(const float* logits, int64_t ldl, const int64_t* label, int B, int C, int64_t* counts,
                         int32_t* cmat, int32_t* pred, void* stream);
 
+/* (ABI 8 addition) S classifiers over n CACHED image features in one launch, head and evaluator fused: what
+ * trainers/zsclip.py:58-63, trainers/coop.py:196-208 and trainers/linear_prob.py:85-95 compute behind `encode_image`,
+ * plus rpo_eval_accumulate, without the logits' round trip through memory.  rpo_amd/csrc/classify.hip.  s < S, i < n, c < C:
+ *   logits[s,i,c] = a_i * r_sc * <feat[i,:], cls[s,c,:]> + bias[s,c]
+ *   a_i  = scale / ||feat[i,:]||  if norm_feat else scale;     r_sc = 1 / ||cls[s,c,:]||  if norm_cls else 1
+ *   pred[s,i] = the row maximum's index by rpo_eval_accumulate's rule (torch CPU fp32: NaN first, larger, lower index)
+ *   counts[s,0] += #(pred == label), counts[s,1] += n, cmat[s][label][pred] += 1
+ * feat [n, e] fp32 with leading dimension ldf >= e; cls [S, C, e] fp32; bias [S, C] fp32 or NULL; label int64 [n];
+ * counts int64 [S, 2]; cmat int32 [S, C, C] or NULL; pred int32 [S, n] or NULL (overwritten); logits_out [S, n, C] fp32 or
+ * NULL (for tests and callers that want the values: with NULL no logit reaches memory); all device memory.  Labels as in
+ * rpo_eval_accumulate: counts and cmat ACCUMULATE across calls; a label outside [0, C) counts in the total, is never
+ * correct and touches no cell.  The dot product runs on the fp32 matrix pipe over the whole k range in one fixed order,
+ * both norms are double sums rounded once, the sums written are integers: a row's logits and prediction do not depend on
+ * which other rows, how many, or which other classifiers are in the call, and the bits repeat from run to run.
+ * e a multiple of 32 up to 1024, 1 <= C <= 65536, 1 <= S <= 1024, n >= 1, else RPO_E_SHAPE; feat and cls 16-byte, counts
+ * 8-byte aligned, else RPO_E_ALIGN; a null feat / cls / label / counts: RPO_E_BADARG; nothing is launched on an error.
+ * One launch on `stream`, no workspace, no allocation, capturable in a HIP graph. */
+int rpo_features_classify(const float* feat, int64_t ldf, const float* cls, const float* bias, const int64_t* label,
+                          float scale, int norm_feat, int norm_cls, int64_t* counts, int32_t* cmat, int32_t* pred,
+                          float* logits_out, int n, int C, int e, int S, void* stream);
+
 /* ---- CLIP ResNet image tower (clip/model.py:10-152, rpo_amd/csrc/conv.hip) ------------------------------------------
  * Activations are NHWC in the act dtype (`dtype`: RPO_F32 / RPO_BF16 / RPO_F16): row m = (b, y, x), channels contiguous.
  * Eval-mode BatchNorm is folded into weight and bias by the caller.  Every sum runs in a fixed order (same bits per call).

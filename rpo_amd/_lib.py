@@ -179,6 +179,8 @@ SIGNATURES = {
     "rpo_text_ensemble_accumulate": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "rpo_text_ensemble_finish": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rpo_eval_accumulate": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rpo_features_classify": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                      c_i32, c_i32, c_i32, c_i32, c_vp]),
     "rpo_conv2d_plan": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "rpo_conv2d_nhwc": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                 c_vp]),

@@ -262,6 +262,20 @@ class CoOp(LoopMixin):
             image = image.to(device=self.device, dtype=torch.float32).contiguous()
             return self._class_logits(image, classes).clone()
 
+    @torch.no_grad()
+    def classifier(self, classes=None):
+        """The text features of the CURRENT context -- of the trained classes (the dense text forward the eval path
+        runs), or of a `ClassSet` -- as the cosine classifier of rpo_features_classify (trainers/coop.py:196-208)."""
+        eng = self.engine
+        with torch.cuda.device(self.device):
+            if classes is None:
+                eng.c_shift[0].copy_(eng.coop_ctx.view(-1, self.cfg.d_t))
+                eng._coop_text_forward(False)
+                cls = eng.c_text_f[:self.cfg.n_cls].clone()
+            else:
+                cls = eng.class_plain_features(classes, eng.coop_ctx, eng.coop_position)
+        return cls, None, True, True, eng.logit_scale_exp
+
     def _class_logits(self, image: torch.Tensor, classes) -> torch.Tensor:
         """The plain towers against a class set whose prompts carry the CURRENT generic context, placed by the layout rule
         of the trainer's class-token position (Engine.class_plain_features)."""
@@ -343,6 +357,12 @@ class CoCoOp(CoOp):
     on ctx and the meta-net; returns {"loss"} (no accuracy: the model returns the loss itself in training mode)."""
 
     _reports_acc = False
+    _features_why_not = ("CoCoOp's text features depend on the image (the meta-net shifts the context per image, "
+                         "trainers/cocoop.py:141-143): every image needs its own text pass, which cached image features "
+                         "cannot spare")
+
+    def classifier(self, classes=None):
+        raise NotImplementedError(f"CoCoOp.classifier: {self._features_why_not}")
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int = 4,
                  optim: Optional[OptimConfig] = None, device: str | torch.device = "cuda:0",

@@ -130,6 +130,8 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         self.Lmax = int(self.len_np.max())
         self.len_i32 = torch.tensor(self.len_np, dtype=torch.int32, device=device)
         self.logit_scale_exp = float(np.exp(np.float32(state_dict["logit_scale"])))
+        from .features import weights_checksum
+        self.weights_id = weights_checksum(state_dict)  # what cached image features belong to (rpo_amd/features.py)
         with torch.cuda.device(device):                 # the convert kernels of _pack launch on the current device
             self._pack(state_dict, tokens)
             self._alloc()
@@ -918,12 +920,7 @@ class Engine(CoopEngineMixin, LpEngineMixin, RnEngineMixin, MultiEngineMixin, Pr
         cfg = self.cfg
         B = self._check(image)
         N, dv, e, n = cfg.n_frozen, cfg.d_v, cfg.embed, cfg.n_cls
-        if not self.text_cache_ready:
-            self.cache_text_kv()
-        if self.plain_text_f is None:
-            self.plain_text_f = self._text_eot_features(self.text_x_final, self.len_i32, n, self.Lmax,
-                                                        torch.empty(n, e, dtype=torch.float32, device=self.dev))
-        text_f = self.plain_text_f if self.plain_text_override is None else self.plain_text_override
+        text_f = self.plain_text_features()
         if cfg.is_rn:
             self.rn_forward(image)                                             # -> img_cls_f[:B] (engine_rn.py)
         else:

@@ -217,6 +217,20 @@ class CoopEngineMixin:
         ops.gemm_nt(self.y_post[:B], self.img_proj_t, self.img_cls_f[:B], EPI_NONE)
         return B
 
+    @torch.no_grad()
+    def encode_image(self, image: torch.Tensor) -> torch.Tensor:
+        """`CLIP.encode_image` (clip/model.py:341-342) of a batch [B, 3, H, W] of up to max_batch images -> [B, e] fp32 on
+        the device, un-normalised, cloned: the plain image pass of `forward_plain` and of the CoOp / LP trainers, ViT or
+        ResNet.  The counterpart of `encode_text`; what `ImageFeatures.build` caches (rpo_amd/features.py)."""
+        with torch.cuda.device(self.dev):
+            image = image.to(device=self.dev, dtype=torch.float32).contiguous()
+            assert image.dim() == 4 and 1 <= image.shape[0] <= self.max_batch and \
+                tuple(image.shape[1:]) == (3, self.cfg.image_size, self.cfg.image_size)
+            if self.img_cls_f is None:
+                self.img_cls_f = torch.empty(self.max_batch, self.cfg.embed, dtype=torch.float32, device=self.dev)
+            B = self._plain_image_features(image)
+            return self.img_cls_f[:B].clone()
+
     def coop_forward_backward(self, image: torch.Tensor, label: Optional[torch.Tensor]) -> torch.Tensor:
         """trainers/coop.py:196-208 + :266-270: logits = exp(logit_scale) * normalise(image features of the plain image
         tower) @ normalise(text features of [SOS | ctx | name . EOT])^T; with `label`, also the mean cross-entropy

@@ -117,6 +117,17 @@ class TextEncodeEngineMixin:
                 self._text_eot_features(x, len_i32, n, L, out[p0:p1])
         return out
 
+    def plain_text_features(self) -> torch.Tensor:
+        """The classifier of `forward_plain`, [n_cls, e] un-normalised (the engine's own buffer): the caller's
+        (`set_plain_text_features`), else the EOT features of the frozen-token pass, computed once per context."""
+        n, e = self.cfg.n_cls, self.cfg.embed
+        if not self.text_cache_ready:
+            self.cache_text_kv()
+        if self.plain_text_f is None:
+            self.plain_text_f = self._text_eot_features(self.text_x_final, self.len_i32, n, self.Lmax,
+                                                        torch.empty(n, e, dtype=torch.float32, device=self.dev))
+        return self.plain_text_f if self.plain_text_override is None else self.plain_text_override
+
     def set_plain_text_features(self, features: Optional[torch.Tensor]) -> None:
         """The classifier of `forward_plain` becomes `features` [n_cls, e] (the head normalises them) instead of the
         engine's own prompts' text features, until None is passed; `cache_text_kv` leaves the override alone."""

@@ -78,12 +78,40 @@ class EvalMixin:
         image_set.check_labels(classes.n)
         return classes.n
 
+    # ---- cached image features (rpo_amd/features.py): for the trainers whose image feature depends on nothing they train
+    _features_why_not: Optional[str] = None        # why `features=` / `val_features=` cannot serve this trainer, or None
+
+    def _refuse_features(self, features, what: str) -> None:
+        if features is not None and self._features_why_not is not None:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: {self._features_why_not}")
+
+    def classifier(self, classes=None):
+        """(cls [C, e], bias [C] or None, norm_feat, norm_cls, scale) of `rpo_features_classify` for the model as it
+        stands -- or for a `ClassSet`: logits = scale (/ |f|) (/ |cls|) <f, cls> + bias on the image feature f."""
+        raise NotImplementedError(f"{type(self).__name__}: no classifier on cached image features")
+
+    def _test_features(self, image_set, features, verbose: bool, per_class_result: bool, classes) -> dict:
+        """`test` on an `ImageFeatures` of this engine and set: one rpo_features_classify launch, one read-back."""
+        from .features import classify_many
+        self._n_classes(image_set, classes)
+        features.check(self.engine, image_set)
+        with torch.cuda.device(self.device):
+            cls, bias, norm_feat, norm_cls, scale = self.classifier(classes)
+            return classify_many(features, cls.unsqueeze(0), None if bias is None else bias.unsqueeze(0), norm_feat,
+                                 norm_cls, scale, verbose=verbose, per_class_result=per_class_result)[0]
+
     @torch.no_grad()
-    def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, classes=None):
+    def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, classes=None,
+             features=None):
         """Dassl's `test()`: eval transform (resize + center crop) from the resident set, the eval forward,
         `rpo_eval_accumulate` on the same stream, one read-back, `Classification.evaluate()` -> its dict
         (+ "confusion_matrix").  Runs chunks of min(batch_size, engine.max_batch), the last one ragged.
-        `classes`: a `ClassSet` -- the evaluator and the confusion matrix are sized by ITS class count."""
+        `classes`: a `ClassSet` -- the evaluator and the confusion matrix are sized by ITS class count.
+        `features`: an `ImageFeatures` of this engine and set (ZeroshotCLIP(2), CoOp, LP) -- no image pass at all: the
+        current classifier over the cached features in one fused launch."""
+        self._refuse_features(features, "test(features=...)")
+        if features is not None:
+            return self._test_features(image_set, features, verbose, per_class_result, classes)
         n, C = len(image_set), self._n_classes(image_set, classes)
         chunk = max(1, min(batch_size, self.engine.max_batch))
         ev = Classification(C, per_class_result)
@@ -280,19 +308,28 @@ class LoopMixin(EvalMixin):
 
     def train(self, train_set, max_epoch: Optional[int] = None, val_set=None, directory: Optional[str] = None,
               generator: Optional[torch.Generator] = None, test_batch_size: int = 100, verbose: bool = True,
-              val_frozen=None) -> List[dict]:
+              val_frozen=None, val_features=None) -> List[dict]:
         """Dassl's `train()`: `run_epoch` until `max_epoch` (default: the optimiser config's), and after each epoch its
         `after_epoch`: with a validation set `test(val_set)` -> `after_epoch_eval` (keeps `model-best`); without one
         the last epoch's model is saved.  Returns one record per epoch (mean loss, training accuracy where the
         trainer reports it, validation accuracy).  `val_frozen`: a `FrozenImageKV` of `val_set` -- the validation images'
-        frozen pass is then never repeated (RPO only: the other trainers' features depend on what they train)."""
+        frozen pass is then never repeated (RPO only: its frozen image rows never read a prompt).  `val_features`: an
+        `ImageFeatures` of `val_set` (CoOp, LP: what they train sits behind the image feature) -- no validation image
+        pass in any epoch.  CoCoOp has neither: its text features depend on the image."""
         max_epoch = self.optim_cfg.max_epoch if max_epoch is None else max_epoch
+        self._refuse_features(val_features, "train(val_features=...)")
+        if val_features is not None:
+            if val_set is None:
+                raise ValueError(f"{type(self).__name__}.train: val_features are the features of val_set; pass both")
+            val_features.check(self.engine, val_set)
         if val_frozen is not None and not self._takes_frozen:
             raise NotImplementedError(f"{type(self).__name__}.train: val_frozen is RPO's (its frozen image rows never read a "
                                       "prompt); this trainer evaluates through its own image pass")
         if val_frozen is not None:
             refuse_long_grid(self.cfg, f"{type(self).__name__}.train(val_frozen=...)")
         val_kw = {} if val_frozen is None else {"frozen": val_frozen}
+        if val_features is not None:
+            val_kw["features"] = val_features
         history = []
         while self.epoch < max_epoch:
             res = self.run_epoch(train_set, generator)

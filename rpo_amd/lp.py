@@ -190,6 +190,21 @@ class LP(LoopMixin):
             image = image.to(device=self.device, dtype=torch.float32).contiguous()
             return self._class_logits(image, classes).clone()
 
+    @torch.no_grad()
+    def classifier(self, classes=None):
+        """lp_layer and the normalised text features (the trained classes', or a `ClassSet`'s) composed into ONE affine
+        classifier on the un-normalised image feature (features.lp_compose): norms off, bias = scale T b."""
+        from .features import lp_compose
+        eng = self.engine
+        with torch.cuda.device(self.device):
+            if classes is None:
+                T = eng.lp_text_f_n
+            else:
+                f = eng._cs_plain_current(eng._cs_check(classes))
+                T = f / f.norm(dim=-1, keepdim=True)                                  # as Engine._cs_lp_forward
+            M, c = lp_compose(T, eng.lp_w, eng.lp_b, eng.logit_scale_exp)
+        return M, c, False, False, eng.logit_scale_exp
+
     def _class_logits(self, image: torch.Tensor, classes) -> torch.Tensor:
         """lp_layer on the image feature, then the class set's normalised text features (Engine._cs_lp_forward)."""
         return self.engine._cs_lp_forward(image, classes)

@@ -90,6 +90,9 @@ def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig)
 
 class RPOMulti(EvalMixin):
     _found_inf = None                                   # amp is refused here; `RPOSweep` has one verdict per member
+    _features_why_not = ("RPO's image rows read its members' prompts, so no image feature outlives a step; what an image set "
+                         "can cache for RPO is the frozen rows' K / V: FrozenImageKV.build(engine, image_set) and "
+                         "test_all(..., frozen=...)")
     _one_counter = " (one step counter covers every member)"     # why a mix of files with and without state is refused
     captures = 0                                        # HIP graphs of the step captured so far (one per distinct learning rate)
 
@@ -311,8 +314,9 @@ class RPOMulti(EvalMixin):
         return self.engine.forward_eval(image, classes=classes)
 
     def test(self, image_set, member: int = 0, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False,
-             classes=None):
+             classes=None, features=None):
         """Dassl's `test()` for member `member` (loop.EvalMixin.test); `classes`: against that `ClassSet`."""
+        self._refuse_features(features, "test(features=...)")
         with torch.cuda.device(self.device):
             self._select(member)
         return super().test(image_set, batch_size, verbose, per_class_result, classes=classes)
@@ -355,10 +359,11 @@ class RPOMulti(EvalMixin):
         return self._sides_logits(image, self._shared_sides)
 
     def test_all(self, image_set, batch_size: int = 100, frozen=None, verbose: bool = True, per_class_result: bool = False,
-                 hook=None, classes=None) -> List[dict]:
+                 hook=None, classes=None, features=None) -> List[dict]:
         """Dassl's `test()` for EVERY member in one pass over the set: per chunk one frozen image pass (none with `frozen`,
         a `FrozenImageKV` of this set) and one prompt-row pass for all S members.  Returns, per member, the dict
         `test(image_set, member=s)` returns.  `classes`: against that `ClassSet`."""
+        self._refuse_features(features, "test_all(features=...)")
         refuse_long_grid(self.cfg, f"{type(self).__name__}.test_all")
         return self._test_shared(image_set, self.n_runs, lambda: self._shared_sides(classes), batch_size, frozen, verbose,
                                  per_class_result, hook, classes=classes)

@@ -646,6 +646,30 @@ def eval_accumulate(logits, label, counts, cmat=None, pred=None):
     return counts
 
 
+def features_classify(feat, cls, bias, label, scale: float, norm_feat: bool, norm_cls: bool, counts, cmat=None, pred=None,
+                      logits_out=None):
+    """S classifiers over cached image features, head and evaluator in one launch (include/rpo_amd.h
+    rpo_features_classify): feat [n, e] fp32 (row stride >= e), cls [S, C, e], bias [S, C] or None, label int64 [n];
+    counts int64 [S, 2] and cmat int32 [S, C, C] accumulate, pred int32 [S, n] and logits_out [S, n, C] are overwritten.
+    Enqueue only."""
+    n, e = feat.shape
+    S, Cc = cls.shape[0], cls.shape[1]
+    assert feat.dtype == torch.float32 and feat.stride(1) == 1
+    assert cls.dtype == torch.float32 and cls.shape == (S, Cc, e) and cls.is_contiguous() and cls.device == feat.device
+    assert bias is None or (bias.dtype == torch.float32 and bias.shape == (S, Cc) and bias.is_contiguous())
+    assert label.dtype == torch.int64 and label.numel() == n and label.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.numel() == 2 * S and counts.is_contiguous()
+    assert cmat is None or (cmat.dtype == torch.int32 and cmat.numel() == S * Cc * Cc and cmat.is_contiguous())
+    assert pred is None or (pred.dtype == torch.int32 and pred.numel() == S * n and pred.is_contiguous())
+    assert logits_out is None or (logits_out.dtype == torch.float32 and logits_out.numel() == S * n * Cc
+                                  and logits_out.is_contiguous())
+    check(_lib.load().rpo_features_classify(feat.data_ptr(), feat.stride(0), cls.data_ptr(), _p(bias), label.data_ptr(),
+                                            float(scale), int(bool(norm_feat)), int(bool(norm_cls)), counts.data_ptr(),
+                                            _p(cmat), _p(pred), _p(logits_out), n, Cc, e, S, _stream()),
+          "rpo_features_classify")
+    return counts
+
+
 def metanet_fwd(img_f, w1, b1, w2, b2, f_norm, hidden, bias):
     B, e = img_f.shape
     h, d = w1.shape[0], w2.shape[0]

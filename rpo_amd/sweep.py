@@ -203,7 +203,8 @@ class RPOSweep(RPOMulti):
         return eng.m_img_prompt, eng.multi_text_features(), eng.m_k_used
 
     def test_all(self, image_set, batch_size: int = 100, frozen=None, verbose: bool = True, per_class_result: bool = False,
-                 hook=None, classes=None) -> List[dict]:
+                 hook=None, classes=None, features=None) -> List[dict]:
+        self._refuse_features(features, "test_all(features=...)")
         if classes is not None:
             self.class_set(None)                      # (refuses, by name and with the reason)
         return super().test_all(image_set, batch_size, frozen, verbose, per_class_result, hook)
@@ -216,8 +217,9 @@ class RPOSweep(RPOMulti):
         return self._sides_logits(image, lambda: self._member_sides(member))[0]
 
     def test(self, image_set, member: int = 0, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False,
-             frozen=None, classes=None):
+             frozen=None, classes=None, features=None):
         """Dassl's `test()` for member `member` (loop.EvalMixin._test_shared with that member alone)."""
+        self._refuse_features(features, "test(features=...)")
         if classes is not None:
             self.class_set(None)                      # (refuses, by name and with the reason)
         return self._test_shared(image_set, 1, lambda: self._member_sides(member), batch_size, frozen, verbose,

@@ -84,6 +84,9 @@ def lr_at_epoch(oc: OptimConfig, epoch: int) -> float:
 
 class RPO(LoopMixin):
     _takes_next_image = True         # run_epoch names the next batch: its patch embedding runs under this step
+    _features_why_not = ("RPO's image rows read its prompts, so no image feature outlives a step; what an image set can cache "
+                         "for RPO is the frozen rows' K / V: FrozenImageKV.build(engine, image_set) and test(..., frozen=...) "
+                         "/ train(..., val_frozen=...)")
     _takes_frozen = True             # test(..., frozen=...): the prompt-row pass alone on a set's cached frozen K / V
 
     def __init__(self, cfg: RPOConfig, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
@@ -546,11 +549,12 @@ class RPO(LoopMixin):
         return eng.img_prompt.unsqueeze(0), text_f, None
 
     def test(self, image_set, batch_size: int = 100, verbose: bool = True, per_class_result: bool = False, frozen=None,
-             hook=None, classes=None):
+             hook=None, classes=None, features=None):
         """Dassl's `test()` (loop.EvalMixin.test).  `frozen`: a `FrozenImageKV` built for this engine and set -- no image
         pass is run at all, only the K prompt rows per image on the cached frozen K / V (rpo_amd/frozen_kv.py).
         `classes`: a `ClassSet` -- the evaluation runs against its classes; a `FrozenImageKV` does not depend on the
         classes, so one cache serves every class set."""
+        self._refuse_features(features, "test(features=...)")
         if frozen is None:
             return super().test(image_set, batch_size, verbose, per_class_result, classes=classes)
         refuse_long_grid(self.cfg, "RPO.test(frozen=...)")

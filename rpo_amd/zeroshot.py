@@ -75,6 +75,15 @@ class ZeroshotCLIP(EvalMixin):
         """`model_inference` on a device batch without the clone (loop.EvalMixin.test)."""
         return self.engine.forward_plain(image, classes=classes)
 
+    @torch.no_grad()
+    def classifier(self, classes=None):
+        """The text features `forward_plain` classifies with (the prompts', `set_text_features`', or a `ClassSet`'s) as
+        the cosine classifier of rpo_features_classify (trainers/zsclip.py:58-63)."""
+        eng = self.engine
+        with torch.cuda.device(eng.dev):
+            cls = eng.plain_text_features() if classes is None else eng._cs_plain_current(eng._cs_check(classes))
+        return cls, None, True, True, eng.logit_scale_exp
+
 
 class ZeroshotCLIP2(ZeroshotCLIP):
     """Prompt ensembling (trainers/zsclip.py:63-99): the class names under T templates; the classifier is the normalised
@@ -96,6 +105,8 @@ class ZeroshotCLIP2(ZeroshotCLIP):
         super().__init__(state_dict, tokens[0], device, act_dtype, max_batch, cfg)
         T, n, _ = tokens.shape
         self.n_templates = T
+        self._template_tokens, self._template_chunk = tokens, chunk             # (held by reference: test_templates)
+        self._template_features = None
         with torch.cuda.device(self.engine.dev):
             feats = self.engine.encode_text(tokens.reshape(T * n, 77), chunk)         # [T * n, e], stays on the device
             acc = torch.empty(n, self.cfg.embed, dtype=torch.float32, device=self.device)
@@ -105,6 +116,25 @@ class ZeroshotCLIP2(ZeroshotCLIP):
 
     def set_context(self, ctx) -> None:
         raise NotImplementedError("ZeroshotCLIP2.set_context: a learned context belongs to one template, the ensemble has T")
+
+    @torch.no_grad()
+    def test_templates(self, image_set, features=None, verbose: bool = False, per_class_result: bool = False):
+        """The accuracy of EVERY template next to the ensemble's, from one launch on cached image features: T + 1
+        evaluator dicts -- template t's own classifier (its text features, as a `ZeroshotCLIP` built on that template
+        classifies), and the ensemble last (`test(image_set)`'s).  `features`: an `ImageFeatures` of this engine and set
+        (default: built here, one image pass).  The per-template text features are computed on the first call and kept."""
+        from .features import ImageFeatures, classify_many
+        if features is None:
+            features = ImageFeatures.build(self, image_set)
+        features.check(self.engine, image_set)
+        T, n, e = self.n_templates, self.cfg.n_cls, self.cfg.embed
+        with torch.cuda.device(self.engine.dev):
+            if self._template_features is None:
+                self._template_features = self.engine.encode_text(self._template_tokens.reshape(T * n, 77),
+                                                                  self._template_chunk).view(T, n, e)
+            cls = torch.cat([self._template_features, self.text_features.view(1, n, e)], 0)
+            return classify_many(features, cls, None, True, True, self.engine.logit_scale_exp, verbose=verbose,
+                                 per_class_result=per_class_result)
 
     @torch.no_grad()
     def class_set(self, tokens, chunk: Optional[int] = None):
