@@ -469,6 +469,22 @@ int rpo_lp_head_fwd_bwd(const float* img_f, const float* w, const float* bias, c
                         const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
                         float* g_w, float* g_bias, int B, int C, int e, float* workspace, void* stream);
 
+/* (ABI 8 addition) S linear-probe heads in the launches of one (the members of a sweep, rpo_amd/lp_sweep.py): the group is
+ * a grid dimension, four launches for training and two for eval whatever S is.  img_f [B,e], text_f_n [C,e] and label [B]
+ * are shared by all groups; group s has its own layer, row s of params = [W_s (e x e, out x in) | b_s (e)] with a row
+ * stride of set_stride floats, and writes z[s] ([S,B,e]), logits[s] ([S,B,C]), loss[s] ([S]) and row s of grads, which
+ * has the layout of params ([g_w | g_bias] per row).  Floats of a row beyond e*e + e (the padding up to set_stride) are
+ * never read or written, in params and in grads.  Per group, bit for bit, what rpo_lp_head_fwd_bwd gives on (img_f, W_s,
+ * b_s, text_f_n, label): the tiles, the split-k, every summation order are that call's, only the addresses differ.
+ * label NULL: eval, only z and logits are written.  A target outside [0, C) poisons every group (the labels are shared)
+ * as it poisons the ungrouped call.  workspace: S * rpo_lp_head_workspace_floats(B, C, e) floats, group s on slice s.
+ * The limits of rpo_lp_head_fwd_bwd on B, C, e, and 1 <= S <= 1024, set_stride >= e*e + e, else RPO_E_SHAPE;
+ * set_stride % 4 != 0 or img_f, params, z, text_f_n off the 16-byte grid: RPO_E_ALIGN; a NULL required pointer (grads and
+ * loss are required with a label): RPO_E_BADARG.  An error launches nothing.  No atomics, no allocation, capturable. */
+int rpo_lp_head_fwd_bwd_grouped(const float* img_f, const float* params, int64_t set_stride, const float* text_f_n,
+                                const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
+                                float* grads, int S, int B, int C, int e, float* workspace, void* stream);
+
 /* (ABI 8 addition) Prompt ensembling (trainers/zsclip.py:85-96, ZeroshotCLIP2): the classifier is the normalised mean over
  * the templates of the normalised text features.  rpo_amd/csrc/ensemble.hip.
  *   accumulate: acc[c,:] = (first ? 0 : acc[c,:]) + sum_t feat[t,c,:] / ||feat[t,c,:]||_2     t = 0 .. T-1, ascending

@@ -1,0 +1,10 @@
+"""rpo_amd: CLIP prompt-learning trainers on hand-written HIP for gfx950.  The trainers live in their own modules;
+`rpo_amd.LPSweep` resolves on first use, so importing the package stays as cheap as it was."""
+__all__ = ["LPSweep"]
+
+
+def __getattr__(name):
+    if name == "LPSweep":
+        from .lp_sweep import LPSweep
+        return LPSweep
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -176,6 +176,8 @@ SIGNATURES = {
     "rpo_lp_head_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "rpo_lp_head_fwd_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                     c_vp, c_vp]),
+    "rpo_lp_head_fwd_bwd_grouped": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                            c_i32, c_i32, c_vp, c_vp]),
     "rpo_text_ensemble_accumulate": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "rpo_text_ensemble_finish": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rpo_eval_accumulate": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

@@ -9,12 +9,14 @@
 //   lp_dz:     lse from the partials (fixed tile order); dz = G . text_f_n with G = scale (softmax - onehot) / B formed on
 //              the fly (split-k over the classes); block (0, 0) also writes the batch-mean loss
 //   lp_gw:     g_w = dz^T . img_f (K = B), g_bias = sum_b dz  (the blocks of input tile 0)
+// rpo_lp_head_fwd_bwd_grouped runs S such heads (the members of a linear-probe sweep: one layer each, shared features,
+// text features and labels) in the same four launches with the group as blockIdx.z, through the same tile functions.
 #include "common.h"
 
 namespace {
 
 constexpr int LP_WAVES = 8;                    // split-k waves of the three launches with a long k
-constexpr int LP_MAX_B = 128, LP_MAX_E = 1024, LP_MAX_C = 32768;
+constexpr int LP_MAX_B = 128, LP_MAX_E = 1024, LP_MAX_C = 32768, LP_MAX_S = 1024;
 
 // acc[r] of v_mfma_f32_32x32x2_f32 is D[(r & 3) + 8 (r >> 2) + 4 half][l31]; operands: lane (l31, half) gives A[l31][k0 + half]
 // and B[k0 + half][l31] (rpo_probe_mfma pins both maps; misc.hip's head kernels use the same)
@@ -69,8 +71,10 @@ __device__ __forceinline__ f32x16_t lp_reduce(f32x16_t d, float* red) {
   return s;
 }
 
-__global__ __launch_bounds__(64 * LP_WAVES) void lp_z_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* z, int B, int e) {
+// The four tiles as device functions: the ungrouped kernels call them on the caller's arrays, the grouped ones on group
+// blockIdx.z's slices (same instructions per tile either way, so a group has the bits of the ungrouped call).
+__device__ __forceinline__ void lp_z_tile(const float* __restrict__ x, const float* __restrict__ w,
+                                          const float* __restrict__ bias, float* z, int B, int e) {
   __shared__ float red[LP_WAVES * 16 * 64];
   const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5, wv = threadIdx.x >> 6;
   const int j0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
@@ -88,9 +92,8 @@ __global__ __launch_bounds__(64 * LP_WAVES) void lp_z_kernel(const float* __rest
 }
 
 // logits tile + per-row partial softmax statistics of its 32 classes: pmax / psum [C tiles][B]
-__global__ __launch_bounds__(64 * LP_WAVES) void lp_logits_kernel(const float* __restrict__ z, const float* __restrict__ t,
-                                                                  float* logits, float* pmax, float* psum, float scale,
-                                                                  int B, int C, int e) {
+__device__ __forceinline__ void lp_logits_tile(const float* __restrict__ z, const float* __restrict__ t, float* logits,
+                                               float* pmax, float* psum, float scale, int B, int C, int e) {
   __shared__ float red[LP_WAVES * 16 * 64];
   const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5, wv = threadIdx.x >> 6;
   const int c0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
@@ -131,10 +134,10 @@ __device__ __forceinline__ void lp_row_stats(const float* __restrict__ pmax, con
 }
 
 // dz[b][j] = sum_c G[b][c] t[c][j], G[b][c] = gmul (exp(logit - m_b) / s_b - [c == label_b]) (+ NaN for a bad label)
-__global__ __launch_bounds__(64 * LP_WAVES) void lp_dz_kernel(const float* __restrict__ logits, const float* __restrict__ t,
-                                                              const float* __restrict__ pmax, const float* __restrict__ psum,
-                                                              const int64_t* __restrict__ label, float* dz, float* loss,
-                                                              float gmul, int B, int C, int e) {
+__device__ __forceinline__ void lp_dz_tile(const float* __restrict__ logits, const float* __restrict__ t,
+                                           const float* __restrict__ pmax, const float* __restrict__ psum,
+                                           const int64_t* __restrict__ label, float* dz, float* loss, float gmul, int B, int C,
+                                           int e) {
   __shared__ float red[LP_WAVES * 16 * 64];
   __shared__ float s_m[32], s_inv[32], s_poison[32];
   __shared__ int s_lb[32];
@@ -194,8 +197,8 @@ __global__ __launch_bounds__(64 * LP_WAVES) void lp_dz_kernel(const float* __res
 }
 
 // g_w[j][i] = sum_b dz[b][j] x[b][i]  (one wave per 32 x 32 tile, k = b in order); g_bias[j] = sum_b dz[b][j] (input tile 0)
-__global__ __launch_bounds__(64) void lp_gw_kernel(const float* __restrict__ dz, const float* __restrict__ x, float* g_w,
-                                                   float* g_bias, int B, int e) {
+__device__ __forceinline__ void lp_gw_tile(const float* __restrict__ dz, const float* __restrict__ x, float* g_w,
+                                           float* g_bias, int B, int e) {
   const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
   const int j0 = blockIdx.x * 32, i0 = blockIdx.y * 32;
   f32x16_t d = lp_zero();
@@ -214,6 +217,68 @@ __global__ __launch_bounds__(64) void lp_gw_kernel(const float* __restrict__ dz,
     for (int b = 0; b < B; ++b) s += dz[(int64_t)b * e + j0 + l31];
     g_bias[j0 + l31] = s;
   }
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_z_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* z, int B, int e) {
+  lp_z_tile(x, w, bias, z, B, e);
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_logits_kernel(const float* __restrict__ z, const float* __restrict__ t,
+                                                                  float* logits, float* pmax, float* psum, float scale,
+                                                                  int B, int C, int e) {
+  lp_logits_tile(z, t, logits, pmax, psum, scale, B, C, e);
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_dz_kernel(const float* __restrict__ logits, const float* __restrict__ t,
+                                                              const float* __restrict__ pmax, const float* __restrict__ psum,
+                                                              const int64_t* __restrict__ label, float* dz, float* loss,
+                                                              float gmul, int B, int C, int e) {
+  lp_dz_tile(logits, t, pmax, psum, label, dz, loss, gmul, B, C, e);
+}
+
+__global__ __launch_bounds__(64) void lp_gw_kernel(const float* __restrict__ dz, const float* __restrict__ x, float* g_w,
+                                                   float* g_bias, int B, int e) {
+  lp_gw_tile(dz, x, g_w, g_bias, B, e);
+}
+
+// ---- S heads in the launches of one: group s = blockIdx.z.  Its layer is row s of `params` = [W_s (e x e) | b_s (e)] (row
+// stride `ps` floats, the gradient in the same layout), its z / logits / loss are slice s of [S, B, e] / [S, B, C] / [S],
+// its workspace is slice s of S slices of `wsf` floats = [dz (B e) | pmax (ct B) | psum (ct B)].  img_f, text_f_n and label
+// are shared.  Floats of a row past e e + e are never addressed.
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_z_grouped_kernel(const float* __restrict__ x,
+                                                                     const float* __restrict__ params, int64_t ps, float* z,
+                                                                     int B, int e) {
+  const int64_t s = blockIdx.z;
+  const float* w = params + s * ps;
+  lp_z_tile(x, w, w + (int64_t)e * e, z + s * B * e, B, e);
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_logits_grouped_kernel(const float* __restrict__ z,
+                                                                          const float* __restrict__ t, float* logits,
+                                                                          float* ws, int64_t wsf, float scale, int B, int C,
+                                                                          int e) {
+  const int64_t s = blockIdx.z;
+  float* pmax = ws + s * wsf + (int64_t)B * e;
+  lp_logits_tile(z + s * B * e, t, logits + s * B * C, pmax, pmax + (int64_t)((C + 31) / 32) * B, scale, B, C, e);
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_dz_grouped_kernel(const float* __restrict__ logits,
+                                                                      const float* __restrict__ t, float* ws, int64_t wsf,
+                                                                      const int64_t* __restrict__ label, float* loss,
+                                                                      float gmul, int B, int C, int e) {
+  const int64_t s = blockIdx.z;
+  float* dz = ws + s * wsf;
+  const float* pmax = dz + (int64_t)B * e;
+  lp_dz_tile(logits + s * B * C, t, pmax, pmax + (int64_t)((C + 31) / 32) * B, label, dz, loss + s, gmul, B, C, e);
+}
+
+__global__ __launch_bounds__(64) void lp_gw_grouped_kernel(const float* __restrict__ ws, int64_t wsf,
+                                                           const float* __restrict__ x, float* grads, int64_t ps, int B,
+                                                           int e) {
+  const int64_t s = blockIdx.z;
+  float* g_w = grads + s * ps;
+  lp_gw_tile(ws + s * wsf, x, g_w, g_w + (int64_t)e * e, B, e);
 }
 
 }  // namespace
@@ -242,5 +307,29 @@ extern "C" int rpo_lp_head_fwd_bwd(const float* img_f, const float* w, const flo
   hipLaunchKernelGGL(lp_dz_kernel, dim3(et, bt), dim3(64 * LP_WAVES), 0, s, logits, text_f_n, pmax, psum, label, dz, loss,
                      scale_exp / (float)B, B, C, e);
   hipLaunchKernelGGL(lp_gw_kernel, dim3(et, et), dim3(64), 0, s, dz, img_f, g_w, g_bias, B, e);
+  return rpo_launch_status();
+}
+
+extern "C" int rpo_lp_head_fwd_bwd_grouped(const float* img_f, const float* params, int64_t set_stride,
+                                           const float* text_f_n, const int64_t* label, float scale_exp, float* z,
+                                           float* logits, float* loss, float* grads, int S, int B, int C, int e,
+                                           float* workspace, void* stream) {
+  if (!img_f || !params || !text_f_n || !z || !logits || !workspace) return RPO_E_BADARG;
+  if (label && (!loss || !grads)) return RPO_E_BADARG;
+  if (B < 1 || B > LP_MAX_B || C < 1 || C > LP_MAX_C || e < 32 || e > LP_MAX_E || e % 32 != 0) return RPO_E_SHAPE;
+  if (S < 1 || S > LP_MAX_S || set_stride < (int64_t)e * e + e) return RPO_E_SHAPE;
+  if (set_stride % 4 != 0 || !aligned16(img_f) || !aligned16(params) || !aligned16(z) || !aligned16(text_f_n))
+    return RPO_E_ALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int bt = (B + 31) / 32, ct = (C + 31) / 32, et = e / 32;
+  const int64_t wsf = rpo_lp_head_workspace_floats(B, C, e);
+  hipLaunchKernelGGL(lp_z_grouped_kernel, dim3(et, bt, S), dim3(64 * LP_WAVES), 0, st, img_f, params, set_stride, z, B, e);
+  hipLaunchKernelGGL(lp_logits_grouped_kernel, dim3(ct, bt, S), dim3(64 * LP_WAVES), 0, st, z, text_f_n, logits, workspace,
+                     wsf, scale_exp, B, C, e);
+  if (!label) return rpo_launch_status();
+  hipLaunchKernelGGL(lp_dz_grouped_kernel, dim3(et, bt, S), dim3(64 * LP_WAVES), 0, st, logits, text_f_n, workspace, wsf,
+                     label, loss, scale_exp / (float)B, B, C, e);
+  hipLaunchKernelGGL(lp_gw_grouped_kernel, dim3(et, et, S), dim3(64), 0, st, workspace, wsf, img_f, grads, set_stride,
+                     B, e);
   return rpo_launch_status();
 }

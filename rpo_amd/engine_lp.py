@@ -58,3 +58,41 @@ class LpEngineMixin:
                             self.lp_z[:B], self.logits[:B], self.loss if train else None, self.lp_gw if train else None,
                             self.lp_gb if train else None, self.lp_ws)
         return self.logits[:B]
+
+    # ---- the members of a sweep (rpo_amd/lp_sweep.py): S layers behind ONE image pass -------------
+    def lp_sweep_setup(self, S: int) -> None:
+        """Buffers of S linear probes on the shared image feature: `lps_params` / `lps_grads` / `lps_moms` [S, stride] fp32,
+        row s = [W_s (e x e, out x in) | b_s (e)] (stride = e e + e, a multiple of 32: every row is 16-byte aligned and the
+        rows are the optimiser's sets), `lps_z` [S, max_batch, e], `lps_logits` [S, max_batch, n_cls], `lps_loss` [S] and
+        the grouped head's workspace.  Nothing here is allocated unless this is called; `lp_setup`'s buffers stay as they
+        are (the text features are its own, shared)."""
+        cfg, dev = self.cfg, self.dev
+        e, n, mb = cfg.embed, cfg.n_cls, self.max_batch
+        if not 1 <= S <= 1024:
+            raise ValueError(f"lp_sweep_setup: {S} members (rpo_lp_head_fwd_bwd_grouped takes 1 .. 1024 groups)")
+        if getattr(self, "lp_text_f_n", None) is None:
+            self.lp_setup()
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        self.lps_S, self.lps_stride = S, e * e + e
+        self.lps_params = torch.zeros(S, self.lps_stride, dtype=torch.float32, device=dev)
+        self.lps_grads = torch.zeros(S, self.lps_stride, dtype=torch.float32, device=dev)
+        self.lps_moms = torch.zeros(S, self.lps_stride, dtype=torch.float32, device=dev)
+        self.lps_w = self.lps_params[:, :e * e].view(S, e, e)                # (views: member s's weight [e, e], bias [e])
+        self.lps_b = self.lps_params[:, e * e:]
+        self.lps_z, self.lps_logits, self.lps_loss = f32(S, mb, e), f32(S, mb, n), torch.zeros(S, dtype=torch.float32, device=dev)
+        self.lps_ws = f32(S * ops.lp_head_workspace_floats(mb, n, e))
+
+    def lp_sweep_forward_backward(self, image: torch.Tensor, label: Optional[torch.Tensor]) -> torch.Tensor:
+        """`lp_forward_backward` for the S members: ONE plain image pass, ONE grouped head call (four launches, two for
+        eval, whatever S is).  With `label`, `lps_loss` [S] and `lps_grads` [S, stride]; member s's bits are those of
+        `lp_forward_backward` with its layer.  Capturable in a HIP graph.  Returns logits [S, B, n_cls], the leading
+        S B n_cls floats of `lps_logits` (valid until the next call)."""
+        B = self._plain_image_features(image)
+        S, train = self.lps_S, label is not None
+        e, n = self.cfg.embed, self.cfg.n_cls
+        z = self.lps_z.view(-1)[:S * B * e].view(S, B, e)                     # (the call's arrays are dense in B)
+        logits = self.lps_logits.view(-1)[:S * B * n].view(S, B, n)
+        ops.lp_head_fwd_bwd_grouped(self.img_cls_f[:B], self.lps_params, self.lp_text_f_n, label, self.logit_scale_exp,
+                                    z, logits, self.lps_loss if train else None, self.lps_grads if train else None,
+                                    self.lps_ws)
+        return logits

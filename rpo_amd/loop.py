@@ -212,6 +212,10 @@ class LoopMixin(EvalMixin):
     def _loop_new_losses(self, nb: int) -> torch.Tensor:
         return torch.zeros(nb, dtype=torch.float32, device=self.device)
 
+    def _loop_loss(self) -> torch.Tensor:
+        """The device loss of the step just enqueued: a scalar, or [S] for a trainer that steps S members (LPSweep)."""
+        return self.engine.loss
+
     def _loop_new_counts(self) -> torch.Tensor:
         return torch.zeros(2, dtype=torch.int64, device=self.device)
 
@@ -256,13 +260,14 @@ class LoopMixin(EvalMixin):
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._enqueue(self._img, self._lab)
                 self._graph = (g, key)
+                self.captures = getattr(self, "captures", 0) + 1
                 # (capture does not execute: the replay below is this step)
             if image.data_ptr() != self._img.data_ptr():
                 self._img.copy_(image, non_blocking=True)
             self._lab.copy_(label, non_blocking=True)
             self._graph[0].replay()
         self._steps += 1
-        return self.engine.loss
+        return self._loop_loss()
 
     # ---- the loops -----------------------------------------------------------------------------------------
     def run_epoch(self, image_set, generator: Optional[torch.Generator] = None, plans=None) -> Dict[str, torch.Tensor]:
@@ -295,7 +300,7 @@ class LoopMixin(EvalMixin):
                     loss = self.step_async(cur, labels[t], next_image=nxt)
                 else:
                     loss = self.step_async(cur, labels[t])
-                losses[t:t + 1].copy_(loss.reshape(1), non_blocking=True)
+                losses[t].copy_(loss.reshape(losses.shape[1:]), non_blocking=True)
                 if counts is not None:
                     self._loop_accumulate(labels[t], counts)
                 if getattr(self, "detect_anomaly", False):

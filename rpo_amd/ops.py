@@ -606,6 +606,29 @@ def lp_head_fwd_bwd(img_f, w, bias, text_f_n, label, scale_exp: float, z, logits
     return logits
 
 
+def lp_head_fwd_bwd_grouped(img_f, params, text_f_n, label, scale_exp: float, z, logits, loss, grads, ws):
+    """S linear-probe heads in the launches of one (include/rpo_amd.h rpo_lp_head_fwd_bwd_grouped): params / grads
+    [S, stride >= e e + e] fp32 with one row stride, row s = [W_s | b_s]; z [S, B, e], logits [S, B, C], loss [S]; img_f,
+    text_f_n and label are shared.  label None = eval (z and logits only)."""
+    B, e = img_f.shape
+    Cc = text_f_n.shape[0]
+    S, stride = params.shape[0], params.stride(0)
+    assert params.dim() == 2 and params.stride(1) == 1 and params.shape[1] >= e * e + e and text_f_n.shape == (Cc, e)
+    assert z.shape == (S, B, e) and logits.shape == (S, B, Cc)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in [img_f, text_f_n, z, logits, ws])
+    assert params.dtype == torch.float32
+    if label is not None:
+        assert label.dtype == torch.int64 and label.numel() == B and loss.dtype == torch.float32 and loss.numel() == S
+        assert loss.is_contiguous() and grads.dtype == torch.float32 and grads.shape[0] == S and grads.stride(1) == 1
+        assert grads.stride(0) == stride and grads.shape[1] >= e * e + e, "grads has the layout of params"
+    assert ws.numel() >= S * lp_head_workspace_floats(B, Cc, e)
+    check(_lib.load().rpo_lp_head_fwd_bwd_grouped(img_f.data_ptr(), params.data_ptr(), stride, text_f_n.data_ptr(),
+                                                  _p(label), scale_exp, z.data_ptr(), logits.data_ptr(), _p(loss),
+                                                  _p(grads), S, B, Cc, e, ws.data_ptr(), _stream()),
+          "rpo_lp_head_fwd_bwd_grouped")
+    return logits
+
+
 def text_ensemble_accumulate(feat, n_cls: int, acc, first: bool = True, template_stride_rows: Optional[int] = None):
     """Prompt ensembling, first half (include/rpo_amd.h rpo_text_ensemble_accumulate): feat [rows, e] fp32 (row stride >= e)
     holds T blocks of n_cls rows, block t at row t * template_stride_rows (default n_cls: T = rows / n_cls); adds every
