@@ -391,6 +391,26 @@ int rpo_text_attn_bwd_dense(const void* q, const void* k, const void* v, int64_t
                             void* dq, void* dk, void* dv, int64_t ldd, int dtype, const int32_t* len, int n_cls,
                             int Lmax, int H, float scale, void* stream);
 
+/* (ABI 8 addition) The causal = 1 forward for n_img * n_cls sequences of P + S positions whose first P rows are SHARED by
+ * the n_cls sequences of an image -- CoCoOp's [SOS | ctx + bias[b] | name . EOT] (trainers/cocoop.py:123-161) under the plain
+ * causal mask: the P = 1 + n_ctx leading rows read only themselves, so they are the same for every class of image b and are
+ * stored once.  q, k, v [rows, ld] and out [rows, ldo] are ONE contiguous row set (LayerNorm and the GEMMs run over it
+ * unchanged), rows = n_img * P + n_img * n_cls * S:
+ *   prefix row (b, p)    at b * P + p:                            position p of every sequence of image b
+ *   suffix row (b, c, s) at n_img * P + (b * n_cls + c) * S + s:  position P + s of sequence (b, c)
+ * len: int32 device array [n_cls], the class's length SOS .. EOT, shared by the images; the caller guarantees
+ * len[c] >= P + 3.  Prefix row (b, p) reads prefix keys (b, 0 .. p); suffix row (b, c, s) reads the P prefix keys of image
+ * b, then suffix keys (b, c, 0 .. s), nk = min(P + s + 1, len[c]) keys in all (rows past the EOT: as rpo_text_attn_fwd).
+ * fp32 VALU arithmetic of rpo_text_attn_fwd's causal kernel, keys in position order: given the same q / k / v values the
+ * output holds THE BITS of rpo_text_attn_fwd(causal = 1, Lmax = P + S) on the sequences gathered densely to
+ * [n_img * n_cls * (P + S)] rows.  One workgroup per (image, head, 4 classes, 4 suffix rows) stages the image's prefix K / V
+ * head slice once.
+ * P + S <= 80 (else RPO_E_SHAPE, as a launch grid over 2^31 - 1 workgroups); k, v and the rows of ld / ldo 16-byte aligned
+ * (RPO_E_ALIGN); f32, bf16 and f16 storage. */
+int rpo_text_attn_fwd_prefix(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo,
+                             int dtype, const int32_t* len, int n_img, int n_cls, int P, int S, int H,
+                             float scale, void* stream);
+
 /* CoCoOp's meta-net (trainers/cocoop.py:93-97, PromptLearner.forward :137-143): bias[b] = linear2(relu(linear1(f[b] /
  * |f[b]|))) for the B raw image features img_f [B, e]; w1 [h, e], b1 [h], w2 [d, h], b2 [d], all fp32.  f_norm [B, e] and
  * hidden [B, h] are kept for rpo_metanet_bwd, which turns d_bias [B, d] into the gradients of the four tensors (batch sum

@@ -122,7 +122,9 @@ class ClassSetEngineMixin:
                                       "mean nothing for another class")
         if getattr(self, "coop_hidden", 0):
             raise NotImplementedError("class_set: CoCoOp's per-image text tower is sized for the classes the engine was "
-                                      "built with; other class sets are out of scope for it")
+                                      "built with and its text features depend on the image, so no cached [n', e] "
+                                      "matrix can serve it; use conditional_class_set(tokens), the per-image "
+                                      "shared-prefix pass (rpo_amd/engine_cocoop_eval.py)")
         return ClassSet(self, tokens, chunk)
 
     def _cs_check(self, cs) -> ClassSet:

@@ -236,6 +236,154 @@ int launch(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t l
   return rpo_launch_status();
 }
 
+// ---- causal forward with a per-image shared prefix (rpo_text_attn_fwd_prefix) -----------------------------------------
+// CoCoOp's prompt of image b and class c is [SOS | ctx + bias[b] | name . EOT] (trainers/cocoop.py:123-161) under the plain
+// causal mask: the first P = 1 + n_ctx rows read only themselves, so through every block they are the same for all classes
+// of an image and are stored ONCE per image.  Rows: n_img * P prefix rows (b * P + p), then the suffix rows
+// n_img * P + (b * n_cls + c) * S + s, which stand for position P + s of sequence (b, c).  One workgroup per (image, head,
+// group of PREFIX_GROUP classes) and chunk of PREFIX_ROWS suffix rows (blockIdx.y) stages the image's P prefix keys /
+// values once and walks its classes NC at a time: every class in flight has its own S-row suffix region behind the prefix
+// (only the keys the chunk's rows can see are staged), wave w serves slot w % NC and the chunk's rows w / NC, w / NC + 4 / NC,
+// ...  Four classes x four rows = four rows per wave: a row is ~1.5 k dependent VALU instructions, so, as for
+// text_attn_kernel, spreading the rows over workgroups is what shortens a launch (measured with 8 classes x all rows per
+// workgroup: one image x 19 classes took 0.7 ms longer per 12-block pass than the dense kernel on MORE rows).  The
+// workgroup of class group 0 and row chunk 0 also writes the P prefix rows' outputs.
+// Arithmetic: text_attn_kernel's causal forward, operation for operation (lane = key for the scores, keys in position
+// order, the same reductions) -- key j is prefix row j below P and suffix row j - P from there on, which changes where an
+// operand is read and nothing else: the bits of rpo_text_attn_fwd(causal = 1) on the sequences gathered densely.
+constexpr int PREFIX_GROUP = 4;                // classes per workgroup: the P-row prefix is staged once per 4 classes x 4 rows
+constexpr int PREFIX_ROWS = 4;                 // suffix rows per class and workgroup
+
+template <typename T>
+__device__ __forceinline__ void stage_kv_rows(const T* __restrict__ k, const T* __restrict__ v, int64_t ld, int64_t row0,
+                                              int nrows, int col0, float* Kd, float* Vd, int tid) {
+  constexpr int EPC = 16 / sizeof(T);          // elements per 16-B chunk
+  constexpr int CPR = 64 / EPC;                // chunks per key row
+  for (int id = tid; id < nrows * CPR; id += 256) {
+    const int j = id / CPR, cch = id % CPR;
+    const int64_t off = (row0 + j) * ld + col0 + cch * EPC;
+    const uint4 kq = *reinterpret_cast<const uint4*>(k + off);
+    const uint4 vq = *reinterpret_cast<const uint4*>(v + off);
+    float* kd = Kd + j * 65 + cch * EPC;
+    float* vd = Vd + j * 65 + cch * EPC;
+    const uint32_t kw[4] = {kq.x, kq.y, kq.z, kq.w};
+    const uint32_t vw[4] = {vq.x, vq.y, vq.z, vq.w};
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        kd[2 * e] = unpack1<T>((uint16_t)(kw[e] & 0xffffu)); kd[2 * e + 1] = unpack1<T>((uint16_t)(kw[e] >> 16));
+        vd[2 * e] = unpack1<T>((uint16_t)(vw[e] & 0xffffu)); vd[2 * e + 1] = unpack1<T>((uint16_t)(vw[e] >> 16));
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { kd[e] = __uint_as_float(kw[e]); vd[e] = __uint_as_float(vw[e]); }
+    }
+  }
+}
+
+// one query row of a wave: keys [0, nk), the first min(nk, P) of them in Kp / Vp, the others in Ks / Vs
+template <typename T>
+__device__ __forceinline__ void prefix_attn_row(const T* __restrict__ qrow, T* orow, const float* Kp, const float* Vp,
+                                                const float* Ks, const float* Vs, int P, int Lmax, int nk, float scale,
+                                                int lane) {
+  const int j0 = min(lane, Lmax - 1), j1 = min(lane + 64, Lmax - 1);
+  const float* k0 = j0 < P ? Kp + j0 * 65 : Ks + (j0 - P) * 65;
+  const float* k1 = j1 < P ? Kp + j1 * 65 : Ks + (j1 - P) * 65;
+  const float qv = ActIO<T>::ld(qrow + lane);
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll 8
+  for (int d = 0; d < 64; ++d) {
+    const float qd = bcast(qv, d);
+    s0 = fmaf(qd, k0[d], s0);
+    s1 = fmaf(qd, k1[d], s1);
+  }
+  s0 = lane < nk ? s0 * scale : -INFINITY;
+  s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
+  const float m = wave_max(fmaxf(s0, s1));
+  float p0 = expf(s0 - m), p1 = expf(s1 - m);
+  const float inv = 1.0f / wave_sum(p0 + p1);
+  p0 *= inv; p1 *= inv;
+  float acc = 0.f;
+  const int np = min(nk, P);
+  for (int j = 0; j < np; ++j) {
+    const float pj = j < 64 ? bcast(p0, j) : bcast(p1, j - 64);
+    acc = fmaf(pj, Vp[j * 65 + lane], acc);
+  }
+  for (int j = np; j < nk; ++j) {
+    const float pj = j < 64 ? bcast(p0, j) : bcast(p1, j - 64);
+    acc = fmaf(pj, Vs[(j - P) * 65 + lane], acc);
+  }
+  ActIO<T>::st(orow + lane, acc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void text_attn_prefix_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                               const T* __restrict__ v, int64_t ld, T* out, int64_t ldo,
+                                                               const int32_t* __restrict__ len, int n_img, int n_cls,
+                                                               int P, int S, int H, int NC, int groups, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Kp = reinterpret_cast<float*>(smem);   // [P][65]
+  float* Vp = Kp + P * 65;
+  float* Sb = Vp + P * 65;                      // NC slots of (K [S][65] | V [S][65])
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = blockIdx.x % H, bg = blockIdx.x / H;
+  const int g = bg % groups, b = bg / groups;
+  const int Lmax = P + S, col0 = h * 64;
+  const int64_t suf0 = (int64_t)n_img * P;      // first suffix row
+  stage_kv_rows<T>(k, v, ld, (int64_t)b * P, P, col0, Kp, Vp, tid);
+  __syncthreads();
+  if (g == 0 && blockIdx.y == 0) {              // the image's own prefix rows: row p reads prefix keys 0 .. p
+    for (int p = wave; p < P; p += 4) {
+      const int64_t row = (int64_t)b * P + p;
+      prefix_attn_row<T>(q + row * ld + col0, out + row * ldo + col0, Kp, Vp, Sb, Sb, P, Lmax, p + 1, scale, lane);
+    }
+  }
+  const int c_end = min(n_cls, (g + 1) * PREFIX_GROUP);
+  const int s_lo = blockIdx.y * PREFIX_ROWS, s_hi = min(S, s_lo + PREFIX_ROWS);      // this workgroup's suffix rows
+  const int slot = wave % NC, s_first = s_lo + wave / NC, s_step = 4 / NC;
+  for (int c0 = g * PREFIX_GROUP; c0 < c_end; c0 += NC) {      // (uniform over the workgroup: the barriers below)
+    for (int i = 0; i < NC && c0 + i < c_end; ++i) {
+      const int L = min(len[c0 + i], Lmax);
+      const int ns = max(0, min(s_hi, L - P));   // suffix keys the rows below s_hi of this class read
+      float* Ks = Sb + i * 2 * S * 65;
+      stage_kv_rows<T>(k, v, ld, suf0 + ((int64_t)b * n_cls + c0 + i) * S, ns, col0, Ks, Ks + S * 65, tid);
+    }
+    __syncthreads();
+    const int c = c0 + slot;
+    if (c < c_end) {
+      const int L = min(len[c], Lmax);
+      const float* Ks = Sb + slot * 2 * S * 65;
+      for (int s = s_first; s < s_hi; s += s_step) {
+        const int64_t row = suf0 + ((int64_t)b * n_cls + c) * S + s;
+        prefix_attn_row<T>(q + row * ld + col0, out + row * ldo + col0, Kp, Vp, Ks, Ks + S * 65, P, Lmax,
+                           min(P + s + 1, L), scale, lane);
+      }
+    }
+    __syncthreads();                            // the slots are re-staged by the next round
+  }
+}
+
+// classes in flight per workgroup: the most of 4, 2, 1 whose LDS stays within 32 KB (five workgroups per CU of 160 KB: the
+// rows are chains of dependent VALU and LDS instructions, which other waves hide); one class alone needs at most
+// 2 * 80 * 65 * 4 = 41.6 KB
+static inline int prefix_lds_bytes(int P, int S, int NC) { return 2 * 65 * 4 * (P + NC * S); }
+
+template <typename T>
+int launch_prefix(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo, const int32_t* len,
+                  int n_img, int n_cls, int P, int S, int H, float scale, hipStream_t s) {
+  static rpo_lds_mask_t lds_ok{0};
+  auto kern = text_attn_prefix_kernel<T>;
+  int NC = 4;
+  while (NC > 1 && prefix_lds_bytes(P, S, NC) > 32 * 1024) NC >>= 1;
+  const int groups = (n_cls + PREFIX_GROUP - 1) / PREFIX_GROUP;
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), 64 * 1024, &lds_ok)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)n_img * groups * H), (S + PREFIX_ROWS - 1) / PREFIX_ROWS), dim3(256),
+                     prefix_lds_bytes(P, S, NC), s,
+                     static_cast<const T*>(q), static_cast<const T*>(k), static_cast<const T*>(v), ld, static_cast<T*>(out),
+                     ldo, len, n_img, n_cls, P, S, H, NC, groups, scale);
+  return rpo_launch_status();
+}
+
 }  // namespace
 
 // n_kv < n_cls: the n_cls classes are VIRTUAL -- class v reads len[v % n_kv] and the cache rows of class v % n_kv
@@ -330,4 +478,20 @@ extern "C" int rpo_text_attn_bwd_dense(const void* q, const void* k, const void*
   if (dtype == RPO_BF16) return launch_dense<bf16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_cls, Lmax, H, scale, s);
   if (dtype == RPO_F32) return launch_dense<float>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_cls, Lmax, H, scale, s);
   return RPO_E_DTYPE;
+}
+
+extern "C" int rpo_text_attn_fwd_prefix(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo,
+                                        int dtype, const int32_t* len, int n_img, int n_cls, int P, int S, int H,
+                                        float scale, void* stream) {
+  if (!q || !k || !v || !out || !len || n_img < 1 || n_cls < 1 || P < 1 || S < 1 || H < 1) return RPO_E_BADARG;
+  if ((int64_t)P + S > 80) return RPO_E_SHAPE;
+  const int64_t wgs = (int64_t)n_img * ((n_cls + PREFIX_GROUP - 1) / PREFIX_GROUP) * H;
+  if (wgs > 2147483647ll) return RPO_E_SHAPE;
+  if (dtype != RPO_F32 && dtype != RPO_BF16 && dtype != RPO_F16) return RPO_E_DTYPE;
+  const int esz = dtype == RPO_F32 ? 4 : 2;
+  if (!aligned16(k) || !aligned16(v) || (ld * esz) % 16 != 0 || (ldo * esz) % 16 != 0) return RPO_E_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == RPO_F16) return launch_prefix<f16_t>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
+  if (dtype == RPO_BF16) return launch_prefix<bf16_t>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
+  return launch_prefix<float>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
 }

@@ -78,6 +78,10 @@ class EvalMixin:
         image_set.check_labels(classes.n)
         return classes.n
 
+    def _test_chunk(self, batch_size: int, classes) -> int:
+        """Images `test` hands to the eval forward at a time: what the engine's image pass takes."""
+        return max(1, min(batch_size, self.engine.max_batch))
+
     # ---- cached image features (rpo_amd/features.py): for the trainers whose image feature depends on nothing they train
     _features_why_not: Optional[str] = None        # why `features=` / `val_features=` cannot serve this trainer, or None
 
@@ -113,7 +117,7 @@ class EvalMixin:
         if features is not None:
             return self._test_features(image_set, features, verbose, per_class_result, classes)
         n, C = len(image_set), self._n_classes(image_set, classes)
-        chunk = max(1, min(batch_size, self.engine.max_batch))
+        chunk = self._test_chunk(batch_size, classes)
         ev = Classification(C, per_class_result)
         with torch.cuda.device(self.device):
             tf = self._loop_transform(False, chunk)

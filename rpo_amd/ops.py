@@ -523,6 +523,19 @@ def text_attn_fwd_shared(q, kc, vc, out, len_i32, n_cls: int, n_kv: int, rows: i
     return out
 
 
+def text_attn_fwd_prefix(q, k, v, out, len_i32, n_img: int, n_cls: int, P: int, S: int, H: int, scale: float = 0.125):
+    """The causal text attention of n_img * n_cls sequences whose first P rows are shared by the classes of an image
+    (include/rpo_amd.h: rpo_text_attn_fwd_prefix): n_img * P prefix rows, then n_img * n_cls * S suffix rows."""
+    rows = n_img * P + n_img * n_cls * S
+    assert _ld(q) == _ld(k) == _ld(v) and len_i32.dtype == torch.int32 and len_i32.numel() >= n_cls
+    assert q.dtype == k.dtype == v.dtype == out.dtype
+    assert min(q.shape[0], k.shape[0], v.shape[0], out.shape[0]) >= rows and min(q.shape[1], out.shape[1]) >= H * 64
+    check(_lib.load().rpo_text_attn_fwd_prefix(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ld(q), out.data_ptr(), _ld(out),
+                                               dtype_code(q.dtype), len_i32.data_ptr(), n_img, n_cls, P, S, H, scale,
+                                               _stream()), "rpo_text_attn_fwd_prefix")
+    return out
+
+
 def text_attn_bwd_shared(q, kc, vc, da, dq, len_i32, n_cls: int, n_kv: int, rows: int, Lmax: int, H: int, scale: float = 0.125):
     """`text_attn_bwd` for n_cls virtual classes on the cache of n_kv real ones (rpo_text_attn_bwd_shared)."""
     assert _ld(kc) == _ld(vc) and len_i32.dtype == torch.int32 and len_i32.numel() >= n_kv
