@@ -682,8 +682,16 @@ typedef struct rpo_image_desc {
 int rpo_preprocess_ksize(int in_size, int out_size);
 /* bytes of caller-owned workspace for B images, output size `size`, crops of at most max_rows rows, kmax taps */
 size_t rpo_preprocess_workspace_bytes(int B, int size, int max_rows, int kmax);
+/* (ABI 8 addition) The descriptor validation of rpo_preprocess_batch on its own: pure host code, no HIP call, nothing
+ * launched, usable on a machine without a GPU.  desc_host: B descriptors in host memory; src_bytes: size of the buffer the
+ * src_offset fields index.  A null pointer or B, size, max_rows or kmax <= 0: RPO_E_BADARG.  RPO_E_SHAPE: a non-positive
+ * image or crop size, a crop box that leaves the image, resize_w/h < size, a window that leaves the resized image, or an
+ * image that does not lie inside [0, src_bytes).  RPO_E_WORKSPACE: rpo_preprocess_ksize of an axis > kmax, or
+ * crop_h > max_rows.  Every field may hold any value of its type: no test inside forms a sum or product that overflows. */
+int rpo_preprocess_check(const rpo_image_desc* desc_host, int B, int size, int max_rows, int kmax, int64_t src_bytes);
 /* src: device buffer holding the B images; desc_host/desc_dev: the same B descriptors in host and device memory
- * (the host copy is validated -> RPO_E_SHAPE / RPO_E_WORKSPACE, the device copy is what the kernels read);
+ * (the host copy is validated by rpo_preprocess_check after the pointer, workspace and alignment checks, and its code is
+ * returned unchanged; the device copy is what the kernels read);
  * mean3/std3: host pointers; out: fp32 [B, 3, size, size] device.  Enqueues three kernels on `stream`. */
 int rpo_preprocess_batch(const uint8_t* src, int64_t src_bytes, const rpo_image_desc* desc_host,
                          const rpo_image_desc* desc_dev, int B, int size, int max_rows, int kmax,

@@ -203,6 +203,7 @@ SIGNATURES = {
     "rpo_probe_peak_copy": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "rpo_preprocess_ksize": (c_i32, [c_i32, c_i32]),
     "rpo_preprocess_workspace_bytes": (C.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    "rpo_preprocess_check": (c_i32, [C.POINTER(ImageDesc), c_i32, c_i32, c_i32, c_i32, c_i64]),
     "rpo_preprocess_batch": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                      C.c_size_t, c_vp]),
     "rpo_jpeg_probe": (c_i32, [c_vp, c_i64, C.POINTER(JpegInfo)]),

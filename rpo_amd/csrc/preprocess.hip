@@ -4,12 +4,13 @@
 // The arithmetic reproduced is Pillow's 8-bit bicubic resample (the reference's transforms end in
 // `PIL.Image.resize(..., BICUBIC)` through torchvision): separable, horizontal pass then vertical pass, both with
 // uint8 results; coefficients computed in DOUBLE, normalised, rounded to 22-bit fixed point; support =
-// 2 * max(scale, 1).  Results are bit-identical to Pillow (tests/test_gpu_preprocess.py), so this file is compiled
-// with -ffp-contract=off: an FMA in the coefficient math would change the rounding.
+// 2 * max(scale, 1).  Results are bit-identical to Pillow (tests/test_gpu_preprocess.py at 224, tests/
+// test_gpu_preprocess_sizes.py at 256 .. 513), so this file is compiled with -ffp-contract=off: an FMA in the
+// coefficient math would change the rounding.
 //
-// Three kernels per batch, all HBM/L2-bound byte work (no MFMA):
-//   coeff_kernel    per (image, axis): bounds + int32 coefficients of the 224 output positions -> workspace
-//   horiz_kernel    per (image, source row): 224 x 3 uint8 outputs from the cropped row       -> workspace temp
+// Three kernels per batch, all HBM/L2-bound byte work (no MFMA); `size` output positions, 256 threads at a time:
+//   coeff_kernel    per (image, axis): bounds + int32 coefficients of the size output positions -> workspace
+//   horiz_kernel    per (image, source row): size x 3 uint8 outputs from the cropped row       -> workspace temp
 //   vert_norm_kernel per (image, output row): vertical pass, flip, ToTensor (/255) and Normalize -> fp32 NCHW
 #include "common.h"
 
@@ -151,31 +152,47 @@ extern "C" int rpo_preprocess_ksize(int in_size, int out_size) {
   if (in_size == out_size) return 1;
   const double scale = (double)((float)in_size) / out_size;
   const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
-  return (int)ceil(support) * 2 + 1;
+  const double k = ceil(support) * 2 + 1;          // in double: 2^31 - 1 -> 1 needs more taps than an int holds
+  return k > 2147483647.0 ? 2147483647 : (int)k;
+}
+
+// The descriptors are the only untrusted input of rpo_preprocess_batch.  Pure host code, no HIP call.  Every field is
+// attacker-sized (any int32 / int64), so no comparison forms a sum or product that can overflow: a bound is tested by
+// subtracting on the side already known to be non-negative.
+extern "C" int rpo_preprocess_check(const rpo_image_desc* desc_host, int B, int size, int max_rows, int kmax,
+                                    int64_t src_bytes) {
+  if (!desc_host || B <= 0 || size <= 0 || max_rows <= 0 || kmax <= 0) return RPO_E_BADARG;
+  for (int b = 0; b < B; ++b) {
+    const rpo_image_desc& d = desc_host[b];
+    if (d.width <= 0 || d.height <= 0 || d.crop_w <= 0 || d.crop_h <= 0 || d.crop_x < 0 || d.crop_y < 0)
+      return RPO_E_SHAPE;
+    if (d.crop_w > d.width || d.crop_x > d.width - d.crop_w || d.crop_h > d.height || d.crop_y > d.height - d.crop_h)
+      return RPO_E_SHAPE;
+    if (d.resize_w < size || d.resize_h < size || d.win_x < 0 || d.win_y < 0 || d.win_x > d.resize_w - size ||
+        d.win_y > d.resize_h - size)
+      return RPO_E_SHAPE;
+    // width * height * 3 <= src_bytes, tested by division; then the product fits and src_bytes - bytes >= 0
+    if (d.src_offset < 0 || src_bytes < 0 || d.height > src_bytes / 3 / d.width) return RPO_E_SHAPE;
+    const int64_t bytes = (int64_t)d.width * d.height * 3;
+    if (d.src_offset > src_bytes - bytes) return RPO_E_SHAPE;
+    if (rpo_preprocess_ksize(d.crop_w, d.resize_w) > kmax || rpo_preprocess_ksize(d.crop_h, d.resize_h) > kmax)
+      return RPO_E_WORKSPACE;
+    if (d.crop_h > max_rows) return RPO_E_WORKSPACE;
+  }
+  return 0;
 }
 
 extern "C" int rpo_preprocess_batch(const uint8_t* src, int64_t src_bytes, const rpo_image_desc* desc_host,
                                     const rpo_image_desc* desc_dev, int B, int size, int max_rows, int kmax,
                                     const float* mean3, const float* std3, float* out, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-  if (!src || !desc_host || !desc_dev || !mean3 || !std3 || !out || !workspace || B <= 0 || size <= 0)
+  if (!src || !desc_host || !desc_dev || !mean3 || !std3 || !out || !workspace || B <= 0 || size <= 0 ||
+      max_rows <= 0 || kmax <= 0)
     return RPO_E_BADARG;
   const Layout L{B, size, max_rows, kmax};
   if (workspace_bytes < L.total()) return RPO_E_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) % 16) return RPO_E_ALIGN;
-  for (int b = 0; b < B; ++b) {        // the descriptors are the only untrusted input: validate on the host copy
-    const rpo_image_desc& d = desc_host[b];
-    if (d.width <= 0 || d.height <= 0 || d.crop_w <= 0 || d.crop_h <= 0 || d.crop_x < 0 || d.crop_y < 0 ||
-        d.crop_x + d.crop_w > d.width || d.crop_y + d.crop_h > d.height)
-      return RPO_E_SHAPE;
-    if (d.resize_w < size || d.resize_h < size || d.win_x < 0 || d.win_y < 0 || d.win_x + size > d.resize_w ||
-        d.win_y + size > d.resize_h)
-      return RPO_E_SHAPE;
-    if (d.src_offset < 0 || d.src_offset + (int64_t)d.width * d.height * 3 > src_bytes) return RPO_E_SHAPE;
-    if (rpo_preprocess_ksize(d.crop_w, d.resize_w) > kmax || rpo_preprocess_ksize(d.crop_h, d.resize_h) > kmax)
-      return RPO_E_WORKSPACE;
-    if (d.crop_h > max_rows) return RPO_E_WORKSPACE;
-  }
+  if (const int rc = rpo_preprocess_check(desc_host, B, size, max_rows, kmax, src_bytes)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(workspace);
   hipLaunchKernelGGL(coeff_kernel, dim3(B, 2), dim3(256), 0, s, desc_dev, ws, L);

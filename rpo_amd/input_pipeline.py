@@ -107,6 +107,26 @@ class SamplePlan:
     flip: bool
 
 
+_I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
+_DESC_I32_FIELDS = ("width", "height", "crop_x", "crop_y", "crop_w", "crop_h", "resize_w", "resize_h", "win_x", "win_y")
+
+
+def _fill_desc(d, b: int, src_offset: int, height: int, width: int, pl: SamplePlan) -> None:
+    """One `rpo_image_desc` from a plan.  ctypes stores a Python int into a `c_int32` field modulo 2^32 without a word,
+    and a wrapped crop can pass the library's validation as another, valid crop: a number that does not fit its field
+    is refused here, by name."""
+    top, left, ch, cw = pl.crop
+    vals = (width, height, left, top, cw, ch, pl.resize[0], pl.resize[1], pl.window[0], pl.window[1])
+    if max(vals) > _I32_MAX or min(vals) < _I32_MIN:
+        name, v = next((n, v) for n, v in zip(_DESC_I32_FIELDS, vals) if not _I32_MIN <= v <= _I32_MAX)
+        raise ValueError(f"image {b}: {name} = {v} does not fit the int32 field of rpo_image_desc")
+    if not 0 <= src_offset < 2 ** 63:
+        raise ValueError(f"image {b}: src_offset = {src_offset} does not fit the int64 field of rpo_image_desc")
+    d.src_offset = src_offset
+    (d.width, d.height, d.crop_x, d.crop_y, d.crop_w, d.crop_h, d.resize_w, d.resize_h, d.win_x, d.win_y) = vals
+    d.flip = int(pl.flip)
+
+
 class DeviceTransform:
     """Batch transform: host plans + one packed H2D copy + `rpo_preprocess_batch`.
 
@@ -163,15 +183,10 @@ class DeviceTransform:
             raise ValueError(f"batch of {B} images, transform built for 1..{self.max_batch}")
         if plans is None:
             plans = [self.plan(im.shape[0], im.shape[1]) for im in images]
-        slot = self.slots[self.turn]
-        self.turn ^= 1
-        if slot["done"] is not None:
-            slot["done"].synchronize()          # the device side of this slot is free again
-        host = slot["host"]
-        descs = (_lib.ImageDesc * B)()
+        descs = (_lib.ImageDesc * B)()          # the descriptors first: a bad image or plan raises with no slot touched
         off = self.desc_bytes
+        offs = []
         max_rows, kmax = 1, 1
-        hv = host.numpy()
         for b, (im, pl) in enumerate(zip(images, plans)):
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError("images must be uint8 arrays of shape [H, W, 3] (decoded RGB)")
@@ -179,18 +194,21 @@ class DeviceTransform:
             n = H * W * 3
             if off + n > self.cap:
                 raise ValueError("staging buffer too small: raise max_image_bytes")
-            hv[off:off + n] = np.ascontiguousarray(im).reshape(-1)
-            top, left, ch, cw = pl.crop
-            d = descs[b]
-            d.src_offset, d.width, d.height = off - self.desc_bytes, W, H
-            d.crop_x, d.crop_y, d.crop_w, d.crop_h = left, top, cw, ch
-            d.resize_w, d.resize_h = pl.resize
-            d.win_x, d.win_y = pl.window
-            d.flip = int(pl.flip)
+            _fill_desc(descs[b], b, off - self.desc_bytes, H, W, pl)
+            ch, cw = pl.crop[2], pl.crop[3]
             max_rows = max(max_rows, ch)
             kmax = max(kmax, self.lib.rpo_preprocess_ksize(cw, pl.resize[0]),
                        self.lib.rpo_preprocess_ksize(ch, pl.resize[1]))
+            offs.append(off)
             off += (n + 15) // 16 * 16
+        slot = self.slots[self.turn]
+        self.turn ^= 1
+        if slot["done"] is not None:
+            slot["done"].synchronize()          # the device side of this slot is free again
+        host = slot["host"]
+        hv = host.numpy()
+        for im, o in zip(images, offs):
+            hv[o:o + im.size] = np.ascontiguousarray(im).reshape(-1)
         ctypes.memmove(host.data_ptr(), descs, ctypes.sizeof(descs))
         need = self.lib.rpo_preprocess_workspace_bytes(B, S, max_rows, kmax)
         if slot["ws"] is None or slot["ws"].numel() < need:
@@ -228,15 +246,18 @@ class DeviceTransform:
             raise ValueError(f"batch of {B} images, transform built for 1..{self.max_batch}")
         if image_set.dev != self.dev:
             raise ValueError(f"the image set lives on {image_set.dev}, the transform on {self.dev}")
+        indices = [int(i) for i in indices]
+        if plans is None:
+            plans = [self.plan(*image_set.sizes[i]) for i in indices]
+        descs = (_lib.ImageDesc * B)()          # everything but src_offset: a bad plan raises with no buffer touched
+        for b, (i, pl) in enumerate(zip(indices, plans)):
+            _fill_desc(descs[b], b, 0, *image_set.sizes[i], pl)
         if getattr(self, "dslots", None) is None:
             self.dslots = [{"host": torch.empty(self.desc_bytes, dtype=torch.uint8).pin_memory(),
                             "dev": torch.empty(self.desc_bytes, dtype=torch.uint8, device=self.dev),
                             "ws": None, "done": None} for _ in range(2)]
             self.dturn = 0
             self._ksize_cache = {}
-        indices = [int(i) for i in indices]
-        if plans is None:
-            plans = [self.plan(*image_set.sizes[i]) for i in indices]
         slot = self.dslots[self.dturn]
         if slot["done"] is not None:
             slot["done"].synchronize()          # the descriptors of two calls ago have been read
@@ -244,17 +265,10 @@ class DeviceTransform:
         turn = self.dturn
         self.dturn ^= 1
         offsets = image_set.stage_spilled(indices, turn, stream)
-        descs = (_lib.ImageDesc * B)()
         max_rows, kmax = 1, 1
-        for b, (i, pl) in enumerate(zip(indices, plans)):
-            H, W = image_set.sizes[i]
-            top, left, ch, cw = pl.crop
-            d = descs[b]
-            d.src_offset, d.width, d.height = offsets[b], W, H
-            d.crop_x, d.crop_y, d.crop_w, d.crop_h = left, top, cw, ch
-            d.resize_w, d.resize_h = pl.resize
-            d.win_x, d.win_y = pl.window
-            d.flip = int(pl.flip)
+        for b, pl in enumerate(plans):
+            descs[b].src_offset = offsets[b]    # inside the set's buffer
+            ch, cw = pl.crop[2], pl.crop[3]
             max_rows = max(max_rows, ch)
             kmax = max(kmax, self._ksize(cw, pl.resize[0]), self._ksize(ch, pl.resize[1]))
         nbytes = ctypes.sizeof(descs)
