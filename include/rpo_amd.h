@@ -411,6 +411,26 @@ int rpo_text_attn_fwd_prefix(const void* q, const void* k, const void* v, int64_
                              int dtype, const int32_t* len, int n_img, int n_cls, int P, int S, int H,
                              float scale, void* stream);
 
+/* (ABI 8 addition) The backward of rpo_text_attn_fwd_prefix, for training on the shared layout (CoOp's and CoCoOp's learned
+ * context IS the prefix): autograd of the causal attention over the first len[c] positions of every sequence (b, c) --
+ * rpo_text_attn_bwd_dense's math, fp32 throughout -- on rpo_text_attn_fwd_prefix's rows.  q, k, v [rows, ld], d_out
+ * [rows, lddo] = dL/d(attention output), dq, dk, dv [rows, ldd]; len: int32 device array [n_cls], len[c] >= P + 1.
+ *   suffix row (b, c, s), P + s <  len[c]: dq, dk, dv of sequence (b, c) at position P + s
+ *   suffix row (b, c, s), P + s >= len[c]: exact zeros in all three (the dX GEMM reads every row)
+ *   prefix row (b, j): dq from the prefix's own P x P causal attention with the prefix rows' d_out; dk and dv = that self
+ *                      part + the sum over ALL n_cls classes of what their suffix queries contribute to key j
+ * so a prefix row's gradient is the sum of the gradients of its n_cls dense copies.  No atomics: workgroups write fp32
+ * partials per group of classes to `workspace` (at least rpo_text_attn_bwd_prefix_workspace_floats(n_img, n_cls, P, H)
+ * floats, no initialisation needed), a second launch adds them in ascending group order, then the self part, and rounds
+ * once.  The same bits on every call, and image b's bits are those of a launch over image b alone.
+ * P + S <= 80 (else RPO_E_SHAPE, as a launch grid over 2^31 - 1 workgroups); k, v, workspace and the rows of ld / lddo / ldd
+ * 16-byte aligned (RPO_E_ALIGN); f32, bf16 and f16 storage.  A refused call launches nothing. */
+int rpo_text_attn_bwd_prefix(const void* q, const void* k, const void* v, int64_t ld, const void* d_out, int64_t lddo,
+                             void* dq, void* dk, void* dv, int64_t ldd, int dtype, const int32_t* len, int n_img,
+                             int n_cls, int P, int S, int H, float scale, float* workspace, void* stream);
+/* (ABI 8 addition) fp32 elements of rpo_text_attn_bwd_prefix's workspace; 0 for non-positive arguments. */
+int64_t rpo_text_attn_bwd_prefix_workspace_floats(int n_img, int n_cls, int P, int H);
+
 /* CoCoOp's meta-net (trainers/cocoop.py:93-97, PromptLearner.forward :137-143): bias[b] = linear2(relu(linear1(f[b] /
  * |f[b]|))) for the B raw image features img_f [B, e]; w1 [h, e], b1 [h], w2 [d, h], b2 [d], all fp32.  f_norm [B, e] and
  * hidden [B, h] are kept for rpo_metanet_bwd, which turns d_bias [B, d] into the gradients of the four tensors (batch sum

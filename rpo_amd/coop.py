@@ -19,6 +19,11 @@ normalised image feature whose output shifts the context PER IMAGE, so every ima
 class: `Engine.cocoop_forward_backward` runs the class set once per image (B * n_cls virtual classes) through the same
 dense text path and trains ctx + the two meta-net layers (`CoCoOpCustomCLIP`, `CoCoOp` below).
 
+`shared_prefix=True` (all four classes below) trains on the shared-prefix row layout instead: the rows
+[SOS | ctx] read only themselves under the causal mask, so they are kept once per replica -- P + n_cls (Lmax - P) text rows
+instead of n_cls Lmax, forward and backward (`rpo_amd/engine_coop_prefix.py`, `rpo_text_attn_bwd_prefix`).  Generic context
+and class token at the end only; everything else (checkpoints included) is the same.  Off by default.
+
 The caller provides the token ids of the "X X .. name." prompts (the BPE tokenizer is out of scope).
 """
 from __future__ import annotations
@@ -34,6 +39,7 @@ from . import optim as _optim
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .engine import Engine, make_engine
+from .engine_coop import check_shared_prefix
 from .loop import LoopMixin
 from .trainer import OptimConfig, load_checkpoint_file, lr_at_epoch, write_checkpoint
 
@@ -95,16 +101,19 @@ class CoOpCustomCLIP:
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int,
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float16, max_batch: int = 32,
                  ctx: Optional[np.ndarray] = None, cfg: Optional[RPOConfig] = None, csc: bool = False,
-                 class_token_position: str = "end", ctx_init: Optional[np.ndarray] = None):
+                 class_token_position: str = "end", ctx_init: Optional[np.ndarray] = None,
+                 shared_prefix: bool = False):
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])     # one (unused) RPO prompt row per image
         self.cfg = cfg
-        self.engine = make_engine(cfg, state_dict, tokens, torch.device(device), act_dtype, max_batch)
         if ctx is None and ctx_init is not None:
             csc = False                      # CTX_INIT wins over CSC, as in the reference (trainers/coop.py:72-80 vs :84)
+        check_shared_prefix(shared_prefix, csc, class_token_position)        # refused before an engine is made
+        self.engine = make_engine(cfg, state_dict, tokens, torch.device(device), act_dtype, max_batch)
         with torch.cuda.device(self.engine.dev):
-            self.engine.coop_setup(n_ctx, csc=csc, class_token_position=class_token_position)
+            self.engine.coop_setup(n_ctx, csc=csc, class_token_position=class_token_position,
+                                   shared_prefix=shared_prefix)
             # (random: the reference's own draw from torch's global generator, so a seeded run starts from its vectors)
             ctx = _init_ctx(cfg, tokens.shape[0], n_ctx, csc, ctx, ctx_init, state_dict["token_embedding.weight"])
             self.engine.coop_ctx.copy_(torch.as_tensor(ctx).reshape(self.engine.coop_ctx.shape))
@@ -130,10 +139,11 @@ class CoOp(LoopMixin):
                  act_dtype: torch.dtype = torch.float16, batch_size: int = 32, num_batches: int = 1,
                  ctx: Optional[np.ndarray] = None, cfg: Optional[RPOConfig] = None, use_graph: bool = False,
                  csc: bool = False, class_token_position: str = "end", ctx_init: Optional[np.ndarray] = None,
-                 amp: bool = False):
+                 amp: bool = False, shared_prefix: bool = False):
         self.optim_cfg = optim or OptimConfig(lr=0.002, max_epoch=50)       # configs/trainers/CoOp/vit_b16_ep50.yaml
         self.model = CoOpCustomCLIP(state_dict, tokenized_prompts, n_ctx, device, act_dtype, batch_size, ctx, cfg,
-                                    csc=csc, class_token_position=class_token_position, ctx_init=ctx_init)
+                                    csc=csc, class_token_position=class_token_position, ctx_init=ctx_init,
+                                    shared_prefix=shared_prefix)
         self._init_common(batch_size, num_batches, use_graph, amp)
 
     def _init_common(self, batch_size: int, num_batches: int, use_graph: bool, amp: bool) -> None:
@@ -307,7 +317,7 @@ class CoCoOpCustomCLIP:
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, n_ctx: int,
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float16, max_batch: int = 1,
                  ctx: Optional[np.ndarray] = None, meta: Optional[Dict[str, np.ndarray]] = None,
-                 cfg: Optional[RPOConfig] = None, ctx_init: Optional[np.ndarray] = None):
+                 cfg: Optional[RPOConfig] = None, ctx_init: Optional[np.ndarray] = None, shared_prefix: bool = False):
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])
@@ -319,7 +329,7 @@ class CoCoOpCustomCLIP:
         e, dt = cfg.embed, cfg.d_t
         h = e // 16                                                          # vis_dim // 16 (:94)
         with torch.cuda.device(eng.dev):
-            eng.coop_setup(n_ctx, replicas=max_batch, meta_hidden=h)
+            eng.coop_setup(n_ctx, replicas=max_batch, meta_hidden=h, shared_prefix=shared_prefix)
             # the reference's draws, in its order: nn.init.normal_(ctx_vectors, std=0.02) (:83-84) or the CTX_INIT words
             # (:72-80, configs/trainers/CoCoOp/vit_b16_c4_ep10_batch1_ctxv1.yaml: "a photo of a") ...
             ctx = _init_ctx(cfg, tokens.shape[0], n_ctx, False, ctx, ctx_init, state_dict["token_embedding.weight"])
@@ -388,10 +398,10 @@ class CoCoOp(CoOp):
                  act_dtype: torch.dtype = torch.float16, batch_size: int = 1, num_batches: int = 1,
                  ctx: Optional[np.ndarray] = None, meta: Optional[Dict[str, np.ndarray]] = None,
                  cfg: Optional[RPOConfig] = None, use_graph: bool = False, ctx_init: Optional[np.ndarray] = None,
-                 amp: bool = False):
+                 amp: bool = False, shared_prefix: bool = False):
         self.optim_cfg = optim or OptimConfig(lr=0.002, max_epoch=10)    # configs/trainers/CoCoOp/vit_b16_c4_ep10_batch1.yaml
         self.model = CoCoOpCustomCLIP(state_dict, tokenized_prompts, n_ctx, device, act_dtype, batch_size, ctx, meta, cfg,
-                                      ctx_init=ctx_init)
+                                      ctx_init=ctx_init, shared_prefix=shared_prefix)
         self._init_common(batch_size, num_batches, use_graph, amp)
 
     def _forward_backward(self, image: torch.Tensor, label: torch.Tensor) -> None:

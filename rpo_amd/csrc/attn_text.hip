@@ -384,6 +384,212 @@ int launch_prefix(const void* q, const void* k, const void* v, int64_t ld, void*
   return rpo_launch_status();
 }
 
+// ---- backward with a per-image shared prefix (rpo_text_attn_bwd_prefix) ----------------------------------------------
+// The backward of text_attn_prefix_kernel's attention, for the trainers whose learned rows ARE the prefix (CoOp's context,
+// trainers/coop.py:117-134; CoCoOp's per image, trainers/cocoop.py:123-161): text_attn_bwd_dense_kernel's math on the row
+// layout above.  A suffix row is a query and a key of ONE sequence, so its dq / dk / dv are that sequence's; a prefix row is
+// a key of every class of its image, so its dk / dv are the prefix's own P x P causal part plus the sum over the classes of
+// what their suffix queries contribute -- summed HERE, in every block, which is what lets LayerNorm backward and the dX
+// GEMMs (linear in the incoming gradient) run on the one shared row too.
+// One workgroup per (image, head, slot).  Slots 0 .. groups - 1 walk `group` classes each: the image's P prefix K / V
+// head slices are staged once, then per class its S suffix rows' Q / K / V / dO; pass 1 (one wave per query row) and pass 2
+// (one wave per key) are the dense kernel's, with key j in the prefix arrays below P and in the class's own from there on.
+// What the class's queries give prefix key j is accumulated in LDS (Ak / Av [P][64]: element (j, lane) belongs to wave
+// j % 4 alone), classes in ascending order, rows in ascending order, and written as an fp32 partial to the workspace.  The
+// last slot (`groups`) is the prefix itself: the same routine on a sequence of no shared keys and P own rows, whose dq goes
+// to the prefix rows and whose dk / dv go to the workspace.  text_attn_bwd_prefix_reduce then adds, per prefix key, the
+// slots in ascending order (class groups, then the self part) and rounds once: no atomics, no arrival order -- the same
+// bits every time, and image b's bits do not depend on the other images of the launch (the grouping is a function of
+// n_cls and H alone).
+struct BwdPrefixLds {                          // floats from the start of the dynamic LDS
+  int kp, vp, ak, av, qs, ks, vs, ds, pm, sm, total;
+  __host__ __device__ BwdPrefixLds(int Pn, int Sn) {
+    kp = 0; vp = kp + Pn * 65; ak = vp + Pn * 65; av = ak + Pn * 64;
+    qs = av + Pn * 64; ks = qs + Sn * 65; vs = ks + Sn * 65; ds = vs + Sn * 65;
+    pm = ds + Sn * 65; sm = pm + Sn * (Pn + Sn + 1); total = sm + Sn * (Pn + Sn + 1);
+  }
+};
+
+// One sequence of Pn shared keys (already in Kp / Vp) and Sn own rows (global rows row0 .., positions Pn ..) of which the
+// first ns are real.  dq of the own rows is written (zeros from ns on); dk / dv of the own rows go to the outputs (zeros
+// from ns on) or, unscaled, to own_k / own_v [Sn][64] where those are given; the shared keys' share is added to Ak / Av.
+// Every thread of the workgroup calls it (barriers inside).
+template <typename T>
+__device__ __forceinline__ void bwd_prefix_sequence(const T* __restrict__ q, const T* __restrict__ k,
+                                                    const T* __restrict__ v, int64_t ld, const T* __restrict__ dout,
+                                                    int64_t lddo, T* dq, T* dk, T* dv, int64_t ldd, int64_t row0, int col0,
+                                                    int Pn, int Sn, int ns, float* lds, const BwdPrefixLds& o,
+                                                    float* own_k, float* own_v, float scale, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int Lt = Pn + Sn, LP = Lt + 1;
+  const float *Kp = lds + o.kp, *Vp = lds + o.vp;
+  float *Ak = lds + o.ak, *Av = lds + o.av, *Qs = lds + o.qs, *Ks = lds + o.ks, *Vs = lds + o.vs, *Ds = lds + o.ds;
+  float *Pm = lds + o.pm, *Sm = lds + o.sm;
+  stage_kv_rows<T>(k, v, ld, row0, ns, col0, Ks, Vs, tid);
+  for (int id = tid; id < Sn * 64; id += 256) {
+    const int s = id >> 6, d = id & 63;
+    const bool ok = s < ns;
+    Qs[s * 65 + d] = ok ? ActIO<T>::ld(q + (row0 + s) * ld + col0 + d) : 0.f;
+    Ds[s * 65 + d] = ok ? ActIO<T>::ld(dout + (row0 + s) * lddo + col0 + d) : 0.f;
+    if (!ok) { Ks[s * 65 + d] = 0.f; Vs[s * 65 + d] = 0.f; }
+  }
+  __syncthreads();
+  const int j0 = min(lane, Lt - 1), j1 = min(lane + 64, Lt - 1);
+  const float* k0 = j0 < Pn ? Kp + j0 * 65 : Ks + (j0 - Pn) * 65;
+  const float* k1 = j1 < Pn ? Kp + j1 * 65 : Ks + (j1 - Pn) * 65;
+  const float* v0 = j0 < Pn ? Vp + j0 * 65 : Vs + (j0 - Pn) * 65;
+  const float* v1 = j1 < Pn ? Vp + j1 * 65 : Vs + (j1 - Pn) * 65;
+  for (int s = wave; s < Sn; s += 4) {
+    T* dqr = dq + (row0 + s) * ldd + col0;
+    if (s >= ns) {                              // past the EOT: zero gradients (the dX GEMM reads every row)
+      ActIO<T>::st(dqr + lane, 0.f);
+      continue;
+    }
+    const int nk = Pn + s + 1;                  // causal, and s < ns: every key up to this row is a real token
+    const float qv = Qs[s * 65 + lane], dov = Ds[s * 65 + lane];
+    float s0 = 0.f, s1 = 0.f, dp0 = 0.f, dp1 = 0.f;
+#pragma unroll 8
+    for (int d = 0; d < 64; ++d) {
+      const float qd = bcast(qv, d), dd = bcast(dov, d);
+      s0 = fmaf(qd, k0[d], s0);
+      s1 = fmaf(qd, k1[d], s1);
+      dp0 = fmaf(dd, v0[d], dp0);
+      dp1 = fmaf(dd, v1[d], dp1);
+    }
+    s0 = lane < nk ? s0 * scale : -INFINITY;
+    s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
+    const float m = wave_max(fmaxf(s0, s1));
+    float p0 = expf(s0 - m), p1 = expf(s1 - m);
+    const float inv = 1.0f / wave_sum(p0 + p1);
+    p0 *= inv; p1 *= inv;
+    dp0 = lane < nk ? dp0 : 0.f;
+    dp1 = lane + 64 < nk ? dp1 : 0.f;
+    const float delta = wave_sum(p0 * dp0 + p1 * dp1);
+    const float ds0 = p0 * (dp0 - delta), ds1 = p1 * (dp1 - delta);
+    if (lane < Lt) { Pm[s * LP + lane] = p0; Sm[s * LP + lane] = ds0; }
+    if (lane + 64 < Lt) { Pm[s * LP + lane + 64] = p1; Sm[s * LP + lane + 64] = ds1; }
+    float acc = 0.f;
+    for (int j = 0; j < Pn; ++j) {
+      const float dj = j < 64 ? bcast(ds0, j) : bcast(ds1, j - 64);
+      acc = fmaf(dj, Kp[j * 65 + lane], acc);
+    }
+    for (int j = Pn; j < nk; ++j) {
+      const float dj = j < 64 ? bcast(ds0, j) : bcast(ds1, j - 64);
+      acc = fmaf(dj, Ks[(j - Pn) * 65 + lane], acc);
+    }
+    ActIO<T>::st(dqr + lane, acc * scale);
+  }
+  __syncthreads();
+  for (int t = wave; t < Sn; t += 4) {          // the sequence's own keys: read by its rows t .. ns - 1
+    float ak = 0.f, av = 0.f;
+    for (int s = t; s < ns; ++s) {              // (empty past the EOT: zeros)
+      ak = fmaf(Sm[s * LP + Pn + t], Qs[s * 65 + lane], ak);
+      av = fmaf(Pm[s * LP + Pn + t], Ds[s * 65 + lane], av);
+    }
+    if (own_k) {
+      own_k[t * 64 + lane] = ak;
+      own_v[t * 64 + lane] = av;
+    } else {
+      ActIO<T>::st(dk + (row0 + t) * ldd + col0 + lane, ak * scale);
+      ActIO<T>::st(dv + (row0 + t) * ldd + col0 + lane, av);
+    }
+  }
+  for (int j = wave; j < Pn; j += 4) {          // the shared keys: read by every real row of the sequence
+    float ak = Ak[j * 64 + lane], av = Av[j * 64 + lane];
+    for (int s = 0; s < ns; ++s) {
+      ak = fmaf(Sm[s * LP + j], Qs[s * 65 + lane], ak);
+      av = fmaf(Pm[s * LP + j], Ds[s * 65 + lane], av);
+    }
+    Ak[j * 64 + lane] = ak;
+    Av[j * 64 + lane] = av;
+  }
+  __syncthreads();                              // the next sequence re-stages the own rows
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void text_attn_bwd_prefix_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                   const T* __restrict__ v, int64_t ld,
+                                                                   const T* __restrict__ dout, int64_t lddo, T* dq, T* dk,
+                                                                   T* dv, int64_t ldd, const int32_t* __restrict__ len,
+                                                                   int n_img, int n_cls, int P, int S, int H, int group,
+                                                                   int groups, float scale, float* __restrict__ ws) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* lds = reinterpret_cast<float*>(smem);
+  const int tid = threadIdx.x;
+  const int slots = groups + 1;
+  const int h = blockIdx.x % H, bg = blockIdx.x / H;
+  const int g = bg % slots, b = bg / slots;
+  const int col0 = h * 64;
+  float* part = ws + (((int64_t)b * H + h) * slots + g) * 2 * P * 64;      // this slot's [dk | dv][P][64] partial
+  if (g == groups) {                            // the prefix's own P x P causal attention
+    const BwdPrefixLds o(0, P);
+    bwd_prefix_sequence<T>(q, k, v, ld, dout, lddo, dq, dk, dv, ldd, (int64_t)b * P, col0, 0, P, P, lds, o, part,
+                           part + P * 64, scale, tid);
+    return;
+  }
+  const BwdPrefixLds o(P, S);
+  stage_kv_rows<T>(k, v, ld, (int64_t)b * P, P, col0, lds + o.kp, lds + o.vp, tid);
+  for (int id = tid; id < 2 * P * 64; id += 256) lds[o.ak + id] = 0.f;      // Ak and Av are adjacent
+  // (the first barrier inside bwd_prefix_sequence orders these writes before any read)
+  const int c_end = min(n_cls, (g + 1) * group);
+  const int64_t suf0 = (int64_t)n_img * P;      // first suffix row
+  for (int c = g * group; c < c_end; ++c) {
+    const int ns = max(0, min(len[c], P + S) - P);
+    bwd_prefix_sequence<T>(q, k, v, ld, dout, lddo, dq, dk, dv, ldd, suf0 + ((int64_t)b * n_cls + c) * S, col0, P, S, ns,
+                           lds, o, nullptr, nullptr, scale, tid);
+  }
+  for (int id = tid; id < 2 * P * 64; id += 256) part[id] = lds[o.ak + id];
+}
+
+template <typename T>
+__global__ __launch_bounds__(128) void text_attn_bwd_prefix_reduce(const float* __restrict__ ws, T* dk, T* dv, int64_t ldd,
+                                                                   int P, int H, int slots, float scale) {
+  const int j = blockIdx.x % P, bh = blockIdx.x / P;
+  const int h = bh % H, b = bh / H;
+  const int which = threadIdx.x >> 6, lane = threadIdx.x & 63;      // wave 0: dk, wave 1: dv
+  const float* src = ws + ((int64_t)bh * slots * 2 + which) * P * 64 + j * 64 + lane;
+  float acc = 0.f;
+  for (int g = 0; g < slots; ++g) acc += src[(int64_t)g * 2 * P * 64];   // class groups in order, the self part last
+  const int64_t off = ((int64_t)b * P + j) * ldd + h * 64 + lane;
+  if (which) ActIO<T>::st(dv + off, acc);
+  else ActIO<T>::st(dk + off, acc * scale);
+}
+
+// classes per workgroup: 1 until the (class, head) pairs alone exceed ~1024 workgroups per image (four per CU), then as
+// many as keep it there, at most 16 -- a class is S rows of ~1.5 k dependent VALU instructions each, so below that count
+// more workgroups shorten the launch and above it a larger group shrinks the workspace.  A function of n_cls and H only.
+static inline int bwd_prefix_group(int n_cls, int H) {
+  const int64_t g = ((int64_t)n_cls * H + 1023) / 1024;
+  return g < 1 ? 1 : g > 16 ? 16 : (int)g;
+}
+static inline int bwd_prefix_groups(int n_cls, int H) {
+  const int group = bwd_prefix_group(n_cls, H);
+  return (n_cls + group - 1) / group;
+}
+static inline int bwd_prefix_lds_floats(int P, int S) {
+  const int a = BwdPrefixLds(P, S).total, b = BwdPrefixLds(0, P).total;
+  return a > b ? a : b;
+}
+
+template <typename T>
+int launch_bwd_prefix(const void* q, const void* k, const void* v, int64_t ld, const void* dout, int64_t lddo, void* dq,
+                      void* dk, void* dv, int64_t ldd, const int32_t* len, int n_img, int n_cls, int P, int S, int H,
+                      float scale, float* ws, hipStream_t s) {
+  static rpo_lds_mask_t lds_ok{0};
+  auto kern = text_attn_bwd_prefix_kernel<T>;
+  const int group = bwd_prefix_group(n_cls, H), groups = bwd_prefix_groups(n_cls, H);
+  // the most any P + S <= 80 needs is 33 596 floats (P = 1, S = 79)
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), 136 * 1024, &lds_ok)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)n_img * (groups + 1) * H)), dim3(256), bwd_prefix_lds_floats(P, S) * 4,
+                     s, static_cast<const T*>(q), static_cast<const T*>(k), static_cast<const T*>(v), ld,
+                     static_cast<const T*>(dout), lddo, static_cast<T*>(dq), static_cast<T*>(dk), static_cast<T*>(dv), ldd,
+                     len, n_img, n_cls, P, S, H, group, groups, scale, ws);
+  if (int rc = rpo_launch_status()) return rc;
+  hipLaunchKernelGGL(text_attn_bwd_prefix_reduce<T>, dim3((unsigned)((int64_t)n_img * H * P)), dim3(128), 0, s, ws,
+                     static_cast<T*>(dk), static_cast<T*>(dv), ldd, P, H, groups + 1, scale);
+  return rpo_launch_status();
+}
+
 }  // namespace
 
 // n_kv < n_cls: the n_cls classes are VIRTUAL -- class v reads len[v % n_kv] and the cache rows of class v % n_kv
@@ -494,4 +700,32 @@ extern "C" int rpo_text_attn_fwd_prefix(const void* q, const void* k, const void
   if (dtype == RPO_F16) return launch_prefix<f16_t>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
   if (dtype == RPO_BF16) return launch_prefix<bf16_t>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
   return launch_prefix<float>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
+}
+
+extern "C" int64_t rpo_text_attn_bwd_prefix_workspace_floats(int n_img, int n_cls, int P, int H) {
+  if (n_img < 1 || n_cls < 1 || P < 1 || H < 1) return 0;
+  return (int64_t)n_img * H * (bwd_prefix_groups(n_cls, H) + 1) * 2 * P * 64;
+}
+
+extern "C" int rpo_text_attn_bwd_prefix(const void* q, const void* k, const void* v, int64_t ld, const void* d_out,
+                                        int64_t lddo, void* dq, void* dk, void* dv, int64_t ldd, int dtype,
+                                        const int32_t* len, int n_img, int n_cls, int P, int S, int H, float scale,
+                                        float* workspace, void* stream) {
+  if (!q || !k || !v || !d_out || !dq || !dk || !dv || !len || !workspace || n_img < 1 || n_cls < 1 || P < 1 || S < 1 ||
+      H < 1)
+    return RPO_E_BADARG;
+  if ((int64_t)P + S > 80) return RPO_E_SHAPE;
+  const int64_t wgs = (int64_t)n_img * (bwd_prefix_groups(n_cls, H) + 1) * H, wgs_reduce = (int64_t)n_img * H * P;
+  if (wgs > 2147483647ll || wgs_reduce > 2147483647ll) return RPO_E_SHAPE;
+  if (dtype != RPO_F32 && dtype != RPO_BF16 && dtype != RPO_F16) return RPO_E_DTYPE;
+  const int esz = dtype == RPO_F32 ? 4 : 2;
+  if (!aligned16(k) || !aligned16(v) || !aligned16(workspace) || (ld * esz) % 16 != 0 || (lddo * esz) % 16 != 0 ||
+      (ldd * esz) % 16 != 0)
+    return RPO_E_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == RPO_F16)
+    return launch_bwd_prefix<f16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale, workspace, s);
+  if (dtype == RPO_BF16)
+    return launch_bwd_prefix<bf16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale, workspace, s);
+  return launch_bwd_prefix<float>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale, workspace, s);
 }

@@ -45,6 +45,26 @@ def coop_layout_of(lengths, n_ctx: int, class_token_position: str = "end", L: Op
     return src, ctx_pos
 
 
+def shared_rows(replicas: int, n_cls: int, Lmax: int, n_ctx: int) -> int:
+    """Rows of the shared-prefix layout (engine_coop_prefix.py): per replica the P = 1 + n_ctx rows [SOS | ctx] once, then
+    the S = Lmax - P later positions of every class -- against the dense replicas * n_cls * Lmax."""
+    P = 1 + n_ctx
+    return replicas * (P + n_cls * (Lmax - P))
+
+
+def check_shared_prefix(shared_prefix: bool, csc: bool, class_token_position: str) -> None:
+    """What `shared_prefix=True` cannot serve, said before any device work: the rows in front of the class name are shared
+    only where they are the same for every class and come first."""
+    if not shared_prefix:
+        return
+    if csc:
+        raise ValueError("shared_prefix=True needs a generic context: with csc=True every class has its own context "
+                         "vectors, so no row is shared between the classes")
+    if class_token_position != "end":
+        raise ValueError(f"shared_prefix=True needs class_token_position='end' (got {class_token_position!r}): only there "
+                         "do the context rows come before every class-name token")
+
+
 class CoopEngineMixin:
     # ------------------------------------------------------------------ CoOp / CoCoOp: training context vectors
     def coop_layout(self, n_ctx: int, class_token_position: str = "end"):
@@ -57,20 +77,24 @@ class CoopEngineMixin:
         return coop_layout_of(self.len_np, n_ctx, class_token_position, self.Lmax)
 
     def coop_setup(self, n_ctx: int, replicas: int = 1, meta_hidden: int = 0, csc: bool = False,
-                   class_token_position: str = "end") -> None:
+                   class_token_position: str = "end", shared_prefix: bool = False) -> None:
         """Buffers of the sibling trainers CoOp (trainers/coop.py) and CoCoOp (trainers/cocoop.py): the learned context
         `coop_ctx` [n_ctx, d_t] and, per text block, everything the DENSE text-tower backward re-reads -- the gradient of a
         context vector flows through every token of every class (plain causal mask), unlike RPO's prompts.
         `replicas` > 1 (CoCoOp): the class set is run once per IMAGE with that image's shifted context, i.e. as
         replicas * n_cls virtual classes; `meta_hidden` > 0 adds the meta-net (linear1 [h, e], linear2 [d_t, h]).  All
         trained tensors live in one flat fp32 buffer (`coop_params` = [ctx | w1 | b1 | w2 | b2]) with matching gradient
-        and momentum buffers: one SGD launch.  n_cls * Lmax rows per replica (a few hundred), so this is small."""
+        and momentum buffers: one SGD launch.  n_cls * Lmax rows per replica (a few hundred), so this is small.
+        `shared_prefix`: the rows [SOS | ctx] every class of a replica shares are kept once (engine_coop_prefix.py):
+        P + n_cls * (Lmax - P) rows per replica, P = 1 + n_ctx; the dense buffers are not allocated."""
+        check_shared_prefix(shared_prefix, csc, class_token_position)
         cfg, dev, act = self.cfg, self.dev, self.act
         n, L, dt, e = cfg.n_cls, self.Lmax, cfg.d_t, cfg.embed
         assert 1 + n_ctx < self.Lmax and self.Lmax <= 80, "tokens must be the ids of the 'X X .. name.' prompts"
         assert 1 <= replicas <= self.max_batch
         nv = replicas * n
-        Rf = nv * L
+        self.coop_shared = bool(shared_prefix)
+        Rf = shared_rows(replicas, n, L, n_ctx) if shared_prefix else nv * L
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         a = lambda *s: torch.empty(*s, dtype=act, device=dev)
         au = f32 if act == torch.float32 else a
@@ -114,14 +138,17 @@ class CoopEngineMixin:
         self.c_dxc, self.c_da = a(Rf, dt), a(Rf, dt)
         self.c_du, self.c_dqkv = a(Rf, 4 * dt), a(Rf, 3 * dt)
         self.c_dy = f32(max(SPLIT_FC, SPLIT_Q), Rf, dt)
-        self.c_eot = torch.arange(nv, device=dev) * L + (self.c_len.to(torch.int64) - 1)          # EOT row of every class
+        if shared_prefix:
+            self._coop_prefix_setup(n_ctx, replicas)
+        else:
+            self.c_eot = torch.arange(nv, device=dev) * L + (self.c_len.to(torch.int64) - 1)      # EOT row of every class
         self.c_x_eot, self.c_dx_eot, self.c_dy_eot = f32(nv, dt), f32(nv, dt), f32(nv, dt)
         self.c_y_eot = a(nv, dt)
         self.c_text_f, self.c_d_text_f = f32(nv, e), f32(nv, e)
         self.c_d_text_f_a = a(nv, e)
         self.c_d_img_f = f32(self.max_batch, e)
         self.c_loss_b = f32(self.max_batch)
-        self.c_ctx_rows = f32(nv * n_ctx, dt)
+        self.c_ctx_rows = None if shared_prefix else f32(nv * n_ctx, dt)
         if self.img_cls_f is None:
             self.img_cls_f = torch.empty(self.max_batch, e, dtype=torch.float32, device=dev)
         # dX of the packed in-projection needs the whole W_in transposed ([d, 3d]); RPO's backward only its q third
@@ -131,6 +158,8 @@ class CoopEngineMixin:
         """TextEncoder.forward of trainers/coop.py:47-58 on prompts = [SOS | ctx | class name . EOT] (:117-134): all
         tokens up to the longest EOT, plain causal mask, every block's inputs kept for the backward.  R replicas of the
         class set, replica r carrying the context c_shift[r] (CoOp: one replica, the context itself)."""
+        if self.coop_shared:
+            return self._coop_prefix_forward(train, R)
         cfg = self.cfg
         n, L, dt, H, nc = cfg.n_cls, self.Lmax, cfg.d_t, cfg.heads_t, self.coop_n_ctx
         nv = R * n
@@ -168,6 +197,8 @@ class CoopEngineMixin:
         """c_dshift[r] = d loss / d (context of replica r): autograd of the whole text tower for all tokens (dX GEMMs only
         -- the weights are frozen), the causal attention backward with dK / dV (rpo_text_attn_bwd_dense), then the rows of
         the context positions summed over the classes (ctx.unsqueeze(0).expand, trainers/coop.py:119-121)."""
+        if self.coop_shared:
+            return self._coop_prefix_backward(R)
         cfg = self.cfg
         n, L, dt, H, nc = cfg.n_cls, self.Lmax, cfg.d_t, cfg.heads_t, self.coop_n_ctx
         nv = R * n

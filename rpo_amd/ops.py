@@ -536,6 +536,31 @@ def text_attn_fwd_prefix(q, k, v, out, len_i32, n_img: int, n_cls: int, P: int, 
     return out
 
 
+def text_attn_bwd_prefix_workspace_floats(n_img: int, n_cls: int, P: int, H: int) -> int:
+    return int(_lib.load().rpo_text_attn_bwd_prefix_workspace_floats(n_img, n_cls, P, H))
+
+
+def text_attn_bwd_prefix(q, k, v, d_out, dq, dk, dv, len_i32, n_img: int, n_cls: int, P: int, S: int, H: int,
+                         scale: float = 0.125, workspace=None):
+    """dq, dk, dv of `text_attn_fwd_prefix`'s attention on its row layout, the prefix rows' dk / dv summed over the classes
+    (include/rpo_amd.h: rpo_text_attn_bwd_prefix).  `workspace`: fp32, text_attn_bwd_prefix_workspace_floats(...) elements
+    (allocated here when not given)."""
+    rows = n_img * P + n_img * n_cls * S
+    assert _ld(q) == _ld(k) == _ld(v) and _ld(dq) == _ld(dk) == _ld(dv) and len_i32.dtype == torch.int32
+    assert len_i32.numel() >= n_cls and q.dtype == k.dtype == v.dtype == d_out.dtype == dq.dtype == dk.dtype == dv.dtype
+    assert min(t.shape[0] for t in (q, k, v, d_out, dq, dk, dv)) >= rows
+    assert min(t.shape[1] for t in (q, k, v, d_out, dq, dk, dv)) >= H * 64
+    need = text_attn_bwd_prefix_workspace_floats(n_img, n_cls, P, H)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= need
+    check(_lib.load().rpo_text_attn_bwd_prefix(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ld(q), d_out.data_ptr(),
+                                               _ld(d_out), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _ld(dq),
+                                               dtype_code(q.dtype), len_i32.data_ptr(), n_img, n_cls, P, S, H, scale,
+                                               workspace.data_ptr(), _stream()), "rpo_text_attn_bwd_prefix")
+    return dq
+
+
 def text_attn_bwd_shared(q, kc, vc, da, dq, len_i32, n_cls: int, n_kv: int, rows: int, Lmax: int, H: int, scale: float = 0.125):
     """`text_attn_bwd` for n_cls virtual classes on the cache of n_kv real ones (rpo_text_attn_bwd_shared)."""
     assert _ld(kc) == _ld(vc) and len_i32.dtype == torch.int32 and len_i32.numel() >= n_kv
