@@ -17,6 +17,65 @@ __device__ __forceinline__ float bcast(float v, int lane_uniform) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_uniform));
 }
 
+// ---- one query row of a wave ------------------------------------------------------------------------------------------
+// The lane holds keys `lane` and `lane + 64` (at most 128 keys): k0 / k1 point at their fp32 rows in LDS.
+__device__ __forceinline__ void row_dots(float av, const float* k0, const float* k1, float& s0, float& s1) {
+  s0 = 0.f; s1 = 0.f;
+#pragma unroll 8
+  for (int d = 0; d < 64; ++d) {
+    const float ad = bcast(av, d);
+    s0 = fmaf(ad, k0[d], s0);
+    s1 = fmaf(ad, k1[d], s1);
+  }
+}
+
+// raw scores of keys lane / lane + 64 -> softmax probabilities over the keys [0, nk)
+__device__ __forceinline__ void row_softmax(float& s0, float& s1, int nk, float scale, int lane) {
+  s0 = lane < nk ? s0 * scale : -INFINITY;
+  s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
+  const float m = wave_max(fmaxf(s0, s1));
+  s0 = expf(s0 - m); s1 = expf(s1 - m);
+  const float inv = 1.0f / wave_sum(s0 + s1);
+  s0 *= inv; s1 *= inv;
+}
+
+// dp_j = <dO, v_j> of keys lane / lane + 64 -> ds_j = p_j (dp_j - sum_j p_j dp_j)
+__device__ __forceinline__ void row_ds(float p0, float p1, float& dp0, float& dp1, int nk, int lane) {
+  dp0 = lane < nk ? dp0 : 0.f;
+  dp1 = lane + 64 < nk ? dp1 : 0.f;
+  // an explicit fma: which of the two products `p0 * dp0 + p1 * dp1` contracts into one is the compiler's choice and
+  // changes with the code around it; this is the rounding every caller has always had
+  const float delta = wave_sum(fmaf(p0, dp0, p1 * dp1));
+  dp0 = p0 * (dp0 - delta); dp1 = p1 * (dp1 - delta);
+}
+
+// acc + sum over keys j in [j_lo, j_hi), ascending, of w_j * rows[j - j_base][lane] (lane = feature; w0 / w1 hold w_j of
+// keys lane / lane + 64)
+__device__ __forceinline__ float row_accumulate(float acc, float w0, float w1, int j_lo, int j_hi, const float* rows,
+                                                int j_base, int lane) {
+  for (int j = j_lo; j < j_hi; ++j) {
+    const float wj = j < 64 ? bcast(w0, j) : bcast(w1, j - 64);
+    acc = fmaf(wj, rows[(j - j_base) * 65 + lane], acc);
+  }
+  return acc;
+}
+
+// one 16-byte chunk of T (8 or 4 elements) -> fp32 at dst
+template <typename T>
+__device__ __forceinline__ void unpack_chunk(const uint4& c, float* dst) {
+  const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+  if constexpr (sizeof(T) == 2) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      dst[2 * e] = unpack1<T>((uint16_t)(w[e] & 0xffffu));
+      dst[2 * e + 1] = unpack1<T>((uint16_t)(w[e] >> 16));
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dst[e] = __uint_as_float(w[e]);
+  }
+}
+
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void text_attn_kernel(const T* __restrict__ q, int64_t ldq,
                                                         const T* __restrict__ kc, const T* __restrict__ vc,
@@ -51,20 +110,8 @@ __global__ __launch_bounds__(256) void text_attn_kernel(const T* __restrict__ q,
     const int id = tid + it * 256;
     const int j = id / CPR, cch = id % CPR;
     if (j < L) {
-      float* kd = Kf + j * 65 + cch * EPC;
-      float* vd = Vf + j * 65 + cch * EPC;
-      const uint32_t kw[4] = {kv[it].x, kv[it].y, kv[it].z, kv[it].w};
-      const uint32_t vw[4] = {vv[it].x, vv[it].y, vv[it].z, vv[it].w};
-      if constexpr (sizeof(T) == 2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          kd[2 * e] = unpack1<T>((uint16_t)(kw[e] & 0xffffu)); kd[2 * e + 1] = unpack1<T>((uint16_t)(kw[e] >> 16));
-          vd[2 * e] = unpack1<T>((uint16_t)(vw[e] & 0xffffu)); vd[2 * e + 1] = unpack1<T>((uint16_t)(vw[e] >> 16));
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { kd[e] = __uint_as_float(kw[e]); vd[e] = __uint_as_float(vw[e]); }
-      }
+      unpack_chunk<T>(kv[it], Kf + j * 65 + cch * EPC);
+      unpack_chunk<T>(vv[it], Vf + j * 65 + cch * EPC);
     }
   }
   __syncthreads();
@@ -74,60 +121,111 @@ __global__ __launch_bounds__(256) void text_attn_kernel(const T* __restrict__ q,
   for (int r = blockIdx.y * 4 + wave; r < rows; r += 4 * gridDim.y) {
     const int64_t row = (int64_t)c * rows + r;
     const int nk = causal ? min(r + 1, L) : L;
-    const float qv = ActIO<T>::ld(q + row * ldq + h * 64 + lane);
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll 8
-    for (int d = 0; d < 64; ++d) {
-      const float qd = bcast(qv, d);
-      s0 = fmaf(qd, Kf[j0 * 65 + d], s0);
-      s1 = fmaf(qd, Kf[j1 * 65 + d], s1);
-    }
-    s0 = lane < nk ? s0 * scale : -INFINITY;
-    s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
-    const float m = wave_max(fmaxf(s0, s1));
-    float p0 = expf(s0 - m), p1 = expf(s1 - m);
-    const float inv = 1.0f / wave_sum(p0 + p1);
-    p0 *= inv; p1 *= inv;
+    float p0, p1;
+    row_dots(ActIO<T>::ld(q + row * ldq + h * 64 + lane), Kf + j0 * 65, Kf + j1 * 65, p0, p1);
+    row_softmax(p0, p1, nk, scale, lane);
     if (!BWD) {
-      float acc = 0.f;
-      for (int j = 0; j < nk; ++j) {
-        const float pj = j < 64 ? bcast(p0, j) : bcast(p1, j - 64);
-        acc = fmaf(pj, Vf[j * 65 + lane], acc);
-      }
-      ActIO<T>::st(out + row * ldo + h * 64 + lane, acc);
+      ActIO<T>::st(out + row * ldo + h * 64 + lane, row_accumulate(0.f, p0, p1, 0, nk, Vf, 0, lane));
     } else {
-      const float dv = ActIO<T>::ld(da + row * ldda + h * 64 + lane);
-      float dp0 = 0.f, dp1 = 0.f;
-#pragma unroll 8
-      for (int d = 0; d < 64; ++d) {
-        const float dd = bcast(dv, d);
-        dp0 = fmaf(dd, Vf[j0 * 65 + d], dp0);
-        dp1 = fmaf(dd, Vf[j1 * 65 + d], dp1);
-      }
-      dp0 = lane < nk ? dp0 : 0.f;
-      dp1 = lane + 64 < nk ? dp1 : 0.f;
-      const float delta = wave_sum(p0 * dp0 + p1 * dp1);
-      const float ds0 = p0 * (dp0 - delta), ds1 = p1 * (dp1 - delta);
-      float acc = 0.f;
-      for (int j = 0; j < nk; ++j) {
-        const float dj = j < 64 ? bcast(ds0, j) : bcast(ds1, j - 64);
-        acc = fmaf(dj, Kf[j * 65 + lane], acc);
-      }
-      ActIO<T>::st(out + row * ldo + h * 64 + lane, acc * scale);
+      float ds0, ds1;
+      row_dots(ActIO<T>::ld(da + row * ldda + h * 64 + lane), Vf + j0 * 65, Vf + j1 * 65, ds0, ds1);
+      row_ds(p0, p1, ds0, ds1, nk, lane);
+      ActIO<T>::st(out + row * ldo + h * 64 + lane, row_accumulate(0.f, ds0, ds1, 0, nk, Kf, 0, lane) * scale);
     }
   }
 }
 
-// ---- dense backward (all rows, dQ / dK / dV) -------------------------------------------------------------------------
+// ---- backward of one causal sequence (dQ / dK / dV of all its rows) ---------------------------------------------------
 // The sibling trainers train parameters that sit IN FRONT of the class name (CoOp's context vectors, trainers/coop.py:
 // 117-134), so their gradient flows through every token of the text tower under the plain causal mask
 // (clip/model.py:332-338): autograd of nn.MultiheadAttention for q, k, v of ALL L = len[c] rows of a class.  Rows past
 // the EOT token (>= len[c]) cannot reach the text feature (it is read at the EOT row, which sees columns <= itself) and
-// get zero gradients.  One workgroup per (class, head); L <= 80 (CLIP's context is 77), head_dim 64 = one wave:
+// get zero gradients.  L <= 80 (CLIP's context is 77), head_dim 64 = one wave:
 //   pass 1, one wave per query row r:   p = softmax(scale q_r K^T) over keys j <= r;  dp_j = <dO_r, v_j>;
 //           ds_j = p_j (dp_j - sum_j p_j dp_j);   dq_r = scale sum_j ds_j k_j;   P[r][:], DS[r][:] parked in LDS
 //   pass 2, one wave per key j:         dk_j = scale sum_{r >= j} DS[r][j] q_r;   dv_j = sum_{r >= j} P[r][j] dO_r
 // fp32 arithmetic throughout, fixed summation orders (bit-reproducible).
+// A sequence is Pn keys it shares with others (K / V only, rpo_text_attn_bwd_prefix below) followed by Sn rows of its own
+// (Q / K / V / dO); Pn = 0, Sn = Lmax is the dense layout of rpo_text_attn_bwd_dense.
+struct BwdPrefixLds {                          // floats from the start of the dynamic LDS
+  int kp, vp, ak, av, qs, ks, vs, ds, pm, sm, total;
+  __host__ __device__ BwdPrefixLds(int Pn, int Sn) {
+    kp = 0; vp = kp + Pn * 65; ak = vp + Pn * 65; av = ak + Pn * 64;
+    qs = av + Pn * 64; ks = qs + Sn * 65; vs = ks + Sn * 65; ds = vs + Sn * 65;
+    pm = ds + Sn * 65; sm = pm + Sn * (Pn + Sn + 1); total = sm + Sn * (Pn + Sn + 1);
+  }
+};
+
+// The two passes over a staged sequence: Pn shared keys in Kp / Vp and Sn own rows (global rows row0 .., positions Pn ..)
+// in Qs / Ks / Vs / Ds, of which the first ns are real and the others zero.  dq of the own rows is written (zeros from ns
+// on); dk / dv of the own rows go to the outputs (zeros from ns on) or, unscaled, to own_k / own_v [Sn][64] where those are
+// given; the shared keys' share is added to Ak / Av.  Every thread of the workgroup calls it after the barrier that ends
+// the staging (one barrier inside).
+template <typename T>
+__device__ __forceinline__ void bwd_sequence_compute(T* dq, T* dk, T* dv, int64_t ldd, int64_t row0, int col0, int Pn,
+                                                     int Sn, int ns, float* lds, const BwdPrefixLds& o, float* own_k,
+                                                     float* own_v, float scale, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int Lt = Pn + Sn, LP = Lt + 1;
+  const float *Kp = lds + o.kp, *Vp = lds + o.vp, *Qs = lds + o.qs, *Ks = lds + o.ks, *Vs = lds + o.vs, *Ds = lds + o.ds;
+  float *Ak = lds + o.ak, *Av = lds + o.av, *Pm = lds + o.pm, *Sm = lds + o.sm;
+  const int j0 = min(lane, Lt - 1), j1 = min(lane + 64, Lt - 1);
+  const float* k0 = j0 < Pn ? Kp + j0 * 65 : Ks + (j0 - Pn) * 65;
+  const float* k1 = j1 < Pn ? Kp + j1 * 65 : Ks + (j1 - Pn) * 65;
+  const float* v0 = j0 < Pn ? Vp + j0 * 65 : Vs + (j0 - Pn) * 65;
+  const float* v1 = j1 < Pn ? Vp + j1 * 65 : Vs + (j1 - Pn) * 65;
+  for (int s = wave; s < Sn; s += 4) {
+    T* dqr = dq + (row0 + s) * ldd + col0;
+    if (s >= ns) {                              // past the EOT: zero gradients (the dX GEMM reads every row)
+      ActIO<T>::st(dqr + lane, 0.f);
+      continue;
+    }
+    const int nk = Pn + s + 1;                  // causal, and s < ns: every key up to this row is a real token
+    const float qv = Qs[s * 65 + lane], dov = Ds[s * 65 + lane];
+    float p0 = 0.f, p1 = 0.f, ds0 = 0.f, ds1 = 0.f;
+#pragma unroll 8
+    for (int d = 0; d < 64; ++d) {              // row_dots of the scores and of dp in one loop
+      const float qd = bcast(qv, d), dd = bcast(dov, d);
+      p0 = fmaf(qd, k0[d], p0);
+      p1 = fmaf(qd, k1[d], p1);
+      ds0 = fmaf(dd, v0[d], ds0);
+      ds1 = fmaf(dd, v1[d], ds1);
+    }
+    row_softmax(p0, p1, nk, scale, lane);
+    row_ds(p0, p1, ds0, ds1, nk, lane);
+    if (lane < Lt) { Pm[s * LP + lane] = p0; Sm[s * LP + lane] = ds0; }
+    if (lane + 64 < Lt) { Pm[s * LP + lane + 64] = p1; Sm[s * LP + lane + 64] = ds1; }
+    const float acc = row_accumulate(0.f, ds0, ds1, 0, Pn, Kp, 0, lane);
+    ActIO<T>::st(dqr + lane, row_accumulate(acc, ds0, ds1, Pn, nk, Ks, Pn, lane) * scale);
+  }
+  __syncthreads();
+  for (int t = wave; t < Sn; t += 4) {          // the sequence's own keys: read by its rows t .. ns - 1
+    float ak = 0.f, av = 0.f;
+    for (int s = t; s < ns; ++s) {              // (empty past the EOT: zeros)
+      ak = fmaf(Sm[s * LP + Pn + t], Qs[s * 65 + lane], ak);
+      av = fmaf(Pm[s * LP + Pn + t], Ds[s * 65 + lane], av);
+    }
+    if (own_k) {
+      own_k[t * 64 + lane] = ak;
+      own_v[t * 64 + lane] = av;
+    } else {
+      ActIO<T>::st(dk + (row0 + t) * ldd + col0 + lane, ak * scale);
+      ActIO<T>::st(dv + (row0 + t) * ldd + col0 + lane, av);
+    }
+  }
+  for (int j = wave; j < Pn; j += 4) {          // the shared keys: read by every real row of the sequence
+    float ak = Ak[j * 64 + lane], av = Av[j * 64 + lane];
+    for (int s = 0; s < ns; ++s) {
+      ak = fmaf(Sm[s * LP + j], Qs[s * 65 + lane], ak);
+      av = fmaf(Pm[s * LP + j], Ds[s * 65 + lane], av);
+    }
+    Ak[j * 64 + lane] = ak;
+    Av[j * 64 + lane] = av;
+  }
+}
+
+// rpo_text_attn_bwd_dense: one workgroup per (class, head), the class's Lmax rows as one sequence of no shared keys.  Its
+// staging is scalar loads: the entry point has no 16-byte alignment contract (d_out may be any column slice).
 template <typename T>
 __global__ __launch_bounds__(256) void text_attn_bwd_dense_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                   const T* __restrict__ v, int64_t ld,
@@ -135,74 +233,28 @@ __global__ __launch_bounds__(256) void text_attn_bwd_dense_kernel(const T* __res
                                                                   T* dv, int64_t ldd, const int32_t* __restrict__ len,
                                                                   int Lmax, int H, float scale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int LP = Lmax + 1;
-  float* Qf = reinterpret_cast<float*>(smem);
-  float* Kf = Qf + Lmax * 65;
-  float* Vf = Kf + Lmax * 65;
-  float* Df = Vf + Lmax * 65;                   // dO
-  float* Pm = Df + Lmax * 65;                   // [Lmax][LP]
-  float* Sm = Pm + Lmax * LP;                   // dS, [Lmax][LP]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* lds = reinterpret_cast<float*>(smem);
+  const BwdPrefixLds o(0, Lmax);
+  const int tid = threadIdx.x;
   const int c = blockIdx.x / H, h = blockIdx.x % H;
   const int L = min(len[c], Lmax);
   for (int id = tid; id < Lmax * 64; id += 256) {
     const int j = id >> 6, d = id & 63;
     const int64_t row = (int64_t)c * Lmax + j;
-    const bool ok = j < L;
-    Qf[j * 65 + d] = ok ? ActIO<T>::ld(q + row * ld + h * 64 + d) : 0.f;
-    Kf[j * 65 + d] = ok ? ActIO<T>::ld(k + row * ld + h * 64 + d) : 0.f;
-    Vf[j * 65 + d] = ok ? ActIO<T>::ld(v + row * ld + h * 64 + d) : 0.f;
-    Df[j * 65 + d] = ok ? ActIO<T>::ld(dout + row * lddo + h * 64 + d) : 0.f;
+    float qv = 0.f, kv = 0.f, vv = 0.f, dv = 0.f;
+    if (j < L) {                                // the four loads in flight together, then the LDS writes
+      qv = ActIO<T>::ld(q + row * ld + h * 64 + d);
+      kv = ActIO<T>::ld(k + row * ld + h * 64 + d);
+      vv = ActIO<T>::ld(v + row * ld + h * 64 + d);
+      dv = ActIO<T>::ld(dout + row * lddo + h * 64 + d);
+    }
+    lds[o.qs + j * 65 + d] = qv;
+    lds[o.ks + j * 65 + d] = kv;
+    lds[o.vs + j * 65 + d] = vv;
+    lds[o.ds + j * 65 + d] = dv;
   }
   __syncthreads();
-  const int j0 = min(lane, Lmax - 1), j1 = min(lane + 64, Lmax - 1);
-  for (int r = wave; r < Lmax; r += 4) {
-    const int64_t row = (int64_t)c * Lmax + r;
-    if (r >= L) {                               // padding rows: zero gradients (the dX GEMM reads every row)
-      ActIO<T>::st(dq + row * ldd + h * 64 + lane, 0.f);
-      continue;
-    }
-    const int nk = r + 1;                       // causal, and r < L so every key j <= r is a real token
-    const float qv = Qf[r * 65 + lane], dov = Df[r * 65 + lane];
-    float s0 = 0.f, s1 = 0.f, dp0 = 0.f, dp1 = 0.f;
-#pragma unroll 8
-    for (int d = 0; d < 64; ++d) {
-      const float qd = bcast(qv, d), dd = bcast(dov, d);
-      s0 = fmaf(qd, Kf[j0 * 65 + d], s0);
-      s1 = fmaf(qd, Kf[j1 * 65 + d], s1);
-      dp0 = fmaf(dd, Vf[j0 * 65 + d], dp0);
-      dp1 = fmaf(dd, Vf[j1 * 65 + d], dp1);
-    }
-    s0 = lane < nk ? s0 * scale : -INFINITY;
-    s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
-    const float m = wave_max(fmaxf(s0, s1));
-    float p0 = expf(s0 - m), p1 = expf(s1 - m);
-    const float inv = 1.0f / wave_sum(p0 + p1);
-    p0 *= inv; p1 *= inv;
-    dp0 = lane < nk ? dp0 : 0.f;
-    dp1 = lane + 64 < nk ? dp1 : 0.f;
-    const float delta = wave_sum(p0 * dp0 + p1 * dp1);
-    const float ds0 = p0 * (dp0 - delta), ds1 = p1 * (dp1 - delta);
-    if (lane < Lmax) { Pm[r * LP + lane] = p0; Sm[r * LP + lane] = ds0; }
-    if (lane + 64 < Lmax) { Pm[r * LP + lane + 64] = p1; Sm[r * LP + lane + 64] = ds1; }
-    float acc = 0.f;
-    for (int j = 0; j < nk; ++j) {
-      const float dj = j < 64 ? bcast(ds0, j) : bcast(ds1, j - 64);
-      acc = fmaf(dj, Kf[j * 65 + lane], acc);
-    }
-    ActIO<T>::st(dq + row * ldd + h * 64 + lane, acc * scale);
-  }
-  __syncthreads();
-  for (int j = wave; j < Lmax; j += 4) {
-    const int64_t row = (int64_t)c * Lmax + j;
-    float ak = 0.f, av = 0.f;
-    for (int r = j; r < L; ++r) {               // (empty for padding keys j >= L: zeros)
-      ak = fmaf(Sm[r * LP + j], Qf[r * 65 + lane], ak);
-      av = fmaf(Pm[r * LP + j], Df[r * 65 + lane], av);
-    }
-    ActIO<T>::st(dk + row * ldd + h * 64 + lane, ak * scale);
-    ActIO<T>::st(dv + row * ldd + h * 64 + lane, av);
-  }
+  bwd_sequence_compute<T>(dq, dk, dv, ldd, (int64_t)c * Lmax, h * 64, 0, Lmax, L, lds, o, nullptr, nullptr, scale, tid);
 }
 
 template <typename T>
@@ -211,8 +263,8 @@ int launch_dense(const void* q, const void* k, const void* v, int64_t ld, const 
                  hipStream_t s) {
   static rpo_lds_mask_t lds_ok{0};
   auto kern = text_attn_bwd_dense_kernel<T>;
-  const int bytes = (4 * Lmax * 65 + 2 * Lmax * (Lmax + 1)) * 4;
-  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), (4 * 80 * 65 + 2 * 80 * 81) * 4, &lds_ok)) return rc;
+  const int bytes = BwdPrefixLds(0, Lmax).total * 4;
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), BwdPrefixLds(0, 80).total * 4, &lds_ok)) return rc;
   hipLaunchKernelGGL(kern, dim3(n_cls * H), dim3(256), bytes, s, static_cast<const T*>(q), static_cast<const T*>(k),
                      static_cast<const T*>(v), ld, static_cast<const T*>(dout), lddo, static_cast<T*>(dq),
                      static_cast<T*>(dk), static_cast<T*>(dv), ldd, len, Lmax, H, scale);
@@ -264,20 +316,8 @@ __device__ __forceinline__ void stage_kv_rows(const T* __restrict__ k, const T* 
     const int64_t off = (row0 + j) * ld + col0 + cch * EPC;
     const uint4 kq = *reinterpret_cast<const uint4*>(k + off);
     const uint4 vq = *reinterpret_cast<const uint4*>(v + off);
-    float* kd = Kd + j * 65 + cch * EPC;
-    float* vd = Vd + j * 65 + cch * EPC;
-    const uint32_t kw[4] = {kq.x, kq.y, kq.z, kq.w};
-    const uint32_t vw[4] = {vq.x, vq.y, vq.z, vq.w};
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        kd[2 * e] = unpack1<T>((uint16_t)(kw[e] & 0xffffu)); kd[2 * e + 1] = unpack1<T>((uint16_t)(kw[e] >> 16));
-        vd[2 * e] = unpack1<T>((uint16_t)(vw[e] & 0xffffu)); vd[2 * e + 1] = unpack1<T>((uint16_t)(vw[e] >> 16));
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { kd[e] = __uint_as_float(kw[e]); vd[e] = __uint_as_float(vw[e]); }
-    }
+    unpack_chunk<T>(kq, Kd + j * 65 + cch * EPC);
+    unpack_chunk<T>(vq, Vd + j * 65 + cch * EPC);
   }
 }
 
@@ -289,31 +329,12 @@ __device__ __forceinline__ void prefix_attn_row(const T* __restrict__ qrow, T* o
   const int j0 = min(lane, Lmax - 1), j1 = min(lane + 64, Lmax - 1);
   const float* k0 = j0 < P ? Kp + j0 * 65 : Ks + (j0 - P) * 65;
   const float* k1 = j1 < P ? Kp + j1 * 65 : Ks + (j1 - P) * 65;
-  const float qv = ActIO<T>::ld(qrow + lane);
-  float s0 = 0.f, s1 = 0.f;
-#pragma unroll 8
-  for (int d = 0; d < 64; ++d) {
-    const float qd = bcast(qv, d);
-    s0 = fmaf(qd, k0[d], s0);
-    s1 = fmaf(qd, k1[d], s1);
-  }
-  s0 = lane < nk ? s0 * scale : -INFINITY;
-  s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
-  const float m = wave_max(fmaxf(s0, s1));
-  float p0 = expf(s0 - m), p1 = expf(s1 - m);
-  const float inv = 1.0f / wave_sum(p0 + p1);
-  p0 *= inv; p1 *= inv;
-  float acc = 0.f;
+  float p0, p1;
+  row_dots(ActIO<T>::ld(qrow + lane), k0, k1, p0, p1);
+  row_softmax(p0, p1, nk, scale, lane);
   const int np = min(nk, P);
-  for (int j = 0; j < np; ++j) {
-    const float pj = j < 64 ? bcast(p0, j) : bcast(p1, j - 64);
-    acc = fmaf(pj, Vp[j * 65 + lane], acc);
-  }
-  for (int j = np; j < nk; ++j) {
-    const float pj = j < 64 ? bcast(p0, j) : bcast(p1, j - 64);
-    acc = fmaf(pj, Vs[(j - P) * 65 + lane], acc);
-  }
-  ActIO<T>::st(orow + lane, acc);
+  const float acc = row_accumulate(0.f, p0, p1, 0, np, Vp, 0, lane);
+  ActIO<T>::st(orow + lane, row_accumulate(acc, p0, p1, np, nk, Vs, P, lane));
 }
 
 template <typename T>
@@ -392,8 +413,8 @@ int launch_prefix(const void* q, const void* k, const void* v, int64_t ld, void*
 // what their suffix queries contribute -- summed HERE, in every block, which is what lets LayerNorm backward and the dX
 // GEMMs (linear in the incoming gradient) run on the one shared row too.
 // One workgroup per (image, head, slot).  Slots 0 .. groups - 1 walk `group` classes each: the image's P prefix K / V
-// head slices are staged once, then per class its S suffix rows' Q / K / V / dO; pass 1 (one wave per query row) and pass 2
-// (one wave per key) are the dense kernel's, with key j in the prefix arrays below P and in the class's own from there on.
+// head slices are staged once, then per class its S suffix rows' Q / K / V / dO; the two passes are bwd_sequence_compute's,
+// with key j in the prefix arrays below P and in the class's own from there on.
 // What the class's queries give prefix key j is accumulated in LDS (Ak / Av [P][64]: element (j, lane) belongs to wave
 // j % 4 alone), classes in ascending order, rows in ascending order, and written as an fp32 partial to the workspace.  The
 // last slot (`groups`) is the prefix itself: the same routine on a sequence of no shared keys and P own rows, whose dq goes
@@ -401,30 +422,15 @@ int launch_prefix(const void* q, const void* k, const void* v, int64_t ld, void*
 // slots in ascending order (class groups, then the self part) and rounds once: no atomics, no arrival order -- the same
 // bits every time, and image b's bits do not depend on the other images of the launch (the grouping is a function of
 // n_cls and H alone).
-struct BwdPrefixLds {                          // floats from the start of the dynamic LDS
-  int kp, vp, ak, av, qs, ks, vs, ds, pm, sm, total;
-  __host__ __device__ BwdPrefixLds(int Pn, int Sn) {
-    kp = 0; vp = kp + Pn * 65; ak = vp + Pn * 65; av = ak + Pn * 64;
-    qs = av + Pn * 64; ks = qs + Sn * 65; vs = ks + Sn * 65; ds = vs + Sn * 65;
-    pm = ds + Sn * 65; sm = pm + Sn * (Pn + Sn + 1); total = sm + Sn * (Pn + Sn + 1);
-  }
-};
-
-// One sequence of Pn shared keys (already in Kp / Vp) and Sn own rows (global rows row0 .., positions Pn ..) of which the
-// first ns are real.  dq of the own rows is written (zeros from ns on); dk / dv of the own rows go to the outputs (zeros
-// from ns on) or, unscaled, to own_k / own_v [Sn][64] where those are given; the shared keys' share is added to Ak / Av.
-// Every thread of the workgroup calls it (barriers inside).
+// Stages a sequence's Sn own rows (the shared keys are already in Kp / Vp) and runs bwd_sequence_compute on it.  Every
+// thread of the workgroup calls it (barriers inside).
 template <typename T>
 __device__ __forceinline__ void bwd_prefix_sequence(const T* __restrict__ q, const T* __restrict__ k,
                                                     const T* __restrict__ v, int64_t ld, const T* __restrict__ dout,
                                                     int64_t lddo, T* dq, T* dk, T* dv, int64_t ldd, int64_t row0, int col0,
                                                     int Pn, int Sn, int ns, float* lds, const BwdPrefixLds& o,
                                                     float* own_k, float* own_v, float scale, int tid) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const int Lt = Pn + Sn, LP = Lt + 1;
-  const float *Kp = lds + o.kp, *Vp = lds + o.vp;
-  float *Ak = lds + o.ak, *Av = lds + o.av, *Qs = lds + o.qs, *Ks = lds + o.ks, *Vs = lds + o.vs, *Ds = lds + o.ds;
-  float *Pm = lds + o.pm, *Sm = lds + o.sm;
+  float *Qs = lds + o.qs, *Ks = lds + o.ks, *Vs = lds + o.vs, *Ds = lds + o.ds;
   stage_kv_rows<T>(k, v, ld, row0, ns, col0, Ks, Vs, tid);
   for (int id = tid; id < Sn * 64; id += 256) {
     const int s = id >> 6, d = id & 63;
@@ -434,75 +440,7 @@ __device__ __forceinline__ void bwd_prefix_sequence(const T* __restrict__ q, con
     if (!ok) { Ks[s * 65 + d] = 0.f; Vs[s * 65 + d] = 0.f; }
   }
   __syncthreads();
-  const int j0 = min(lane, Lt - 1), j1 = min(lane + 64, Lt - 1);
-  const float* k0 = j0 < Pn ? Kp + j0 * 65 : Ks + (j0 - Pn) * 65;
-  const float* k1 = j1 < Pn ? Kp + j1 * 65 : Ks + (j1 - Pn) * 65;
-  const float* v0 = j0 < Pn ? Vp + j0 * 65 : Vs + (j0 - Pn) * 65;
-  const float* v1 = j1 < Pn ? Vp + j1 * 65 : Vs + (j1 - Pn) * 65;
-  for (int s = wave; s < Sn; s += 4) {
-    T* dqr = dq + (row0 + s) * ldd + col0;
-    if (s >= ns) {                              // past the EOT: zero gradients (the dX GEMM reads every row)
-      ActIO<T>::st(dqr + lane, 0.f);
-      continue;
-    }
-    const int nk = Pn + s + 1;                  // causal, and s < ns: every key up to this row is a real token
-    const float qv = Qs[s * 65 + lane], dov = Ds[s * 65 + lane];
-    float s0 = 0.f, s1 = 0.f, dp0 = 0.f, dp1 = 0.f;
-#pragma unroll 8
-    for (int d = 0; d < 64; ++d) {
-      const float qd = bcast(qv, d), dd = bcast(dov, d);
-      s0 = fmaf(qd, k0[d], s0);
-      s1 = fmaf(qd, k1[d], s1);
-      dp0 = fmaf(dd, v0[d], dp0);
-      dp1 = fmaf(dd, v1[d], dp1);
-    }
-    s0 = lane < nk ? s0 * scale : -INFINITY;
-    s1 = lane + 64 < nk ? s1 * scale : -INFINITY;
-    const float m = wave_max(fmaxf(s0, s1));
-    float p0 = expf(s0 - m), p1 = expf(s1 - m);
-    const float inv = 1.0f / wave_sum(p0 + p1);
-    p0 *= inv; p1 *= inv;
-    dp0 = lane < nk ? dp0 : 0.f;
-    dp1 = lane + 64 < nk ? dp1 : 0.f;
-    const float delta = wave_sum(p0 * dp0 + p1 * dp1);
-    const float ds0 = p0 * (dp0 - delta), ds1 = p1 * (dp1 - delta);
-    if (lane < Lt) { Pm[s * LP + lane] = p0; Sm[s * LP + lane] = ds0; }
-    if (lane + 64 < Lt) { Pm[s * LP + lane + 64] = p1; Sm[s * LP + lane + 64] = ds1; }
-    float acc = 0.f;
-    for (int j = 0; j < Pn; ++j) {
-      const float dj = j < 64 ? bcast(ds0, j) : bcast(ds1, j - 64);
-      acc = fmaf(dj, Kp[j * 65 + lane], acc);
-    }
-    for (int j = Pn; j < nk; ++j) {
-      const float dj = j < 64 ? bcast(ds0, j) : bcast(ds1, j - 64);
-      acc = fmaf(dj, Ks[(j - Pn) * 65 + lane], acc);
-    }
-    ActIO<T>::st(dqr + lane, acc * scale);
-  }
-  __syncthreads();
-  for (int t = wave; t < Sn; t += 4) {          // the sequence's own keys: read by its rows t .. ns - 1
-    float ak = 0.f, av = 0.f;
-    for (int s = t; s < ns; ++s) {              // (empty past the EOT: zeros)
-      ak = fmaf(Sm[s * LP + Pn + t], Qs[s * 65 + lane], ak);
-      av = fmaf(Pm[s * LP + Pn + t], Ds[s * 65 + lane], av);
-    }
-    if (own_k) {
-      own_k[t * 64 + lane] = ak;
-      own_v[t * 64 + lane] = av;
-    } else {
-      ActIO<T>::st(dk + (row0 + t) * ldd + col0 + lane, ak * scale);
-      ActIO<T>::st(dv + (row0 + t) * ldd + col0 + lane, av);
-    }
-  }
-  for (int j = wave; j < Pn; j += 4) {          // the shared keys: read by every real row of the sequence
-    float ak = Ak[j * 64 + lane], av = Av[j * 64 + lane];
-    for (int s = 0; s < ns; ++s) {
-      ak = fmaf(Sm[s * LP + j], Qs[s * 65 + lane], ak);
-      av = fmaf(Pm[s * LP + j], Ds[s * 65 + lane], av);
-    }
-    Ak[j * 64 + lane] = ak;
-    Av[j * 64 + lane] = av;
-  }
+  bwd_sequence_compute<T>(dq, dk, dv, ldd, row0, col0, Pn, Sn, ns, lds, o, own_k, own_v, scale, tid);
   __syncthreads();                              // the next sequence re-stages the own rows
 }
 
@@ -590,6 +528,15 @@ int launch_bwd_prefix(const void* q, const void* k, const void* v, int64_t ld, c
   return rpo_launch_status();
 }
 
+// f(T{}) for the storage type T of `dtype`
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+  if (dtype == RPO_F16) return f(f16_t{});
+  if (dtype == RPO_BF16) return f(bf16_t{});
+  if (dtype == RPO_F32) return f(float{});
+  return RPO_E_DTYPE;
+}
+
 }  // namespace
 
 // n_kv < n_cls: the n_cls classes are VIRTUAL -- class v reads len[v % n_kv] and the cache rows of class v % n_kv
@@ -610,13 +557,10 @@ static int text_attn_fwd_impl(const void* q, int64_t ldq, const void* kc, const 
     if (rc != RPO_E_SHAPE) return rc;
   }
 #endif
-  if (dtype == RPO_F16)
-    return launch<f16_t, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, n_kv, s);
-  if (dtype == RPO_BF16)
-    return launch<bf16_t, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, n_kv, s);
-  if (dtype == RPO_F32)
-    return launch<float, false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale, n_kv, s);
-  return RPO_E_DTYPE;
+  return by_dtype(dtype, [&](auto t) {
+    return launch<decltype(t), false>(q, ldq, kc, vc, ldkv, nullptr, 0, out, ldo, len, n_cls, rows, Lmax, H, causal, scale,
+                                      n_kv, s);
+  });
 }
 
 static int text_attn_bwd_impl(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv, const void* da,
@@ -635,13 +579,9 @@ static int text_attn_bwd_impl(const void* q, int64_t ldq, const void* kc, const 
     if (rc != RPO_E_SHAPE) return rc;
   }
 #endif
-  if (dtype == RPO_F16)
-    return launch<f16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
-  if (dtype == RPO_BF16)
-    return launch<bf16_t, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
-  if (dtype == RPO_F32)
-    return launch<float, true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
-  return RPO_E_DTYPE;
+  return by_dtype(dtype, [&](auto t) {
+    return launch<decltype(t), true>(q, ldq, kc, vc, ldkv, da, ldda, dq, lddq, len, n_cls, rows, Lmax, H, 0, scale, n_kv, s);
+  });
 }
 
 extern "C" int rpo_text_attn_fwd(const void* q, int64_t ldq, const void* kc, const void* vc, int64_t ldkv,
@@ -680,10 +620,9 @@ extern "C" int rpo_text_attn_bwd_dense(const void* q, const void* k, const void*
   if (!q || !k || !v || !d_out || !dq || !dk || !dv || !len || n_cls <= 0 || Lmax <= 0 || H <= 0) return RPO_E_BADARG;
   if (Lmax > 80) return RPO_E_SHAPE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == RPO_F16) return launch_dense<f16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_cls, Lmax, H, scale, s);
-  if (dtype == RPO_BF16) return launch_dense<bf16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_cls, Lmax, H, scale, s);
-  if (dtype == RPO_F32) return launch_dense<float>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_cls, Lmax, H, scale, s);
-  return RPO_E_DTYPE;
+  return by_dtype(dtype, [&](auto t) {
+    return launch_dense<decltype(t)>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_cls, Lmax, H, scale, s);
+  });
 }
 
 extern "C" int rpo_text_attn_fwd_prefix(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo,
@@ -697,9 +636,9 @@ extern "C" int rpo_text_attn_fwd_prefix(const void* q, const void* k, const void
   const int esz = dtype == RPO_F32 ? 4 : 2;
   if (!aligned16(k) || !aligned16(v) || (ld * esz) % 16 != 0 || (ldo * esz) % 16 != 0) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == RPO_F16) return launch_prefix<f16_t>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
-  if (dtype == RPO_BF16) return launch_prefix<bf16_t>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
-  return launch_prefix<float>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
+  return by_dtype(dtype, [&](auto t) {
+    return launch_prefix<decltype(t)>(q, k, v, ld, out, ldo, len, n_img, n_cls, P, S, H, scale, s);
+  });
 }
 
 extern "C" int64_t rpo_text_attn_bwd_prefix_workspace_floats(int n_img, int n_cls, int P, int H) {
@@ -723,9 +662,8 @@ extern "C" int rpo_text_attn_bwd_prefix(const void* q, const void* k, const void
       (ldd * esz) % 16 != 0)
     return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == RPO_F16)
-    return launch_bwd_prefix<f16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale, workspace, s);
-  if (dtype == RPO_BF16)
-    return launch_bwd_prefix<bf16_t>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale, workspace, s);
-  return launch_bwd_prefix<float>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale, workspace, s);
+  return by_dtype(dtype, [&](auto t) {
+    return launch_bwd_prefix<decltype(t)>(q, k, v, ld, d_out, lddo, dq, dk, dv, ldd, len, n_img, n_cls, P, S, H, scale,
+                                          workspace, s);
+  });
 }

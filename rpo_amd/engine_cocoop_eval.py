@@ -24,10 +24,10 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_NONE
 from .class_set import ClassSet
+from .engine_coop import shared_eot_rows, shared_fill, shared_split
+from .engine_text import SCALE
 
-SCALE = 0.125                       # 1 / sqrt(head_dim = 64)
 MAX_IMAGES_PER_PASS = 256           # rpo_metanet_fwd keeps B * h floats in 48 KB of LDS; the grouped head takes <= 1024 groups
 
 
@@ -82,10 +82,7 @@ class ConditionalClassSet(ClassSet):
         assert plan is not None and plan["Lmax"] == self.Lmax
         P = self.P = plan["P"]
         self.S, self.images_per_pass, self.classes_per_pass = plan["S"], plan["images_per_pass"], plan["classes_per_pass"]
-        dt = engine.cfg.d_t
-        x = self.x_frozen.view(self.n, self.Lmax, dt)
-        self.x_sos = x[0, 0].clone()                                        # SOS embedding + pos[0]: the same for every class
-        self.x_suffix = x[:, P:].reshape(self.n * self.S, dt).contiguous()  # positions >= P of every class
+        self.x_sos, self.x_suffix = shared_split(self.x_frozen, self.n, self.Lmax, P)
         self.x_frozen = None
         self._ws = None                                                     # per-pass buffers, sized on first use
         self._out = None                                                    # per-call buffers (image features, logits)
@@ -123,10 +120,7 @@ class ConditionalClassSet(ClassSet):
         """The EOT row of every (image, class) of a pass over Bc images and classes [c0, c1): always a suffix row."""
         key = (Bc, c0, c1)
         if key not in self._eot:
-            nc = c1 - c0
-            off = np.arange(nc, dtype=np.int64) * self.S + (self.len_np[c0:c1].astype(np.int64) - 1 - self.P)
-            rows = Bc * self.P + np.arange(Bc, dtype=np.int64)[:, None] * (nc * self.S) + off[None, :]
-            self._eot[key] = torch.as_tensor(rows.reshape(-1), device=self.engine.dev)
+            self._eot[key] = torch.as_tensor(shared_eot_rows(Bc, self.P, self.S, self.len_np[c0:c1]), device=self.engine.dev)
         return self._eot[key]
 
 
@@ -145,7 +139,7 @@ class ConditionalEvalEngineMixin:
         """logits [Bc, n'] of Bc images (raw features img_f [Bc, e]) against the class set: meta-net, the text blocks over
         Bc * (P + nc * S) rows per class chunk, EOT features, one grouped head launch."""
         cfg = self.cfg
-        dt, e, H, n, P, S = cfg.d_t, cfg.embed, cfg.heads_t, ccs.n, ccs.P, ccs.S
+        e, H, n, P, S, Lt = cfg.embed, cfg.heads_t, ccs.n, ccs.P, ccs.S, len(self.txt)
         Bc = img_f.shape[0]
         ws = ccs.pass_buffers(Bc)
         w1, b1, w2, b2 = self.meta
@@ -159,27 +153,13 @@ class ConditionalEvalEngineMixin:
             nc = c1 - c0
             R = Bc * (P + nc * S)
             x, xm, h, qkv, att, g = (ws[k][:R] for k in ("x", "xm", "h", "qkv", "att", "g"))
-            xp = x[:Bc * P].view(Bc, P, dt)
-            xp[:, 0] = ccs.x_sos
-            torch.add(shift, pos[1:P], out=xp[:, 1:])
-            x[Bc * P:].view(Bc, nc * S, dt).copy_(ccs.x_suffix[c0 * S:c1 * S].unsqueeze(0).expand(Bc, -1, -1))
+            shared_fill(x, Bc, P, ccs.x_sos, shift, pos, ccs.x_suffix[c0 * S:c1 * S])
             ln = ccs.len_i32[c0:c1]
-            for blk in self.txt:
-                ops.layernorm_fwd(x, blk.ln1_w, blk.ln1_b, h)
-                ops.gemm_nt(h, blk.w_in, qkv, EPI_BIAS, bias=blk.b_in)
-                ops.text_attn_fwd_prefix(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], att, ln, Bc, nc, P, S, H, SCALE)
-                ops.gemm_nt(att, blk.w_out, xm, EPI_BIAS_RESID, bias=blk.b_out, resid=x)
-                ops.layernorm_fwd(xm, blk.ln2_w, blk.ln2_b, h)
-                ops.gemm_nt(h, blk.w_fc, g, EPI_BIAS_QGELU, bias=blk.b_fc, aux=None, aux_row0=R)
-                ops.gemm_nt(g, blk.w_proj, x, EPI_BIAS_RESID, bias=blk.b_proj, resid=xm)
-            x_eot, y_eot = ws["x_eot"][:Bc * nc], ws["y_eot"][:Bc * nc]
-            torch.index_select(x, 0, ccs.eot_rows(Bc, c0, c1), out=x_eot)                     # feature at the EOT token
-            ops.layernorm_fwd(x_eot, self.ln_final[0], self.ln_final[1], y_eot)
-            if nc == n:
-                ops.gemm_nt(y_eot, self.text_proj_t, ws["text_f"][:Bc * n], EPI_NONE)
-            else:
-                f = ws["f_chunk"][:Bc * nc]
-                ops.gemm_nt(y_eot, self.text_proj_t, f, EPI_NONE)
+            attn = lambda q, k, v, out: ops.text_attn_fwd_prefix(q, k, v, out, ln, Bc, nc, P, S, H, SCALE)
+            self._text_blocks([x] * (Lt + 1), [xm] * Lt, [qkv] * Lt, h, att, g, attn)
+            f = ws["text_f"][:Bc * n] if nc == n else ws["f_chunk"][:Bc * nc]
+            self._text_eot_tail(x, ccs.eot_rows(Bc, c0, c1), ws["x_eot"][:Bc * nc], ws["y_eot"][:Bc * nc], f)
+            if nc != n:
                 text_f[:, c0:c1].copy_(f.view(Bc, nc, e))
         # every image has its own text features: Bc independent heads of one image each, in one launch
         ops.head_fwd_bwd_grouped(img_f.view(Bc, 1, e), ws["text_f"][:Bc * n].view(Bc * n, 1, e), None, self.logit_scale_exp,

@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_NONE, EPI_QGELU_BWD
+from ._lib import EPI_NONE, EPI_QGELU_BWD
+from .engine_text import SCALE
 
-SCALE = 0.125                       # 1 / sqrt(head_dim = 64)
 SPLIT_FC, SPLIT_Q = 3, 2            # split-K factors of the two fp32-output dX GEMMs on rpo_gemm_nt (engine.py)
 
 
@@ -50,6 +50,33 @@ def shared_rows(replicas: int, n_cls: int, Lmax: int, n_ctx: int) -> int:
     the S = Lmax - P later positions of every class -- against the dense replicas * n_cls * Lmax."""
     P = 1 + n_ctx
     return replicas * (P + n_cls * (Lmax - P))
+
+
+def shared_split(x_frozen: torch.Tensor, n_cls: int, Lmax: int, P: int):
+    """The frozen rows [n_cls * Lmax, d] (token + positional embeddings) as the shared layout keeps them: (x_sos [d], the
+    SOS row, the same for every class; x_suffix [n_cls * S, d], the positions >= P of every class)."""
+    x = x_frozen.view(n_cls, Lmax, -1)
+    return x[0, 0].clone(), x[:, P:].reshape(n_cls * (Lmax - P), -1).contiguous()
+
+
+def shared_fill(x: torch.Tensor, replicas: int, P: int, x_sos: torch.Tensor, shift: torch.Tensor, pos: torch.Tensor,
+                x_suffix: torch.Tensor) -> None:
+    """The input rows x of a pass over `replicas` replicas: per replica [SOS | shift[r] + pos[1:P]], then the suffix rows
+    x_suffix [n_cls * S, d] of its classes once per replica."""
+    xp = x[:replicas * P].view(replicas, P, -1)
+    xp[:, 0] = x_sos
+    torch.add(shift, pos[1:P], out=xp[:, 1:])
+    x[replicas * P:].view(replicas, *x_suffix.shape).copy_(x_suffix.unsqueeze(0).expand(replicas, -1, -1))
+
+
+def shared_eot_rows(replicas: int, P: int, S: int, lengths) -> np.ndarray:
+    """The EOT row of every (replica, class) of a pass over `replicas` replicas and the classes whose prompt lengths are
+    given: always a suffix row; the prefix block in front grows with the replica count."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    n = lengths.shape[0]
+    off = np.arange(n, dtype=np.int64) * S + (lengths - 1 - P)
+    assert int((lengths - P).min()) >= 1 and int((lengths - P).max()) <= S
+    return (replicas * P + np.arange(replicas, dtype=np.int64)[:, None] * (n * S) + off[None, :]).reshape(-1)
 
 
 def check_shared_prefix(shared_prefix: bool, csc: bool, class_token_position: str) -> None:
@@ -178,38 +205,30 @@ class CoopEngineMixin:
             vals = (cs if self.coop_csc else cs.unsqueeze(1).expand(R, n, nc, dt).reshape(R, n * nc, dt)) + cpos
             for r in range(R):
                 x0[r * n * L:(r + 1) * n * L].index_copy_(0, self.c_ctx_rows_idx, vals[r])
-        ch, catt, cg, ln = self.ch[:Rf], self.catt[:Rf], self.cg[:Rf], self.c_len[:nv]
-        for l, blk in enumerate(self.txt):
-            x, xm, qkv = self.cx[l][:Rf], self.cxm[l][:Rf], self.cqkv[l][:Rf]
-            ops.layernorm_fwd(x, blk.ln1_w, blk.ln1_b, ch)
-            ops.gemm_nt(ch, blk.w_in, qkv, EPI_BIAS, bias=blk.b_in)
-            ops.text_attn_fwd(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], catt, ln, nv, L, L, H, causal=True, scale=SCALE)
-            ops.gemm_nt(catt, blk.w_out, xm, EPI_BIAS_RESID, bias=blk.b_out, resid=x)
-            ops.layernorm_fwd(xm, blk.ln2_w, blk.ln2_b, ch)
-            ops.gemm_nt(ch, blk.w_fc, cg, EPI_BIAS_QGELU, bias=blk.b_fc, aux=self.cu[l][:Rf] if train else None,
-                        aux_row0=0 if train else Rf)
-            ops.gemm_nt(cg, blk.w_proj, self.cx[l + 1][:Rf], EPI_BIAS_RESID, bias=blk.b_proj, resid=xm)
-        torch.index_select(self.cx[-1], 0, self.c_eot[:nv], out=self.c_x_eot[:nv])        # feature at the EOT token
-        ops.layernorm_fwd(self.c_x_eot[:nv], self.ln_final[0], self.ln_final[1], self.c_y_eot[:nv])
-        ops.gemm_nt(self.c_y_eot[:nv], self.text_proj_t, self.c_text_f[:nv], EPI_NONE)
+        ln = self.c_len[:nv]
+        self._coop_blocks_forward(train, Rf, nv, self.c_eot[:nv], lambda q, k, v, out: ops.text_attn_fwd(
+            q, k, v, out, ln, nv, L, L, H, causal=True, scale=SCALE))
 
-    def _coop_text_backward(self, R: int = 1) -> None:
-        """c_dshift[r] = d loss / d (context of replica r): autograd of the whole text tower for all tokens (dX GEMMs only
-        -- the weights are frozen), the causal attention backward with dK / dV (rpo_text_attn_bwd_dense), then the rows of
-        the context positions summed over the classes (ctx.unsqueeze(0).expand, trainers/coop.py:119-121)."""
-        if self.coop_shared:
-            return self._coop_prefix_backward(R)
-        cfg = self.cfg
-        n, L, dt, H, nc = cfg.n_cls, self.Lmax, cfg.d_t, cfg.heads_t, self.coop_n_ctx
-        nv = R * n
-        Rf = nv * L
+    def _coop_blocks_forward(self, train: bool, Rf: int, nv: int, eot: torch.Tensor, attn) -> None:
+        """cx[0][:Rf] -> c_text_f[:nv] on coop_setup's buffers: the text blocks with every block's inputs kept for the
+        backward, then the EOT tail of rows `eot`.  attn: the attention of the row layout (dense or shared-prefix)."""
+        cut = lambda ts: [t[:Rf] for t in ts]
+        self._text_blocks(cut(self.cx), cut(self.cxm), cut(self.cqkv), self.ch[:Rf], self.catt[:Rf], self.cg[:Rf], attn,
+                          aux=cut(self.cu) if train else None)
+        self._text_eot_tail(self.cx[-1], eot, self.c_x_eot[:nv], self.c_y_eot[:nv], self.c_text_f[:nv])
+
+    def _coop_blocks_backward(self, Rf: int, nv: int, eot: torch.Tensor, attn_bwd) -> torch.Tensor:
+        """d loss / d cx[0][:Rf] from c_d_text_f[:nv]: autograd of the EOT tail and of the text blocks for all rows (dX
+        GEMMs only -- the weights are frozen).  attn_bwd(q, k, v, d_out, dq, dk, dv): the attention backward of the row
+        layout.  Returns the buffer that holds the result."""
+        dt = self.cfg.d_t
         f32m = self.act == torch.float32
         dxa, dxb, dxc, dy = self.c_dxa[:Rf], self.c_dxb[:Rf], self.c_dxc[:Rf], self.c_dy[:, :Rf]
-        du, da, dq, ln = self.c_du[:Rf], self.c_da[:Rf], self.c_dqkv[:Rf], self.c_len[:nv]
+        du, da, dq = self.c_du[:Rf], self.c_da[:Rf], self.c_dqkv[:Rf]
         ops.gemm_nt(self.c_d_text_f[:nv] if f32m else self.c_d_text_f_a[:nv], self.text_proj, self.c_dy_eot[:nv], EPI_NONE)
         ops.layernorm_bwd(self.c_dy_eot[:nv], self.c_x_eot[:nv], self.ln_final[0], None, self.c_dx_eot[:nv])
         dxa.zero_()
-        dxa.index_copy_(0, self.c_eot[:nv], self.c_dx_eot[:nv])
+        dxa.index_copy_(0, eot, self.c_dx_eot[:nv])
         if not f32m:
             ops.convert(dxa, dxc)
         for l in reversed(range(len(self.txt))):
@@ -218,10 +237,24 @@ class CoopEngineMixin:
             ops.gemm_nt(du, blk.w_fc_t, dy[:SPLIT_FC], EPI_NONE, split_k=SPLIT_FC)
             ops.layernorm_bwd(dy[:SPLIT_FC], self.cxm[l][:Rf], blk.ln2_w, dxa, dxb, None if f32m else dxc)
             ops.gemm_nt(dxb if f32m else dxc, blk.w_out_t, da, EPI_NONE)
-            ops.text_attn_bwd_dense(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], da, dq[:, :dt], dq[:, dt:2 * dt],
-                                    dq[:, 2 * dt:], ln, nv, L, H, SCALE)
+            attn_bwd(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], da, dq[:, :dt], dq[:, dt:2 * dt], dq[:, 2 * dt:])
             ops.gemm_nt(dq, self.c_w_in_t[l], dy[:SPLIT_Q], EPI_NONE, split_k=SPLIT_Q)
             ops.layernorm_bwd(dy[:SPLIT_Q], self.cx[l][:Rf], blk.ln1_w, dxb, dxa, None if f32m else dxc)
+        return dxa
+
+    def _coop_text_backward(self, R: int = 1) -> None:
+        """c_dshift[r] = d loss / d (context of replica r): `_coop_blocks_backward` with the causal attention backward with
+        dK / dV (rpo_text_attn_bwd_dense), then the rows of the context positions summed over the classes
+        (ctx.unsqueeze(0).expand, trainers/coop.py:119-121)."""
+        if self.coop_shared:
+            return self._coop_prefix_backward(R)
+        cfg = self.cfg
+        n, L, dt, H, nc = cfg.n_cls, self.Lmax, cfg.d_t, cfg.heads_t, self.coop_n_ctx
+        nv = R * n
+        Rf = nv * L
+        ln = self.c_len[:nv]
+        dxa = self._coop_blocks_backward(Rf, nv, self.c_eot[:nv], lambda q, k, v, da, dq, dk, dv: ops.text_attn_bwd_dense(
+            q, k, v, da, dq, dk, dv, ln, nv, L, H, SCALE))
         rows = self.c_ctx_rows[:nv * nc]
         if self.coop_position == "end" and not self.coop_csc:
             rows.view(nv, nc, dt).copy_(dxa.view(nv, L, dt)[:, 1:1 + nc])

@@ -1,12 +1,12 @@
-"""The plain text tower of the engine for prompts it was NOT built with (rpo_amd/engine.py mixes this in): the block loop
-`cache_text_kv` runs, the EOT feature tail `forward_plain` runs, `encode_text` on top of the two (any [P, 77] token ids,
-chunked), and the caller-given classifier of `forward_plain`.  Prompt ensembling (rpo_amd.zeroshot.ZeroshotCLIP2,
-DESIGN.md 9j) is built on it."""
+"""The plain text tower of the engine (rpo_amd/engine.py mixes this in): the ONE block loop (`_text_blocks`) and EOT
+feature tail (`_text_eot_tail`) that every plain-tower pass runs -- `cache_text_kv`, `forward_plain`, class sets, the dense
+and shared-prefix CoOp / CoCoOp passes -- then `encode_text` on top of the two for prompts the engine was NOT built with
+(any [P, 77] token ids, chunked), and the caller-given classifier of `forward_plain`.  Prompt ensembling
+(rpo_amd.zeroshot.ZeroshotCLIP2) is built on it."""
 from __future__ import annotations
 
-import math
 import os
-from typing import List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -14,42 +14,56 @@ import torch
 from . import ops
 from ._lib import EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_NONE
 
-SCALE = 1.0 / math.sqrt(64.0)
+SCALE = 0.125                       # 1 / sqrt(head_dim = 64)
 
 
 class TextEncodeEngineMixin:
-    def _text_blocks_plain(self, x: torch.Tensor, len_i32: torch.Tensor, n: int, L: int,
-                           kv: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
-        """The text blocks over the first L positions of n prompts, x [n * L, d_t] fp32 updated in place to the last
-        block's output, under the causal AND col < len mask.  kv: per layer [n * L, 2 d_t], receives that layer's K | V."""
-        cfg, act = self.cfg, self.act
-        dt, H = cfg.d_t, cfg.heads_t
-        Rf = n * L
-        xm = torch.empty_like(x)
-        h = torch.empty(Rf, dt, dtype=act, device=self.dev)
-        qkv = torch.empty(Rf, 3 * dt, dtype=act, device=self.dev)
-        att = torch.empty(Rf, dt, dtype=act, device=self.dev)
-        g = torch.empty(Rf, 4 * dt, dtype=act, device=self.dev)
+    def _text_blocks(self, xs: Sequence[torch.Tensor], xms: Sequence[torch.Tensor], qkvs: Sequence[torch.Tensor],
+                     h: torch.Tensor, att: torch.Tensor, g: torch.Tensor, attn: Callable,
+                     kv: Optional[List[torch.Tensor]] = None, aux: Optional[Sequence[torch.Tensor]] = None) -> None:
+        """The plain text blocks (clip/model.py:171-186) over R rows: block l reads xs[l] [R, d_t] fp32 and writes
+        xs[l + 1], with xms[l] (fp32, the residual after attention) and qkvs[l] [R, 3 d_t] as its buffers.  A pass that
+        keeps nothing gives the same tensor for every layer, so x is updated in place; a training pass gives the lists the
+        backward re-reads.  h, att [R, d_t] and g [R, 4 d_t] are workspace.  attn(q, k, v, out): the attention of the row
+        layout.  kv: per layer [R, 2 d_t], receives that layer's K | V.  aux: per layer [R, 4 d_t], receives the QuickGELU
+        operand (training only)."""
+        dt, R = self.cfg.d_t, h.shape[0]
         for l, blk in enumerate(self.txt):
+            x, xm, qkv = xs[l], xms[l], qkvs[l]
             ops.layernorm_fwd(x, blk.ln1_w, blk.ln1_b, h)
             ops.gemm_nt(h, blk.w_in, qkv, EPI_BIAS, bias=blk.b_in)
-            ops.text_attn_fwd(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], att, len_i32, n, L, L, H,
-                              causal=True, scale=SCALE)
+            attn(qkv[:, :dt], qkv[:, dt:2 * dt], qkv[:, 2 * dt:], att)
             if kv is not None:
                 kv[l].copy_(qkv[:, dt:])
             ops.gemm_nt(att, blk.w_out, xm, EPI_BIAS_RESID, bias=blk.b_out, resid=x)
             ops.layernorm_fwd(xm, blk.ln2_w, blk.ln2_b, h)
-            ops.gemm_nt(h, blk.w_fc, g, EPI_BIAS_QGELU, bias=blk.b_fc, aux=None, aux_row0=Rf)
-            ops.gemm_nt(g, blk.w_proj, x, EPI_BIAS_RESID, bias=blk.b_proj, resid=xm)
+            ops.gemm_nt(h, blk.w_fc, g, EPI_BIAS_QGELU, bias=blk.b_fc, aux=None if aux is None else aux[l],
+                        aux_row0=R if aux is None else 0)
+            ops.gemm_nt(g, blk.w_proj, xs[l + 1], EPI_BIAS_RESID, bias=blk.b_proj, resid=xm)
+
+    def _text_blocks_plain(self, x: torch.Tensor, len_i32: torch.Tensor, n: int, L: int,
+                           kv: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+        """The text blocks over the first L positions of n prompts, x [n * L, d_t] fp32 updated in place to the last
+        block's output, under the causal AND col < len mask.  kv: per layer [n * L, 2 d_t], receives that layer's K | V."""
+        dt, H, Lt = self.cfg.d_t, self.cfg.heads_t, len(self.txt)
+        a = lambda w: torch.empty(n * L, w, dtype=self.act, device=self.dev)
+        attn = lambda q, k, v, out: ops.text_attn_fwd(q, k, v, out, len_i32, n, L, L, H, causal=True, scale=SCALE)
+        self._text_blocks([x] * (Lt + 1), [torch.empty_like(x)] * Lt, [a(3 * dt)] * Lt, a(dt), a(dt), a(4 * dt), attn, kv)
         return x
 
+    def _text_eot_tail(self, x: torch.Tensor, rows: torch.Tensor, x_eot: torch.Tensor, y_eot: torch.Tensor,
+                       out: torch.Tensor) -> torch.Tensor:
+        """out [n, e] fp32 = text_projection of ln_final of rows `rows` [n] (the EOT tokens) of x (clip/model.py:352-354);
+        x_eot [n, d_t] fp32 keeps the gathered rows (the backward re-reads them), y_eot [n, d_t] is workspace."""
+        torch.index_select(x, 0, rows, out=x_eot)
+        ops.layernorm_fwd(x_eot, self.ln_final[0], self.ln_final[1], y_eot)
+        return ops.gemm_nt(y_eot, self.text_proj_t, out, EPI_NONE)
+
     def _text_eot_features(self, x: torch.Tensor, len_i32: torch.Tensor, n: int, L: int, out: torch.Tensor) -> torch.Tensor:
-        """out [n, e] fp32 = text_projection of ln_final of every prompt's EOT row of x [n * L, d_t] (clip/model.py:352-354)."""
+        """out [n, e] fp32 = `_text_eot_tail` of every prompt's EOT row of x [n * L, d_t]."""
         rows = torch.arange(n, device=self.dev) * L + (len_i32.to(torch.int64) - 1)            # EOT positions
-        eot = x.index_select(0, rows).contiguous()
-        y = torch.empty(n, self.cfg.d_t, dtype=self.act, device=self.dev)
-        ops.layernorm_fwd(eot, self.ln_final[0], self.ln_final[1], y)
-        return ops.gemm_nt(y, self.text_proj_t, out, EPI_NONE)
+        return self._text_eot_tail(x, rows, torch.empty(n, self.cfg.d_t, dtype=torch.float32, device=self.dev),
+                                   torch.empty(n, self.cfg.d_t, dtype=self.act, device=self.dev), out)
 
     def _text_tables(self):
         """(token_embedding.weight [vocab, d_t], positional_embedding [context, d_t]) as fp32 device tensors for
