@@ -525,6 +525,38 @@ int rpo_lp_head_fwd_bwd_grouped(const float* img_f, const float* params, int64_t
                                 const int64_t* label, float scale_exp, float* z, float* logits, float* loss,
                                 float* grads, int S, int B, int C, int e, float* workspace, void* stream);
 
+/* (ABI 8 additions) CoCoOp for S independent runs ("members") of b images each in the launches of one (rpo_amd/coop_multi.py;
+ * rpo_amd/csrc/cocoop_sets.hip).  Member s owns row s of params / grads [S, set_stride], fp32:
+ *   [ctx (n_ctx * d) | w1 (h * e) | b1 (h) | w2 (d * h) | b2 (d)]
+ * -- the flat buffer of a standalone run, so a row can be copied into one and back.  Floats of a row past that length (the
+ * padding up to set_stride) are never read or written.  Images, and everything per image, are member-major: image i of
+ * member s is row s * b + i.
+ *   rpo_metanet_fwd_sets      bias[s b + i] = linear2_s(relu(linear1_s(f / |f|))) for img_f [S*b, e]; f_norm [S*b, e] and
+ *                             hidden [S*b, h] are kept for the backward.  One workgroup per (member, image); per image the
+ *                             bits of rpo_metanet_fwd called with member s's four tensors.
+ *   rpo_cocoop_shift_sets     c_shift[s b + i, r, :] = ctx_s[r, :] + bias[s b + i, :]   (c_shift [S*b, n_ctx, d])
+ *   rpo_cocoop_grad_tail_sets per member, sums in ascending i, then r, starting from their first term:
+ *                               row s of grads, ctx part = (1 / b) sum_i d_shift[s b + i]          (d_shift [S*b, n_ctx, d])
+ *                               d_bias[s b + i]          = (1 / b) sum_r d_shift[s b + i, r]       (d_bias [S*b, d])
+ *                               loss[s]                  = (1 / b) sum_i loss_img[s b + i]
+ *                             b = 1: d_shift and loss_img themselves.  Writes nothing else of grads.
+ *   rpo_metanet_bwd_sets      the member is a grid dimension; per member the bits of rpo_metanet_bwd(B = b) on its slices
+ *                             of d_bias / f_norm / hidden with its w2, written into row s of grads at the four offsets
+ *                             (the ctx part is not touched).
+ * One launch each, fixed summation orders, no atomics, no allocation, capturable in a HIP graph.  A NULL pointer or a
+ * non-positive n_ctx / e / h / d: RPO_E_BADARG.  S outside 1 .. 1024, b < 1, set_stride below the floats of a row the call
+ * touches (the meta-net pair: the row length; the other two: n_ctx * d), or (e + h) * 4 (forward) / b * h * 4 (backward)
+ * bytes beyond 48 KB of LDS: RPO_E_SHAPE.  set_stride % 4 != 0, or params / grads off the 16-byte grid: RPO_E_ALIGN.  An
+ * error launches nothing. */
+int rpo_metanet_fwd_sets(const float* img_f, const float* params, int64_t set_stride, int n_ctx, float* f_norm,
+                         float* hidden, float* bias, int S, int b, int e, int h, int d, void* stream);
+int rpo_cocoop_shift_sets(const float* params, int64_t set_stride, const float* bias, float* c_shift, int S, int b,
+                          int n_ctx, int d, void* stream);
+int rpo_cocoop_grad_tail_sets(const float* d_shift, const float* loss_img, float* grads, int64_t set_stride, float* d_bias,
+                              float* loss, int S, int b, int n_ctx, int d, void* stream);
+int rpo_metanet_bwd_sets(const float* d_bias, const float* f_norm, const float* hidden, const float* params, float* grads,
+                         int64_t set_stride, int n_ctx, int S, int b, int e, int h, int d, void* stream);
+
 /* (ABI 8 addition) Prompt ensembling (trainers/zsclip.py:85-96, ZeroshotCLIP2): the classifier is the normalised mean over
  * the templates of the normalised text features.  rpo_amd/csrc/ensemble.hip.
  *   accumulate: acc[c,:] = (first ? 0 : acc[c,:]) + sum_t feat[t,c,:] / ||feat[t,c,:]||_2     t = 0 .. T-1, ascending

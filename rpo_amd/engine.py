@@ -33,6 +33,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RESID, EPI_LN_BIAS, EPI_LN
 from .class_set import ClassSetEngineMixin
 from .config import ATTN_LDS_TOKENS, RPOConfig
 from .engine_cocoop_eval import ConditionalEvalEngineMixin
+from .engine_cocoop_multi import CocoopMultiEngineMixin
 from .engine_coop import CoopEngineMixin
 from .engine_coop_prefix import PrefixTrainEngineMixin
 from .engine_lp import LpEngineMixin
@@ -75,8 +76,8 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, PrefixTrainEngineMixin, ConditionalEvalEngineMixin, LpEngineMixin, RnEngineMixin,
-             MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin, ClassSetEngineMixin):
+class Engine(CoopEngineMixin, PrefixTrainEngineMixin, ConditionalEvalEngineMixin, CocoopMultiEngineMixin, LpEngineMixin,
+             RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin, ClassSetEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under

@@ -49,14 +49,15 @@ def seeded_prompts(state_dict: Dict[str, np.ndarray], cfg: RPOConfig, seeds: Seq
     return out
 
 
-def member_batches(set_sizes: Sequence[int], batch_size: int, generators: Sequence[Optional[torch.Generator]]) -> List[list]:
+def member_batches(set_sizes: Sequence[int], batch_size: int, generators: Sequence[Optional[torch.Generator]],
+                   who: str = "RPOMulti") -> List[list]:
     """Per member, the index batches of one epoch: `epoch_indices` with that member's set size and generator, i.e. exactly
     the order a standalone run sees.  Every member must get the same number of batches (a step advances all of them)."""
     if len(set_sizes) != len(generators):
         raise ValueError(f"{len(set_sizes)} image sets for {len(generators)} generators")
     nbs = [n // batch_size for n in set_sizes]
     if any(nb != nbs[0] for nb in nbs) or nbs[0] == 0:
-        raise ValueError(f"RPOMulti.run_epoch: the members' sets have {list(set_sizes)} images = {nbs} batches of {batch_size}; "
+        raise ValueError(f"{who}.run_epoch: the members' sets have {list(set_sizes)} images = {nbs} batches of {batch_size}; "
                          "every member must have the same, non-zero number of batches per epoch (a step advances all members)")
     return [epoch_indices(n, batch_size, g) for n, g in zip(set_sizes, generators)]
 
@@ -88,7 +89,88 @@ def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig)
     return flat, ck
 
 
-class RPOMulti(EvalMixin):
+class MemberLoopMixin:
+    """The member-major batch and epoch loop of a trainer that advances S members of `batch_size` images by one
+    `step_async(image [S*B], label [S*B])` (`RPOMulti`, `RPOSweep`, `CoCoOpMulti`): needs `n_runs`, `batch_size`, `num_batches`,
+    `batch_idx`, `cfg`, `device`, `_image` (the step's own [S*B] image buffer), `update_lr`."""
+
+    _loop_name = "RPOMulti"                             # who the refusals of the loop name
+
+    def parse_batch_train(self, batches: Sequence[dict]):
+        """S Dassl-style batches {"img": float [B, 3, H, W], "label": [B]} -> one member-major device batch."""
+        if len(batches) != self.n_runs:
+            raise ValueError(f"{len(batches)} batches for {self.n_runs} members")
+        n = self.cfg.n_cls
+        for s, b in enumerate(batches):
+            lab = torch.as_tensor(b["label"])
+            if not lab.is_cuda and lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= n):
+                raise IndexError(f"member {s}: target out of bounds (n_cls = {n}; labels must be renumbered after the "
+                                 "base/new split)")
+        img = torch.cat([torch.as_tensor(b["img"]).to(self.device, dtype=torch.float32) for b in batches]).contiguous()
+        label = torch.cat([torch.as_tensor(b["label"]).to(self.device, dtype=torch.int64) for b in batches]).contiguous()
+        return img, label
+
+    def _loop_advance(self) -> None:
+        if (self.batch_idx + 1) == self.num_batches:
+            self.update_lr()
+            self.batch_idx = 0
+        else:
+            self.batch_idx += 1
+
+    # ------------------------------------------------------------------ the epoch loop
+    def run_epoch(self, image_sets, generators: Optional[Sequence[Optional[torch.Generator]]] = None,
+                  plans=None) -> Dict[str, object]:
+        """One epoch of every member over its own resident set (`image_sets`: one `DeviceImageSet` per member, or one
+        shared set) in the order `epoch_indices` gives a standalone run with that member's generator.  `plans`: per member,
+        per batch, the `SamplePlan`s of its images (default: drawn by the transform, member by member within a step).
+        As `loop.LoopMixin.run_epoch`: no device scalar is read, and batch t + 1 is in its buffer before step t is
+        enqueued.  Returns {"loss": float32 [num_batches, S] on the device, "indices": per member, the batches}."""
+        S, B = self.n_runs, self.batch_size
+        sets = list(image_sets) if isinstance(image_sets, (list, tuple)) else [image_sets] * S
+        if len(sets) != S:
+            raise ValueError(f"{len(sets)} image sets for {S} members")
+        gens = list(generators) if generators is not None else [None] * S
+        batches = member_batches([len(ds) for ds in sets], B, gens, self._loop_name)
+        nb = len(batches[0])
+        if nb != self.num_batches:
+            raise ValueError(f"the sets give {nb} batches of {B} per member; the trainer was built with num_batches = "
+                             f"{self.num_batches} (its LR schedule counts on it)")
+        if self.batch_idx != 0:
+            raise RuntimeError("run_epoch starts at an epoch boundary (batch_idx != 0: forward_backward is mid-epoch)")
+        for ds in set(sets):
+            ds.check_labels(self.cfg.n_cls)
+        with torch.cuda.device(self.device):
+            if getattr(self, "_loop_bufs", None) is None:
+                self._loop_bufs = [torch.zeros_like(self._image) for _ in range(2)]
+            # one transform (= one pair of descriptor slots) per MEMBER, also when members share a set: a slot is reused
+            # only after its call of two turns ago has been read, so with one transform for several members the host would
+            # wait for the step before inside every fill and the one-batch lookahead would be gone.  (A shared set's spill
+            # tail is guarded by the set's own events and every call is on one stream.)  The transforms hold no set.
+            if getattr(self, "_member_tfs", None) is None:
+                from .input_pipeline import DeviceTransform, InputConfig
+                icfg = InputConfig(SIZE=(self.cfg.image_size, self.cfg.image_size))
+                self._member_tfs = [DeviceTransform(icfg, True, self.device, B, max_image_bytes=16) for _ in range(S)]
+            tfs = self._member_tfs
+            labels = torch.stack([ds.labels_dev[torch.tensor(bt, dtype=torch.int64).to(self.device)]
+                                  for ds, bt in zip(sets, batches)], 1).reshape(nb, S * B)      # [nb, S*B] member-major
+            losses = torch.zeros(nb, S, dtype=torch.float32, device=self.device)
+
+            def fill(t, out):
+                for s in range(S):
+                    tfs[s].from_set(sets[s], batches[s][t], None if plans is None else plans[s][t], out=out[s * B:(s + 1) * B])
+
+            fill(0, self._loop_bufs[0])
+            for t in range(nb):
+                cur = self._loop_bufs[t & 1]
+                if t + 1 < nb:
+                    fill(t + 1, self._loop_bufs[(t + 1) & 1])
+                loss = self.step_async(cur, labels[t])
+                losses[t].copy_(loss, non_blocking=True)
+                self._loop_advance()
+        return {"loss": losses, "indices": batches}
+
+
+class RPOMulti(MemberLoopMixin, EvalMixin):
     _found_inf = None                                   # amp is refused here; `RPOSweep` has one verdict per member
     _features_why_not = ("RPO's image rows read its members' prompts, so no image feature outlives a step; what an image set "
                          "can cache for RPO is the frozen rows' K / V: FrozenImageKV.build(engine, image_set) and "
@@ -203,20 +285,6 @@ class RPOMulti(EvalMixin):
         self.engine.text_f_version = -1
         return self.engine.m_loss
 
-    def parse_batch_train(self, batches: Sequence[dict]):
-        """S Dassl-style batches {"img": float [B, 3, H, W], "label": [B]} -> one member-major device batch."""
-        if len(batches) != self.n_runs:
-            raise ValueError(f"{len(batches)} batches for {self.n_runs} members")
-        n = self.cfg.n_cls
-        for s, b in enumerate(batches):
-            lab = torch.as_tensor(b["label"])
-            if not lab.is_cuda and lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= n):
-                raise IndexError(f"member {s}: target out of bounds (n_cls = {n}; labels must be renumbered after the "
-                                 "base/new split)")
-        img = torch.cat([torch.as_tensor(b["img"]).to(self.device, dtype=torch.float32) for b in batches]).contiguous()
-        label = torch.cat([torch.as_tensor(b["label"]).to(self.device, dtype=torch.int64) for b in batches]).contiguous()
-        return img, label
-
     def forward_backward(self, batches: Sequence[dict]) -> List[Dict[str, float]]:
         """trainers/rpo.py:290-316 for every member: a list of S batches in, a list of S {"loss", "acc"} out."""
         S, B = self.n_runs, self.batch_size
@@ -233,65 +301,6 @@ class RPOMulti(EvalMixin):
         self.epoch += 1
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
         self._opt.set_epoch(self.epoch)
-
-    def _loop_advance(self) -> None:
-        if (self.batch_idx + 1) == self.num_batches:
-            self.update_lr()
-            self.batch_idx = 0
-        else:
-            self.batch_idx += 1
-
-    # ------------------------------------------------------------------ the epoch loop
-    def run_epoch(self, image_sets, generators: Optional[Sequence[Optional[torch.Generator]]] = None,
-                  plans=None) -> Dict[str, object]:
-        """One epoch of every member over its own resident set (`image_sets`: one `DeviceImageSet` per member, or one
-        shared set) in the order `epoch_indices` gives a standalone run with that member's generator.  `plans`: per member,
-        per batch, the `SamplePlan`s of its images (default: drawn by the transform, member by member within a step).
-        As `loop.LoopMixin.run_epoch`: no device scalar is read, and batch t + 1 is in its buffer before step t is
-        enqueued.  Returns {"loss": float32 [num_batches, S] on the device, "indices": per member, the batches}."""
-        S, B = self.n_runs, self.batch_size
-        sets = list(image_sets) if isinstance(image_sets, (list, tuple)) else [image_sets] * S
-        if len(sets) != S:
-            raise ValueError(f"{len(sets)} image sets for {S} members")
-        gens = list(generators) if generators is not None else [None] * S
-        batches = member_batches([len(ds) for ds in sets], B, gens)
-        nb = len(batches[0])
-        if nb != self.num_batches:
-            raise ValueError(f"the sets give {nb} batches of {B} per member; the trainer was built with num_batches = "
-                             f"{self.num_batches} (its LR schedule counts on it)")
-        if self.batch_idx != 0:
-            raise RuntimeError("run_epoch starts at an epoch boundary (batch_idx != 0: forward_backward is mid-epoch)")
-        for ds in set(sets):
-            ds.check_labels(self.cfg.n_cls)
-        with torch.cuda.device(self.device):
-            if getattr(self, "_loop_bufs", None) is None:
-                self._loop_bufs = [torch.zeros_like(self._image) for _ in range(2)]
-            # one transform (= one pair of descriptor slots) per MEMBER, also when members share a set: a slot is reused
-            # only after its call of two turns ago has been read, so with one transform for several members the host would
-            # wait for the step before inside every fill and the one-batch lookahead would be gone.  (A shared set's spill
-            # tail is guarded by the set's own events and every call is on one stream.)  The transforms hold no set.
-            if getattr(self, "_member_tfs", None) is None:
-                from .input_pipeline import DeviceTransform, InputConfig
-                icfg = InputConfig(SIZE=(self.cfg.image_size, self.cfg.image_size))
-                self._member_tfs = [DeviceTransform(icfg, True, self.device, B, max_image_bytes=16) for _ in range(S)]
-            tfs = self._member_tfs
-            labels = torch.stack([ds.labels_dev[torch.tensor(bt, dtype=torch.int64).to(self.device)]
-                                  for ds, bt in zip(sets, batches)], 1).reshape(nb, S * B)      # [nb, S*B] member-major
-            losses = torch.zeros(nb, S, dtype=torch.float32, device=self.device)
-
-            def fill(t, out):
-                for s in range(S):
-                    tfs[s].from_set(sets[s], batches[s][t], None if plans is None else plans[s][t], out=out[s * B:(s + 1) * B])
-
-            fill(0, self._loop_bufs[0])
-            for t in range(nb):
-                cur = self._loop_bufs[t & 1]
-                if t + 1 < nb:
-                    fill(t + 1, self._loop_bufs[(t + 1) & 1])
-                loss = self.step_async(cur, labels[t])
-                losses[t].copy_(loss, non_blocking=True)
-                self._loop_advance()
-        return {"loss": losses, "indices": batches}
 
     # ------------------------------------------------------------------ evaluation: the single-run path, one member
     def _select(self, member: int) -> None:

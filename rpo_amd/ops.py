@@ -750,6 +750,64 @@ def metanet_bwd(d_bias, f_norm, hidden, w2, g_w1, g_b1, g_w2, g_b2):
                                       _stream()), "rpo_metanet_bwd")
 
 
+def _sets_rows(params, what: str = "params"):
+    """(S, row stride) of a members' buffer [S, stride] whose rows the *_sets entry points address by one stride."""
+    assert params.dim() == 2 and params.dtype == torch.float32 and params.stride(1) == 1, f"{what} is fp32 [S, set_stride]"
+    return params.shape[0], params.stride(0)
+
+
+def metanet_fwd_sets(img_f, params, n_ctx: int, f_norm, hidden, bias, b: int):
+    """The meta-net of S members on b images each (include/rpo_amd.h rpo_metanet_fwd_sets): img_f [S*b, e] member-major,
+    params [S, set_stride] with row s = [ctx | w1 | b1 | w2 | b2]; writes f_norm [S*b, e], hidden [S*b, h], bias [S*b, d]."""
+    S, stride = _sets_rows(params)
+    SB, e = img_f.shape
+    h, d = hidden.shape[1], bias.shape[1]
+    assert SB == S * b and f_norm.shape == (SB, e) and hidden.shape == (SB, h) and bias.shape == (SB, d)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (img_f, f_norm, hidden, bias))
+    check(_lib.load().rpo_metanet_fwd_sets(img_f.data_ptr(), params.data_ptr(), stride, n_ctx, f_norm.data_ptr(),
+                                           hidden.data_ptr(), bias.data_ptr(), S, b, e, h, d, _stream()),
+          "rpo_metanet_fwd_sets")
+    return bias
+
+
+def cocoop_shift_sets(params, bias, c_shift, b: int):
+    """c_shift[s b + i, r, :] = ctx_s[r, :] + bias[s b + i, :] in one launch (rpo_cocoop_shift_sets): params [S, set_stride],
+    bias [S*b, d], c_shift [S*b, n_ctx, d]."""
+    S, stride = _sets_rows(params)
+    SB, n_ctx, d = c_shift.shape
+    assert SB == S * b and bias.shape == (SB, d)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (bias, c_shift))
+    check(_lib.load().rpo_cocoop_shift_sets(params.data_ptr(), stride, bias.data_ptr(), c_shift.data_ptr(), S, b, n_ctx, d,
+                                            _stream()), "rpo_cocoop_shift_sets")
+    return c_shift
+
+
+def cocoop_grad_tail_sets(d_shift, loss_img, grads, d_bias, loss, b: int):
+    """The members' gradient tail in one launch (rpo_cocoop_grad_tail_sets): d_shift [S*b, n_ctx, d], loss_img [S*b] ->
+    the ctx part of row s of grads [S, set_stride], d_bias [S*b, d], loss [S] (means over the member's b images)."""
+    S, stride = _sets_rows(grads, "grads")
+    SB, n_ctx, d = d_shift.shape
+    assert SB == S * b and loss_img.numel() == SB and d_bias.shape == (SB, d) and loss.numel() == S
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (d_shift, loss_img, d_bias, loss))
+    check(_lib.load().rpo_cocoop_grad_tail_sets(d_shift.data_ptr(), loss_img.data_ptr(), grads.data_ptr(), stride,
+                                                d_bias.data_ptr(), loss.data_ptr(), S, b, n_ctx, d, _stream()),
+          "rpo_cocoop_grad_tail_sets")
+
+
+def metanet_bwd_sets(d_bias, f_norm, hidden, params, grads, n_ctx: int, b: int):
+    """The meta-net backward of S members (rpo_metanet_bwd_sets): per member rpo_metanet_bwd(B = b) on its slices, written
+    into row s of grads [S, set_stride] (the layout and stride of params)."""
+    S, stride = _sets_rows(params)
+    SB, d = d_bias.shape
+    e, h = f_norm.shape[1], hidden.shape[1]
+    assert SB == S * b and f_norm.shape == (SB, e) and hidden.shape == (SB, h)
+    assert _sets_rows(grads, "grads") == (S, stride), "grads has the layout of params"
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (d_bias, f_norm, hidden))
+    check(_lib.load().rpo_metanet_bwd_sets(d_bias.data_ptr(), f_norm.data_ptr(), hidden.data_ptr(), params.data_ptr(),
+                                           grads.data_ptr(), stride, n_ctx, S, b, e, h, d, _stream()),
+          "rpo_metanet_bwd_sets")
+
+
 def sgd_step(p, g, buf, lr: float, momentum: float, wd: float, grad_scale: float, first_step: bool):
     assert p.is_contiguous() and g.is_contiguous() and buf.is_contiguous()
     check(_lib.load().rpo_sgd_step(p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), lr, momentum, wd,
