@@ -557,6 +557,33 @@ int rpo_cocoop_grad_tail_sets(const float* d_shift, const float* loss_img, float
 int rpo_metanet_bwd_sets(const float* d_bias, const float* f_norm, const float* hidden, const float* params, float* grads,
                          int64_t set_stride, int n_ctx, int S, int b, int e, int h, int d, void* stream);
 
+/* (ABI 8 additions) CoOp for S independent runs ("members") with their OWN number of context vectors on one dense text pass
+ * (rpo_amd/coop_sweep.py; rpo_amd/csrc/coop_sets.hip).  The prompts are those of n_max placeholders; member s has
+ * n_s = n_ctx_members[s] context vectors (int32 [S] on the DEVICE, 1 <= n_s <= n_max; a value outside [0, n_max] is clamped
+ * into it, so nothing is read or written out of bounds), delta = n_max - n_s, and owns row s of params / grads
+ * [S, set_stride], fp32: its context is the first n_s * d floats of the row.  Rows of the pass are member-major: row
+ * ((s * n_cls + c) * L + p) is position p of class c of member s.
+ *   rpo_coop_fill_sets      x0[(s, c, p), :] from tok [n_cls * L, d] (the token embeddings of the n_max prompts, no
+ *                           positional part) and pos [L, d]:
+ *                             p = 0                     tok[c, 0] + pos[0]
+ *                             1 <= p <= n_s             params[s, (p - 1) * d + :] + pos[p]
+ *                             p > n_s, p + delta < L    tok[c, p + delta] + pos[p]
+ *                             otherwise                 pos[p]
+ *                           One fp32 add per element: the host's float32 composition, bit for bit.
+ *   rpo_coop_ctx_grad_sets  grads[s, r * d + j] = the sum over the classes c of dx[(s, c, 1 + r), j] for r < n_s, IN THE
+ *                           ORDER of rpo_reduce_groups(groups = n_cls, rows = n_s) (one thread per element below 64 classes,
+ *                           eight partial sums per element from 64 on), read from dx [S * n_cls * L, d] in place; the
+ *                           entries [n_s * d, n_max * d) of the row are written as exact zeros.
+ * Floats of a row past n_max * d (the padding up to set_stride) are never read or written.  One launch each, no atomics, no
+ * allocation, capturable in a HIP graph.  A NULL pointer or a non-positive n_cls / L / d: RPO_E_BADARG.  S outside 1 .. 1024,
+ * n_max < 1, n_max + 1 > L, set_stride < n_max * d, S * n_cls * L beyond 2^31 - 1 (and for the fill d % 4 != 0):
+ * RPO_E_SHAPE.  set_stride % 4 != 0, or params / grads (for the fill also tok, pos, x0) off the 16-byte grid: RPO_E_ALIGN.
+ * An error launches nothing. */
+int rpo_coop_fill_sets(const float* tok, const float* pos, const float* params, int64_t set_stride,
+                       const int32_t* n_ctx_members, float* x0, int S, int n_cls, int L, int n_max, int d, void* stream);
+int rpo_coop_ctx_grad_sets(const float* dx, float* grads, int64_t set_stride, const int32_t* n_ctx_members, int S, int n_cls,
+                           int L, int n_max, int d, void* stream);
+
 /* (ABI 8 addition) Prompt ensembling (trainers/zsclip.py:85-96, ZeroshotCLIP2): the classifier is the normalised mean over
  * the templates of the normalised text features.  rpo_amd/csrc/ensemble.hip.
  *   accumulate: acc[c,:] = (first ? 0 : acc[c,:]) + sum_t feat[t,c,:] / ||feat[t,c,:]||_2     t = 0 .. T-1, ascending

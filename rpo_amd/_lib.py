@@ -187,6 +187,8 @@ SIGNATURES = {
     "rpo_cocoop_shift_sets": (c_i32, [c_vp, c_i64, c_vp, c_vp] + [c_i32] * 4 + [c_vp]),
     "rpo_cocoop_grad_tail_sets": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp] + [c_i32] * 4 + [c_vp]),
     "rpo_metanet_bwd_sets": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64] + [c_i32] * 6 + [c_vp]),
+    "rpo_coop_fill_sets": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp] + [c_i32] * 5 + [c_vp]),
+    "rpo_coop_ctx_grad_sets": (c_i32, [c_vp, c_vp, c_i64, c_vp] + [c_i32] * 5 + [c_vp]),
     "rpo_text_ensemble_accumulate": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "rpo_text_ensemble_finish": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "rpo_eval_accumulate": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

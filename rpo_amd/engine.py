@@ -36,6 +36,7 @@ from .engine_cocoop_eval import ConditionalEvalEngineMixin
 from .engine_cocoop_multi import CocoopMultiEngineMixin
 from .engine_coop import CoopEngineMixin
 from .engine_coop_prefix import PrefixTrainEngineMixin
+from .engine_coop_sweep import CoopSweepEngineMixin
 from .engine_lp import LpEngineMixin
 from .engine_multi import MultiEngineMixin
 from .engine_prompt_rows import PromptRowsEngineMixin
@@ -76,8 +77,8 @@ class _Block:
     w_fc_ln: Optional[torch.Tensor] = None; s_fc: Optional[torch.Tensor] = None; b_fc_ln: Optional[torch.Tensor] = None
 
 
-class Engine(CoopEngineMixin, PrefixTrainEngineMixin, ConditionalEvalEngineMixin, CocoopMultiEngineMixin, LpEngineMixin,
-             RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin, ClassSetEngineMixin):
+class Engine(CoopEngineMixin, PrefixTrainEngineMixin, ConditionalEvalEngineMixin, CocoopMultiEngineMixin, CoopSweepEngineMixin,
+             LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin, ClassSetEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under

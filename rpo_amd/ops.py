@@ -808,6 +808,33 @@ def metanet_bwd_sets(d_bias, f_norm, hidden, params, grads, n_ctx: int, b: int):
           "rpo_metanet_bwd_sets")
 
 
+def coop_fill_sets(tok, pos, params, n_ctx_members, x0, n_cls: int, L: int, n_max: int):
+    """The input rows of a dense text pass over S CoOp members with their own n_ctx (include/rpo_amd.h rpo_coop_fill_sets):
+    tok [n_cls * L, d], pos [L, d], params [S, set_stride], n_ctx_members int32 [S] on the device -> x0 [S * n_cls * L, d]."""
+    S, stride = _sets_rows(params)
+    d = tok.shape[1]
+    assert tok.shape == (n_cls * L, d) and pos.shape == (L, d) and x0.shape == (S * n_cls * L, d)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (tok, pos, x0))
+    assert n_ctx_members.dtype == torch.int32 and n_ctx_members.is_cuda and n_ctx_members.numel() == S \
+        and n_ctx_members.is_contiguous()
+    check(_lib.load().rpo_coop_fill_sets(tok.data_ptr(), pos.data_ptr(), params.data_ptr(), stride, n_ctx_members.data_ptr(),
+                                         x0.data_ptr(), S, n_cls, L, n_max, d, _stream()), "rpo_coop_fill_sets")
+    return x0
+
+
+def coop_ctx_grad_sets(dx, grads, n_ctx_members, n_cls: int, L: int, n_max: int):
+    """The members' context gradients in one launch (rpo_coop_ctx_grad_sets): dx [S * n_cls * L, d] read in place -> the first
+    n_max * d floats of row s of grads [S, set_stride], in rpo_reduce_groups's summation order, the unused tail zeroed."""
+    S, stride = _sets_rows(grads, "grads")
+    d = dx.shape[1]
+    assert dx.shape == (S * n_cls * L, d) and dx.dtype == torch.float32 and dx.is_contiguous()
+    assert n_ctx_members.dtype == torch.int32 and n_ctx_members.is_cuda and n_ctx_members.numel() == S \
+        and n_ctx_members.is_contiguous()
+    check(_lib.load().rpo_coop_ctx_grad_sets(dx.data_ptr(), grads.data_ptr(), stride, n_ctx_members.data_ptr(), S, n_cls, L,
+                                             n_max, d, _stream()), "rpo_coop_ctx_grad_sets")
+    return grads
+
+
 def sgd_step(p, g, buf, lr: float, momentum: float, wd: float, grad_scale: float, first_step: bool):
     assert p.is_contiguous() and g.is_contiguous() and buf.is_contiguous()
     check(_lib.load().rpo_sgd_step(p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), lr, momentum, wd,
