@@ -243,15 +243,6 @@ class CoOp(LoopMixin):
         self._graph = None
         return self.epoch
 
-    def parse_batch_train(self, batch):
-        img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        label = torch.as_tensor(batch["label"])
-        if not label.is_cuda:
-            lo, hi = int(label.min()), int(label.max())
-            if lo < 0 or hi >= self.cfg.n_cls:
-                raise IndexError(f"Target {hi if hi >= self.cfg.n_cls else lo} is out of bounds (n_cls = {self.cfg.n_cls})")
-        return img, label.to(self.device, dtype=torch.int64, non_blocking=True)
-
     def forward_backward(self, batch) -> Dict[str, float]:
         eng = self.engine
         with torch.cuda.device(self.device):

@@ -16,12 +16,12 @@ member's row into the engine's single-run parameters.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import members as _members
 from . import optim as _optim
 from .config import RPOConfig
 from .coop import CoCoOp, CoCoOpCustomCLIP, CoCoOpPromptLearner, _init_ctx
@@ -29,8 +29,7 @@ from .custom_clip import config_from_state_dict
 from .engine_cocoop_multi import MAX_REPLICAS
 from .evaluator import Classification
 from .loop import EvalMixin
-from .multi import MemberLoopMixin
-from .trainer import OptimConfig, load_checkpoint_file, lr_at_epoch, write_checkpoint
+from .trainer import OptimConfig, lr_at_epoch
 
 META_KEYS = ("w1", "b1", "w2", "b2")
 PARAM_NAMES = ("ctx", "meta_net.linear1.weight", "meta_net.linear1.bias", "meta_net.linear2.weight", "meta_net.linear2.bias")
@@ -45,19 +44,11 @@ def check_members(members: Sequence[dict]) -> List[dict]:
     out = []
     for s, m in enumerate(members):
         m = dict(m)
-        unknown = set(m) - {"seed", "ctx", "meta", "ctx_init", "optim"}
-        if unknown:
-            raise ValueError(f"CoCoOpMulti: member {s} has unknown keys {sorted(unknown)}")
-        seeded = m.get("seed") is not None
-        given = m.get("ctx") is not None or m.get("meta") is not None
-        if seeded == given:
-            raise ValueError(f"CoCoOpMulti: member {s} must have exactly one of seed=... or (ctx=..., meta=...); it has "
-                             + ("both" if seeded else "neither"))
+        given = _members.check_member_dict("CoCoOpMulti", s, m, ("seed", "ctx", "meta", "ctx_init", "optim"), ("ctx", "meta"),
+                                           "(ctx=..., meta=...)")
         if given and (m.get("ctx") is None or m.get("meta") is None):
             raise ValueError(f"CoCoOpMulti: member {s} gives its tensors: both ctx [n_ctx, d_t] and meta "
                              f"{{{', '.join(META_KEYS)}}} are needed")
-        if given and m.get("ctx_init") is not None:
-            raise ValueError(f"CoCoOpMulti: member {s}: ctx_init initialises a seeded member; this one brings its ctx")
         out.append(m)
     return out
 
@@ -93,7 +84,8 @@ class _MemberCLIP(CoCoOpCustomCLIP):
         self.tokenized_prompts = tokens
 
 
-class CoCoOpMulti(MemberLoopMixin, EvalMixin):
+class CoCoOpMulti(_members.MemberCheckpointMixin, _members.MemberScheduleMixin, _members.MemberLoopMixin,
+                  EvalMixin):
     """S CoCoOp runs on one frozen CLIP, advanced by one step.
 
     members: per member dict(seed=int [, ctx_init=...]) or dict(ctx=[n_ctx, d_t], meta={w1, b1, w2, b2}), each with an
@@ -111,10 +103,8 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
                  use_graph: bool = False, amp: bool = False, shared_prefix: bool = False, cfg: Optional[RPOConfig] = None,
                  device: str | torch.device = "cuda:0", world_size: int = 1):
         # ---- refusals, before any device is touched
-        if world_size != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("CoCoOpMulti: world_size > 1 is not supported (data parallelism for this trainer is not "
-                                      "built: the members fill the step that data parallelism would split); run one "
-                                      "CoCoOpMulti per GPU with different members")
+        _members.refuse_world_size("CoCoOpMulti", world_size, "data parallelism for this trainer is not built: the members "
+                                   "fill the step that data parallelism would split")
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])
@@ -130,14 +120,7 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
             raise ValueError(f"CoCoOpMulti: S * b = {S} * {b} = {S * b} images per step; the text pass takes at most "
                              f"{MAX_REPLICAS} replicas (rpo_metanet_fwd's limit, DESIGN.md section 9p)")
         members = check_members(members)
-        for m in members:
-            m["optim"] = m.get("optim") or default_optim()
-            _optim.validate(m["optim"])                                  # (radam and the other refusals of optim.py)
-        self.optim_cfgs: List[OptimConfig] = [m["optim"] for m in members]
-        epochs = [oc.max_epoch for oc in self.optim_cfgs]
-        if any(ep != epochs[0] for ep in epochs):
-            raise ValueError(f"CoCoOpMulti: the members differ in max_epoch ({epochs}): one loop runs all members, and the "
-                             "schedules count on its length -- run schedules of different lengths as separate trainers")
+        self.optim_cfgs: List[OptimConfig] = _members.member_optim_configs("CoCoOpMulti", members, default_optim)
         # ---- the members' starting rows (host; a seed draws from torch's global generator as the standalone trainer does)
         emb = state_dict["token_embedding.weight"]
         starts = np.stack([member_start(m, cfg, tokens.shape[0], n_ctx, emb) for m in members])
@@ -167,14 +150,10 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
         self.model = _MemberCLIP(eng, cfg, self.n_ctx, emb, tokens)
 
     # ------------------------------------------------------------------ members' state
-    def _param_shapes(self):
+    def _param_shapes(self, member: int = 0):
         e, dt = self.cfg.embed, self.cfg.d_t
         h = e // 16
         return [(self.n_ctx, dt), (h, e), (h,), (dt, h), (dt,)]
-
-    def _check_member(self, member: int) -> None:
-        if not 0 <= member < self.n_runs:
-            raise IndexError(f"member {member} of {self.n_runs}")
 
     def named_parameters(self, member: int):
         """(name, device tensor) of member `member`'s trained tensors, in torch.optim's parameter order: views of its row."""
@@ -183,49 +162,18 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
         for name, k in zip(PARAM_NAMES, ("ctx",) + META_KEYS):
             yield name, views[k]
 
-    @property
-    def skipped_steps(self) -> List[int]:
-        """amp: per member, the steps skipped so far because its own gradients held Inf / NaN (one D2H read)."""
-        if self._found_inf is None:
-            return [0] * self.n_runs
-        return [int(v) for v in self._found_inf[:, 1].tolist()]
+    skipped_steps = property(_members.MemberScheduleMixin.skipped_steps)     # (a property here, a method on the other three)
 
-    # ------------------------------------------------------------------ the step
+    # ------------------------------------------------------------------ the step: `MemberLoopMixin.step_async` enqueues these
+    def _forward_backward(self, image: torch.Tensor, label: torch.Tensor) -> None:
+        self.engine.cocoop_multi_forward_backward(image, label)
+
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
         eng = self.engine
-        eng.cocoop_multi_forward_backward(image, label)
+        self._forward_backward(image, label)
         self._opt.step(eng.cm_params, eng.cm_grads, self._found_inf, first_step=(self._steps == 0))
 
-    def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-        """One optimisation step of every member, nothing synchronised: image [S*b, 3, H, W] and label [S*b], member-major
-        (member s owns rows [s b, (s+1) b)).  Returns loss [S] on the device.  With use_graph the whole step is ONE HIP
-        graph, captured after the first (eager) step; rates and step counters are device data, so a new epoch needs no
-        recapture."""
-        assert torch.cuda.current_device() == self.device.index, "set the trainer's device current (torch.cuda.set_device)"
-        SB = self.n_runs * self.batch_size
-        assert image.shape[0] == SB and label.shape == (SB,), f"step_async takes S * b = {SB} images, member-major"
-        if image.data_ptr() != self._image.data_ptr():
-            self._image.copy_(image, non_blocking=True)
-        self._label.copy_(label, non_blocking=True)
-        self._opt.set_epoch(self.epoch)                 # (in front of the step, on its stream; nothing within an epoch)
-        key = self._opt.graph_key()
-        if not self.use_graph or self._steps == 0:
-            self._enqueue(self._image, self._label)
-            self._warm = True
-        else:
-            if self._graph is None or self._graph[1] != key:
-                if not self._warm:                      # (a resumed run: an eager forward + backward first; it writes only
-                    self.engine.cocoop_multi_forward_backward(self._image, self._label)   # what the step overwrites)
-                    self._warm = True
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._enqueue(self._image, self._label)
-                self._graph = (g, key)                 # (capture does not execute: the replay below is this step)
-                self.captures += 1
-            self._graph[0].replay()
-        self._steps += 1
-        self._eval_member = None
+    def _loop_loss(self) -> torch.Tensor:
         return self.engine.cm_loss
 
     def forward_backward(self, batches: Sequence[dict]) -> List[Dict[str, float]]:
@@ -236,38 +184,15 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
         self._loop_advance()
         return [{"loss": float(v)} for v in loss]
 
-    def update_lr(self) -> None:
-        self.epoch += 1
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        self._opt.set_epoch(self.epoch)
-
     def train(self, image_sets, max_epoch: Optional[int] = None, val_set=None, directories: Optional[Sequence[str]] = None,
               generators: Optional[Sequence[Optional[torch.Generator]]] = None, test_batch_size: int = 100,
               verbose: bool = True) -> List[dict]:
         """`run_epoch` until `max_epoch` (default: the members' shared one).  After each epoch, with a validation set,
         `test_all(val_set)` and per member Dassl's `after_epoch` bookkeeping (a member that beats its own best is saved to
         its directory as `model-best`); without one the last epoch's models are saved.  One record per epoch."""
-        max_epoch = self.optim_cfgs[0].max_epoch if max_epoch is None else max_epoch
-        if directories is not None and len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        history = []
-        while self.epoch < max_epoch:
-            res = self.run_epoch(image_sets, generators)
-            rec = {"epoch": self.epoch, "loss": res["loss"].mean(0).tolist()}              # one read per epoch
-            if val_set is not None:
-                rec["val_acc"] = [r["accuracy"] for r in self.test_all(val_set, test_batch_size, verbose=False)]
-                if directories:
-                    for s, v in enumerate(rec["val_acc"]):
-                        if v > self.best_results[s]:
-                            self.best_results[s] = v
-                            self._save_member(s, directories[s], None, True, v)
-            elif directories and self.epoch == max_epoch:
-                self.save_model(directories)
-            if verbose:
-                print("epoch [{}/{}] loss ".format(self.epoch, max_epoch) + " ".join(f"{v:.4f}" for v in rec["loss"])
-                      + ("" if "val_acc" not in rec else " val_acc " + " ".join(f"{v:.2f}" for v in rec["val_acc"])))
-            history.append(rec)
-        return history
+        return self._train_members(
+            max_epoch, lambda i: self.run_epoch(image_sets, generators),
+            None if val_set is None else lambda: self.test_all(val_set, test_batch_size, verbose=False), directories, verbose)
 
     # ------------------------------------------------------------------ evaluation: the standalone path, one member
     def select_member(self, member: int) -> None:
@@ -338,54 +263,13 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
             out.append(res)
         return out
 
-    # ------------------------------------------------------------------ checkpoints: per member, a standalone CoCoOp's files
-    def checkpoint_dict(self, member: int, epoch: Optional[int] = None, val_result: Optional[float] = None) -> dict:
-        """The dict a standalone ``CoCoOp(optim=optim_cfgs[member])`` in this state pickles (``CoOp.save_model``)."""
-        self._check_member(member)
-        epoch = self.epoch if epoch is None else epoch
-        optimizer = self._opt.state_dict(self._param_shapes(), s=member, lr=self.lr[member], steps=self._steps)
-        state = {n: t.detach().cpu().clone() for n, t in self.named_parameters(member)}
+    # ------------------------------------------------------------------ checkpoints: `MemberCheckpointMixin`, CoCoOp's files
+    def _checkpoint_extra(self, member: int) -> Dict[str, torch.Tensor]:
         pl = self.model.prompt_learner
-        state["token_prefix"], state["token_suffix"] = pl.token_prefix.clone(), pl.token_suffix.clone()
-        return {"state_dict": state, "epoch": int(epoch), "optimizer": optimizer, "scheduler": {"last_epoch": int(epoch)},
-                "val_result": val_result, "steps": int(self._steps)}
-
-    def _save_member(self, member: int, directory: str, epoch, is_best: bool, val_result) -> str:
-        ck = self.checkpoint_dict(member, epoch, val_result)
-        return write_checkpoint(directory, ck, ck["epoch"], is_best)
-
-    def save_model(self, directories: Sequence[str], epoch: Optional[int] = None, is_best: bool = False,
-                   val_results: Optional[Sequence[Optional[float]]] = None) -> List[str]:
-        """Per member `<directories[s]>/prompt_learner/model.pth.tar-<epoch>` (+ `model-best.pth.tar`): ``CoCoOp``'s file."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        return [self._save_member(s, d, epoch, is_best, None if val_results is None else val_results[s])
-                for s, d in enumerate(directories)]
-
-    def _read(self, directories: Sequence[str], epoch: Optional[int]) -> List[dict]:
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        model_file = "model-best.pth.tar" if epoch is None else f"model.pth.tar-{epoch}"
-        got = []
-        for d in directories:
-            path = os.path.join(d, "prompt_learner", model_file)
-            if not os.path.exists(path):
-                raise FileNotFoundError(f'Model not found at "{path}"')
-            ck = load_checkpoint_file(path)
-            for name, sh in zip(PARAM_NAMES, self._param_shapes()):
-                if name not in ck["state_dict"]:
-                    raise ValueError(f"{path}: the checkpoint lacks {name}: it was not written by a CoCoOp trainer")
-                if tuple(torch.as_tensor(ck["state_dict"][name]).shape) != sh:
-                    raise ValueError(f"{path}: {name} has shape {tuple(torch.as_tensor(ck['state_dict'][name]).shape)}, "
-                                     f"this trainer {sh}")
-            got.append(ck)
-        return got
+        return {"token_prefix": pl.token_prefix.clone(), "token_suffix": pl.token_suffix.clone()}
 
     def _load_weights(self, got: Sequence[dict]) -> None:
-        with torch.no_grad(), torch.cuda.device(self.device):
-            for s, ck in enumerate(got):                                 # (token_prefix / token_suffix are dropped, as
-                for name, p in self.named_parameters(s):                 #  trainers/cocoop.py:304-309 drops them)
-                    p.copy_(torch.as_tensor(ck["state_dict"][name]).to(p.dtype).reshape(p.shape))
+        super()._load_weights(got)                   # (token_prefix / token_suffix are dropped, as trainers/cocoop.py:304-309)
         self._eval_member = None
 
     def load_model(self, directories: Sequence[str], epoch: Optional[int] = None) -> List[dict]:
@@ -399,28 +283,4 @@ class CoCoOpMulti(MemberLoopMixin, EvalMixin):
         """``CoCoOp.resume_model`` for every member: `load_model` plus the optimiser state, the epoch and the learning
         rates of the checkpoints.  One loop runs all members: files of different epochs are refused, and so is a mix of
         files with and without optimiser state.  Returns the epoch to continue from."""
-        got = self._read(directories, epoch)
-        epochs = [int(ck.get("epoch", 0)) for ck in got]
-        if any(ep != epochs[0] for ep in epochs):
-            raise ValueError(f"CoCoOpMulti.resume_model: the checkpoints are of epochs {epochs}; one loop runs all members")
-        has = [bool((ck.get("optimizer") or {}).get("state")) for ck in got]
-        if any(has) != all(has):
-            raise ValueError("CoCoOpMulti.resume_model: some checkpoints carry optimiser state and some do not (one step "
-                             "count covers every member)")
-        shapes = self._param_shapes()
-        with torch.no_grad(), torch.cuda.device(self.device):
-            for s, ck in enumerate(got):
-                if has[s] and not self._opt.load_state_dict(ck["optimizer"], shapes, s=s, steps=ck.get("steps", 1)):
-                    raise ValueError(f"CoCoOpMulti.resume_model: member {s}'s checkpoint holds optimiser state that is not "
-                                     f"{self.optim_cfgs[s].name}'s for these tensors")
-        self._load_weights(got)
-        if all(has):
-            self._steps = max(1, max(int(ck.get("steps", 1)) for ck in got))
-        self.epoch = epochs[0]
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        with torch.cuda.device(self.device):
-            self._opt.set_epoch(self.epoch)
-            if self._found_inf is not None:                              # the skip counts are the resumed run's own
-                self._found_inf.zero_()
-        self._graph = None
-        return self.epoch
+        return self._resume(directories, epoch, "resume_model")

@@ -17,19 +17,19 @@ Generic contexts in front of the class name only.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import members as _members
 from . import optim as _optim
 from .config import RPOConfig
 from .coop import _init_ctx
 from .custom_clip import config_from_state_dict
 from .engine_coop_sweep import MAX_MEMBERS, sweep_used
 from .loop import LoopMixin
-from .trainer import OptimConfig, load_checkpoint_file, lr_at_epoch, write_checkpoint
+from .trainer import OptimConfig, lr_at_epoch
 
 MEMBER_KEYS = {"seed", "ctx", "ctx_init", "n_ctx", "optim", "csc", "class_token_position"}
 
@@ -64,20 +64,12 @@ def check_members(members: Sequence[dict], n_max: int) -> List[dict]:
     out = []
     for s, m in enumerate(members):
         m = dict(m)
-        unknown = set(m) - MEMBER_KEYS
-        if unknown:
-            raise ValueError(f"CoOpSweep: member {s} has unknown keys {sorted(unknown)}")
+        _members.check_member_dict("CoOpSweep", s, m, MEMBER_KEYS, ("ctx",), "ctx=[n_ctx, d_t]")
         if m.get("csc") or m.get("class_token_position", "end") != "end":
             raise ValueError(f"CoOpSweep: member {s} asks for csc={m.get('csc', False)!r}, class_token_position="
                              f"{m.get('class_token_position', 'end')!r}: the members of a sweep have a generic context at "
                              "the front of the name only (csc=False, class_token_position='end'); run the other settings "
                              "as standalone CoOp trainers")
-        seeded, given = m.get("seed") is not None, m.get("ctx") is not None
-        if seeded == given:
-            raise ValueError(f"CoOpSweep: member {s} must have exactly one of seed=... or ctx=[n_ctx, d_t]; it has "
-                             + ("both" if seeded else "neither"))
-        if given and m.get("ctx_init") is not None:
-            raise ValueError(f"CoOpSweep: member {s}: ctx_init initialises a seeded member; this one brings its ctx")
         ns = n_max if m.get("n_ctx") is None else int(m["n_ctx"])
         if not 1 <= ns <= n_max:
             raise ValueError(f"CoOpSweep: member {s} has n_ctx = {ns}; a member's n_ctx must be in 1 .. {n_max} (the trainer's "
@@ -101,7 +93,7 @@ def member_start(m: dict, cfg: RPOConfig, n_cls: int, token_embedding) -> np.nda
     return np.ascontiguousarray(ctx, dtype=np.float32)
 
 
-class CoOpSweep(LoopMixin):
+class CoOpSweep(_members.MemberCheckpointMixin, _members.MemberScheduleMixin, LoopMixin):
     """S CoOp runs on one frozen CLIP, advanced by one step on shared batches.
 
     members: per member dict(seed=int [, ctx_init=...]) or dict(ctx=[n_s, d_t]), each with an optional n_ctx=n_s (1 .. the
@@ -119,10 +111,8 @@ class CoOpSweep(LoopMixin):
                  shared_prefix: bool = False, cfg: Optional[RPOConfig] = None, max_batch: Optional[int] = None,
                  world_size: int = 1, csc: bool = False, class_token_position: str = "end", classes=None, class_set=None):
         # ---- refusals, before any device is touched
-        if world_size != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("CoOpSweep: world_size > 1 is not supported (data parallelism for the sweep is not "
-                                      "built: the members share one image pass on one card); run one CoOpSweep per GPU with "
-                                      "different members")
+        _members.refuse_world_size("CoOpSweep", world_size, "data parallelism for the sweep is not built: the members share "
+                                   "one image pass on one card")
         if classes is not None or class_set is not None:
             _refuse_classes("__init__(classes=... / class_set=...)")
         if csc or class_token_position != "end":
@@ -143,14 +133,7 @@ class CoOpSweep(LoopMixin):
             raise ValueError(f"CoOpSweep: shared_prefix=True with members of different n_ctx {self.n_ctx_members}: the prefix "
                              "length P = 1 + n_ctx is per pass, so the shared-prefix rows serve members of the trainer's "
                              f"n_ctx = {n_max} only; use the dense rows (shared_prefix=False) for a mix")
-        for m in members:
-            m["optim"] = m.get("optim") or default_optim()
-            _optim.validate(m["optim"])
-        self.optim_cfgs: List[OptimConfig] = [m["optim"] for m in members]
-        epochs = [oc.max_epoch for oc in self.optim_cfgs]
-        if any(ep != epochs[0] for ep in epochs):
-            raise ValueError(f"CoOpSweep: the members differ in max_epoch ({epochs}): one loop runs all members, and the "
-                             "schedules count on its length -- run schedules of different lengths as separate trainers")
+        self.optim_cfgs: List[OptimConfig] = _members.member_optim_configs("CoOpSweep", members, default_optim)
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])
@@ -191,10 +174,6 @@ class CoOpSweep(LoopMixin):
     def _param_shapes(self, member: int):
         return [(self.n_ctx_members[member], self.cfg.d_t)]
 
-    def _check_member(self, member: int) -> None:
-        if not 0 <= member < self.n_runs:
-            raise IndexError(f"member {member} of {self.n_runs}")
-
     def named_parameters(self, member: int):
         """(name, device tensor) of member `member`'s trained tensor: ctx [n_s, d_t], a view of its row."""
         self._check_member(member)
@@ -204,12 +183,6 @@ class CoOpSweep(LoopMixin):
         """The tokenized prompts a standalone ``CoOp(n_ctx=n_s)`` of member `member` is built with."""
         self._check_member(member)
         return member_tokens(self.tokenized_prompts, self.n_ctx, self.n_ctx_members[member])
-
-    def skipped_steps(self) -> List[int]:
-        """amp: per member, the steps skipped so far because its own gradients held Inf / NaN (one D2H read)."""
-        if self._found_inf is None:
-            return [0] * self.n_runs
-        return [int(v) for v in self._found_inf[:, 1].tolist()]
 
     # ------------------------------------------------------------------ the step (`LoopMixin.step_async` / `run_epoch`)
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
@@ -222,20 +195,6 @@ class CoOpSweep(LoopMixin):
 
     def _loop_new_losses(self, nb: int) -> torch.Tensor:
         return torch.zeros(nb, self.n_runs, dtype=torch.float32, device=self.device)
-
-    def update_lr(self) -> None:
-        self.epoch += 1
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        self._opt.set_epoch(self.epoch)
-
-    def parse_batch_train(self, batch):
-        img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        label = torch.as_tensor(batch["label"])
-        if not label.is_cuda:
-            lo, hi = int(label.min()), int(label.max())
-            if lo < 0 or hi >= self.cfg.n_cls:
-                raise IndexError(f"Target {hi if hi >= self.cfg.n_cls else lo} is out of bounds (n_cls = {self.cfg.n_cls})")
-        return img, label.to(self.device, dtype=torch.int64, non_blocking=True)
 
     def forward_backward(self, batch) -> Dict[str, List[float]]:
         """One step of every member on ONE Dassl-style batch: {"loss": [S floats]}; update_lr() after the last batch of an
@@ -254,40 +213,11 @@ class CoOpSweep(LoopMixin):
         `test_all(val_set, features=val_features)` and per member Dassl's `after_epoch` bookkeeping: a member whose
         validation accuracy beats its own best so far is saved to its directory as `model-best`.  Without a validation set
         the last epoch's models are saved.  One record per epoch: the members' mean losses, and "val_acc" [S]."""
-        max_epoch = self.optim_cfgs[0].max_epoch if max_epoch is None else max_epoch
-        if directories is not None and len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        if val_features is not None:
-            if val_set is None:
-                raise ValueError("CoOpSweep.train: val_features are the features of val_set; pass both")
-            val_features.check(self.engine, val_set)
-        history, ep = [], 0
-        while self.epoch < max_epoch:
-            res = self.run_epoch(train_set, generator, None if plans is None else plans[ep])
-            ep += 1
-            rec = {"epoch": self.epoch, "loss": res["loss"].mean(0).tolist()}              # one read per epoch
-            if val_set is not None:
-                rec["val_acc"] = [r["accuracy"] for r in self.test_all(val_set, test_batch_size, val_features, verbose=False)]
-                if directories:
-                    self.after_epoch_eval(directories, rec["val_acc"])
-            elif directories and self.epoch == max_epoch:
-                self.save_model(directories)
-            if verbose:
-                print("epoch [{}/{}] loss ".format(self.epoch, max_epoch) + " ".join(f"{v:.4f}" for v in rec["loss"])
-                      + ("" if "val_acc" not in rec else " val_acc " + " ".join(f"{v:.2f}" for v in rec["val_acc"])))
-            history.append(rec)
-        return history
-
-    def after_epoch_eval(self, directories: Sequence[str], val_results: Sequence[float]) -> List[bool]:
-        """`LoopMixin.after_epoch_eval` per member: keep the checkpoint with the member's best validation result."""
-        best = []
-        for s, v in enumerate(val_results):
-            is_best = v > self.best_results[s]
-            if is_best:
-                self.best_results[s] = v
-                self._save_member(s, directories[s], None, True, v)
-            best.append(is_best)
-        return best
+        self._check_val_features(val_set, val_features)
+        return self._train_members(
+            max_epoch, lambda i: self.run_epoch(train_set, generator, None if plans is None else plans[i]),
+            None if val_set is None else lambda: self.test_all(val_set, test_batch_size, val_features, verbose=False),
+            directories, verbose)
 
     # ------------------------------------------------------------------ evaluation: all members per image pass
     @torch.no_grad()
@@ -348,60 +278,19 @@ class CoOpSweep(LoopMixin):
     def class_set(self, tokens, chunk=None):
         _refuse_classes("class_set")
 
-    # ------------------------------------------------------------------ checkpoints: per member, a standalone CoOp's files
-    def checkpoint_dict(self, member: int, epoch: Optional[int] = None, val_result: Optional[float] = None) -> dict:
-        """The dict a standalone ``CoOp(n_ctx=n_s, optim=optim_cfgs[member])`` on `member_tokens(member)` in this state
-        pickles (``CoOp.save_model``): ctx, the token_prefix / token_suffix buffers of ITS prompts, the optimiser's state."""
-        self._check_member(member)
-        epoch = self.epoch if epoch is None else epoch
+    # ------------------------------------------------------------------ checkpoints: `MemberCheckpointMixin`, CoOp's files
+    def _checkpoint_extra(self, member: int) -> Dict[str, torch.Tensor]:
+        """The token_prefix / token_suffix buffers of the prompts a standalone ``CoOp(n_ctx=n_s)`` of this member has:
+        those of `member_tokens(member)`."""
         ns = self.n_ctx_members[member]
-        optimizer = self._opt.state_dict(self._param_shapes(member), s=member, lr=self.lr[member], steps=self._steps)
-        state = {n: t.detach().cpu().clone() for n, t in self.named_parameters(member)}
         emb = np.asarray(self._token_embedding)[self.member_tokens(member)]                 # [n_cls, 77, d_t]
-        state["token_prefix"] = torch.from_numpy(np.ascontiguousarray(emb[:, :1]))
-        state["token_suffix"] = torch.from_numpy(np.ascontiguousarray(emb[:, 1 + ns:]))
-        return {"state_dict": state, "epoch": int(epoch), "optimizer": optimizer, "scheduler": {"last_epoch": int(epoch)},
-                "val_result": val_result, "steps": int(self._steps)}
-
-    def _save_member(self, member: int, directory: str, epoch, is_best: bool, val_result) -> str:
-        ck = self.checkpoint_dict(member, epoch, val_result)
-        return write_checkpoint(directory, ck, ck["epoch"], is_best)
-
-    def save_model(self, directories: Sequence[str], epoch: Optional[int] = None, is_best: bool = False,
-                   val_results: Optional[Sequence[Optional[float]]] = None) -> List[str]:
-        """Per member `<directories[s]>/prompt_learner/model.pth.tar-<epoch>` (+ `model-best.pth.tar`): ``CoOp``'s file."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        return [self._save_member(s, d, epoch, is_best, None if val_results is None else val_results[s])
-                for s, d in enumerate(directories)]
-
-    def _read(self, directories: Sequence[str], epoch: Optional[int]) -> List[dict]:
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        model_file = "model-best.pth.tar" if epoch is None else f"model.pth.tar-{epoch}"
-        got = []
-        for s, d in enumerate(directories):
-            path = os.path.join(d, "prompt_learner", model_file)
-            if not os.path.exists(path):
-                raise FileNotFoundError(f'Model not found at "{path}"')
-            ck = load_checkpoint_file(path)
-            if "ctx" not in ck["state_dict"]:
-                raise ValueError(f"{path}: the checkpoint lacks ctx: it was not written by a CoOp trainer")
-            sh, want = tuple(torch.as_tensor(ck["state_dict"]["ctx"]).shape), self._param_shapes(s)[0]
-            if sh != want:
-                raise ValueError(f"{path}: ctx has shape {sh}, member {s} of this trainer {want}")
-            got.append(ck)
-        return got
-
-    def _load_weights(self, got: Sequence[dict]) -> None:
-        with torch.no_grad(), torch.cuda.device(self.device):
-            for s, ck in enumerate(got):                                 # (token_prefix / token_suffix are dropped, as
-                for name, p in self.named_parameters(s):                 #  trainers/coop.py:315-320 drops them)
-                    p.copy_(torch.as_tensor(ck["state_dict"][name]).to(p.dtype).reshape(p.shape))
+        return {"token_prefix": torch.from_numpy(np.ascontiguousarray(emb[:, :1])),
+                "token_suffix": torch.from_numpy(np.ascontiguousarray(emb[:, 1 + ns:]))}
 
     def load_model(self, directories: Sequence[str], epoch: Optional[int] = None) -> List[dict]:
         """Reads S files written by standalone ``CoOp`` runs (or by `save_model`): weights only, as ``CoOp.load_model`` --
-        optimiser state, epoch and learning rates stay what they were.  Returns the checkpoint dicts."""
+        optimiser state, epoch and learning rates stay what they were (token_prefix / token_suffix are dropped, as
+        trainers/coop.py:315-320 drops them).  Returns the checkpoint dicts."""
         got = self._read(directories, epoch)
         self._load_weights(got)
         return got
@@ -410,28 +299,4 @@ class CoOpSweep(LoopMixin):
         """``CoOp.resume_model`` for every member: `load_model` plus the optimiser state, the epoch and the learning rates
         of the checkpoints.  One loop runs all members: files of different epochs are refused, and so is a mix of files
         with and without optimiser state.  Returns the epoch to continue from."""
-        got = self._read(directories, epoch)
-        epochs = [int(ck.get("epoch", 0)) for ck in got]
-        if any(ep != epochs[0] for ep in epochs):
-            raise ValueError(f"CoOpSweep.resume_model: the checkpoints are of epochs {epochs}; one loop runs all members")
-        has = [bool((ck.get("optimizer") or {}).get("state")) for ck in got]
-        if any(has) != all(has):
-            raise ValueError("CoOpSweep.resume_model: some checkpoints carry optimiser state and some do not (one step "
-                             "count covers every member)")
-        with torch.no_grad(), torch.cuda.device(self.device):
-            for s, ck in enumerate(got):
-                if has[s] and not self._opt.load_state_dict(ck["optimizer"], self._param_shapes(s), s=s,
-                                                            steps=ck.get("steps", 1)):
-                    raise ValueError(f"CoOpSweep.resume_model: member {s}'s checkpoint holds optimiser state that is not "
-                                     f"{self.optim_cfgs[s].name}'s for its ctx")
-        self._load_weights(got)
-        if all(has):
-            self._steps = max(1, max(int(ck.get("steps", 1)) for ck in got))
-        self.epoch = epochs[0]
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        with torch.cuda.device(self.device):
-            self._opt.set_epoch(self.epoch)
-            if self._found_inf is not None:                              # the skip counts are the resumed run's own
-                self._found_inf.zero_()
-        self._graph = None
-        return self.epoch
+        return self._resume(directories, epoch, "resume_model")

@@ -229,6 +229,18 @@ class LoopMixin(EvalMixin):
     def _loop_device(self):
         return torch.cuda.device(self.device)
 
+    # ---- the batch of a `forward_backward` ------------------------------------------------------------------
+    def parse_batch_train(self, batch):
+        """One Dassl-style batch {"img": float [B, 3, H, W], "label": [B]} on the device (CoOp, CoCoOp, LP and the sweeps
+        on shared batches; `RPO` has its own, which also takes decoded images)."""
+        img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
+        label = torch.as_tensor(batch["label"])
+        if not label.is_cuda:
+            lo, hi = int(label.min()), int(label.max())
+            if lo < 0 or hi >= self.cfg.n_cls:
+                raise IndexError(f"Target {hi if hi >= self.cfg.n_cls else lo} is out of bounds (n_cls = {self.cfg.n_cls})")
+        return img, label.to(self.device, dtype=torch.int64, non_blocking=True)
+
     # ---- bookkeeping ---------------------------------------------------------------------------------------
     def _loop_advance(self) -> None:
         """What every `forward_backward` does after its step: the LR / epoch update behind the epoch's last batch."""

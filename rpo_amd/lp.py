@@ -159,15 +159,6 @@ class LP(LoopMixin):
         """amp: steps GradScaler would have skipped so far (a device read)."""
         return int(self._found_inf[1].item()) if self.amp else 0
 
-    def parse_batch_train(self, batch):
-        img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        label = torch.as_tensor(batch["label"])
-        if not label.is_cuda:
-            lo, hi = int(label.min()), int(label.max())
-            if lo < 0 or hi >= self.cfg.n_cls:
-                raise IndexError(f"Target {hi if hi >= self.cfg.n_cls else lo} is out of bounds (n_cls = {self.cfg.n_cls})")
-        return img, label.to(self.device, dtype=torch.int64, non_blocking=True)
-
     def forward_backward(self, batch) -> Dict[str, float]:
         """trainers/linear_prob.py:151-184: {"loss", "acc"}; update_lr() after the last batch of an epoch."""
         eng = self.engine

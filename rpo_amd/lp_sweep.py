@@ -15,18 +15,18 @@ member per step for a number the sweep is not judged by -- the validation accura
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import members as _members
 from . import optim as _optim
 from .config import RPOConfig
 from .custom_clip import config_from_state_dict
 from .loop import LoopMixin
 from .lp import LP_MODEL_NAME, _check_prec, lp_optim_config
-from .trainer import OptimConfig, load_checkpoint_file, lr_at_epoch, write_checkpoint
+from .trainer import OptimConfig, lr_at_epoch
 
 
 def _refuse_classes(what: str):
@@ -45,7 +45,7 @@ def member_optimizer(optim_cfgs: Sequence[OptimConfig], stride: int, device, s0:
     return _optim.make_optimizer(optim_cfgs, stride, stride, 0, device, s0=s0, used=used)
 
 
-class LPSweep(LoopMixin):
+class LPSweep(_members.MemberCheckpointMixin, _members.MemberScheduleMixin, LoopMixin):
     """S linear probes with their own optimiser configs on one frozen CLIP, advanced by one step on shared batches.
 
     members: per member dict(optim=OptimConfig [, weight=[e, e], bias=[e]]); the default start is the reference's identity /
@@ -55,16 +55,15 @@ class LPSweep(LoopMixin):
 
     _reports_acc = False
     captures = 0                       # HIP graphs of the step captured so far (rates are device data: one)
+    _checkpoint_name = LP_MODEL_NAME   # `MemberCheckpointMixin`: per member, a standalone ``LP``'s file
 
     def __init__(self, state_dict: Dict[str, np.ndarray], tokenized_prompts: np.ndarray, members: Sequence[dict] = (),
                  device: str | torch.device = "cuda:0", act_dtype: torch.dtype = torch.float32, batch_size: int = 32,
                  num_batches: int = 1, use_graph: bool = False, amp: bool = False, prec: Optional[str] = None,
                  max_batch: Optional[int] = None, cfg: Optional[RPOConfig] = None, world_size: int = 1):
         # ---- refusals, before any device is touched
-        if world_size != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("LPSweep: world_size > 1 is not supported (data parallelism for the sweep is not built: "
-                                      "the members share one image pass on one card); run one LPSweep per GPU with different "
-                                      "members")
+        _members.refuse_world_size("LPSweep", world_size, "data parallelism for the sweep is not built: the members share "
+                                   "one image pass on one card")
         _check_prec(prec)
         if prec == "fp32":
             act_dtype, amp = torch.float32, False
@@ -76,14 +75,7 @@ class LPSweep(LoopMixin):
             raise ValueError("LPSweep: no members -- pass members=[dict(optim=OptimConfig(...)), ...], one per point of the sweep")
         if S > 1024:
             raise ValueError(f"LPSweep: {S} members; the grouped head and the fused evaluation take at most 1024")
-        for m in members:
-            m["optim"] = m.get("optim") or lp_optim_config()
-            _optim.validate(m["optim"])
-        self.optim_cfgs: List[OptimConfig] = [m["optim"] for m in members]
-        epochs = [oc.max_epoch for oc in self.optim_cfgs]
-        if any(ep != epochs[0] for ep in epochs):
-            raise ValueError(f"LPSweep: the members differ in max_epoch ({epochs}): one loop runs all members, and the schedules "
-                             "count on its length -- run schedules of different lengths as separate trainers")
+        self.optim_cfgs: List[OptimConfig] = _members.member_optim_configs("LPSweep", members, lp_optim_config)
         tokens = np.asarray(tokenized_prompts, dtype=np.int64)
         if cfg is None:
             cfg = config_from_state_dict(state_dict, 1, tokens.shape[0])
@@ -122,7 +114,7 @@ class LPSweep(LoopMixin):
             self._opt = member_optimizer(self.optim_cfgs, stride, self.device, eng.lps_moms)
 
     # ------------------------------------------------------------------ members' state
-    def _param_shapes(self):
+    def _param_shapes(self, member: int = 0):
         e = self.cfg.embed
         return [(e, e), (e,)]
 
@@ -131,16 +123,6 @@ class LPSweep(LoopMixin):
         self._check_member(member)
         yield "weight", self.engine.lps_w[member]
         yield "bias", self.engine.lps_b[member]
-
-    def _check_member(self, member: int) -> None:
-        if not 0 <= member < self.n_runs:
-            raise IndexError(f"member {member} of {self.n_runs}")
-
-    def skipped_steps(self) -> List[int]:
-        """amp: per member, the steps skipped so far because its own gradients held Inf / NaN (one D2H read)."""
-        if self._found_inf is None:
-            return [0] * self.n_runs
-        return [int(v) for v in self._found_inf[:, 1].tolist()]
 
     # ------------------------------------------------------------------ the step (`LoopMixin.step_async` / `run_epoch`)
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
@@ -153,20 +135,6 @@ class LPSweep(LoopMixin):
 
     def _loop_new_losses(self, nb: int) -> torch.Tensor:
         return torch.zeros(nb, self.n_runs, dtype=torch.float32, device=self.device)
-
-    def update_lr(self) -> None:
-        self.epoch += 1
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        self._opt.set_epoch(self.epoch)
-
-    def parse_batch_train(self, batch):
-        img = batch["img"].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
-        label = torch.as_tensor(batch["label"])
-        if not label.is_cuda:
-            lo, hi = int(label.min()), int(label.max())
-            if lo < 0 or hi >= self.cfg.n_cls:
-                raise IndexError(f"Target {hi if hi >= self.cfg.n_cls else lo} is out of bounds (n_cls = {self.cfg.n_cls})")
-        return img, label.to(self.device, dtype=torch.int64, non_blocking=True)
 
     def forward_backward(self, batch) -> Dict[str, List[float]]:
         """One step of every member on ONE Dassl-style batch: {"loss": [S floats]}; update_lr() after the last batch of an
@@ -186,40 +154,11 @@ class LPSweep(LoopMixin):
         validation accuracy beats its own best so far is saved to its directory as `model-best`.  Without a validation set
         the last epoch's models are saved.  `plans`: per epoch of this call, per batch, the images' `SamplePlan`s.
         One record per epoch: the members' mean losses, and "val_acc" [S]."""
-        max_epoch = self.optim_cfgs[0].max_epoch if max_epoch is None else max_epoch
-        if directories is not None and len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        if val_features is not None:
-            if val_set is None:
-                raise ValueError("LPSweep.train: val_features are the features of val_set; pass both")
-            val_features.check(self.engine, val_set)
-        history, ep = [], 0
-        while self.epoch < max_epoch:
-            res = self.run_epoch(train_set, generator, None if plans is None else plans[ep])
-            ep += 1
-            rec = {"epoch": self.epoch, "loss": res["loss"].mean(0).tolist()}              # one read per epoch
-            if val_set is not None:
-                rec["val_acc"] = [r["accuracy"] for r in self.test_all(val_set, test_batch_size, val_features, verbose=False)]
-                if directories:
-                    self.after_epoch_eval(directories, rec["val_acc"])
-            elif directories and self.epoch == max_epoch:
-                self.save_model(directories)
-            if verbose:
-                print("epoch [{}/{}] loss ".format(self.epoch, max_epoch) + " ".join(f"{v:.4f}" for v in rec["loss"])
-                      + ("" if "val_acc" not in rec else " val_acc " + " ".join(f"{v:.2f}" for v in rec["val_acc"])))
-            history.append(rec)
-        return history
-
-    def after_epoch_eval(self, directories: Sequence[str], val_results: Sequence[float]) -> List[bool]:
-        """`LoopMixin.after_epoch_eval` per member: keep the checkpoint with the member's best validation result."""
-        best = []
-        for s, v in enumerate(val_results):
-            is_best = v > self.best_results[s]
-            if is_best:
-                self.best_results[s] = v
-                self._save_member(s, directories[s], None, True, v)
-            best.append(is_best)
-        return best
+        self._check_val_features(val_set, val_features)
+        return self._train_members(
+            max_epoch, lambda i: self.run_epoch(train_set, generator, None if plans is None else plans[i]),
+            None if val_set is None else lambda: self.test_all(val_set, test_batch_size, val_features, verbose=False),
+            directories, verbose)
 
     # ------------------------------------------------------------------ evaluation: all members per image pass
     @torch.no_grad()
@@ -270,68 +209,10 @@ class LPSweep(LoopMixin):
     def class_set(self, tokens, chunk=None):
         _refuse_classes("class_set")
 
-    # ------------------------------------------------------------------ checkpoints: per member, a standalone LP's files
-    def checkpoint_dict(self, member: int, epoch: Optional[int] = None, val_result: Optional[float] = None) -> dict:
-        """The dict a standalone `LP(optim=optim_cfgs[member])` in this state pickles (`LP.checkpoint_dict`)."""
-        self._check_member(member)
-        epoch = self.epoch if epoch is None else epoch
-        optimizer = self._opt.state_dict(self._param_shapes(), s=member, lr=self.lr[member], steps=self._steps)
-        state = {n: t.detach().cpu().clone() for n, t in self.named_parameters(member)}
-        return {"state_dict": state, "epoch": int(epoch), "optimizer": optimizer, "scheduler": {"last_epoch": int(epoch)},
-                "val_result": val_result, "steps": int(self._steps)}
-
-    def _save_member(self, member: int, directory: str, epoch, is_best: bool, val_result) -> str:
-        ck = self.checkpoint_dict(member, epoch, val_result)
-        return write_checkpoint(directory, ck, ck["epoch"], is_best, name=LP_MODEL_NAME)
-
-    def save_model(self, directories: Sequence[str], epoch: Optional[int] = None, is_best: bool = False,
-                   val_results: Optional[Sequence[Optional[float]]] = None) -> List[str]:
-        """Per member `<directories[s]>/lp_layer/model.pth.tar-<epoch>` (+ `model-best.pth.tar`): `LP.save_model`'s file."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        return [self._save_member(s, d, epoch, is_best, None if val_results is None else val_results[s])
-                for s, d in enumerate(directories)]
-
+    # ------------------------------------------------------------------ checkpoints: `MemberCheckpointMixin`, LP's files
     def load_model(self, directories: Sequence[str], epoch: Optional[int] = None) -> None:
         """Reads S files written by standalone `LP` runs (or by `save_model`): the layer, the optimiser state, the epoch and
-        the learning rates (what `LP.resume_model` restores).  One loop runs all members: files of different epochs are
-        refused, and so is a mix of files with and without optimiser state."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        model_file = "model-best.pth.tar" if epoch is None else f"model.pth.tar-{epoch}"
-        shapes, got = self._param_shapes(), []
-        for s, d in enumerate(directories):
-            path = os.path.join(d, LP_MODEL_NAME, model_file)
-            if not os.path.exists(path):
-                raise FileNotFoundError(f'Model not found at "{path}"')
-            ck = load_checkpoint_file(path)
-            sd = ck["state_dict"]
-            for name, sh in zip(("weight", "bias"), shapes):
-                if name not in sd:
-                    raise ValueError(f"{path}: the checkpoint lacks lp_layer's {name}: it was written by another trainer")
-                if tuple(torch.as_tensor(sd[name]).shape) != sh:
-                    raise ValueError(f"{path}: {name} has shape {tuple(torch.as_tensor(sd[name]).shape)}, lp_layer {sh}")
-            got.append(ck)
-        epochs = [int(ck.get("epoch", 0)) for ck in got]
-        if any(ep != epochs[0] for ep in epochs):
-            raise ValueError(f"LPSweep.load_model: the checkpoints are of epochs {epochs}; one loop runs all members")
-        has = [bool((ck.get("optimizer") or {}).get("state")) for ck in got]
-        if any(has) != all(has):
-            raise ValueError("LPSweep.load_model: some checkpoints carry optimiser state and some do not (one step count "
-                             "covers every member)")
-        eng = self.engine
-        with torch.no_grad():
-            for s, ck in enumerate(got):
-                if has[s] and not self._opt.load_state_dict(ck["optimizer"], shapes, s=s, steps=ck.get("steps", 1)):
-                    raise ValueError(f"LPSweep.load_model: member {s}'s checkpoint holds optimiser state that is not "
-                                     f"{self.optim_cfgs[s].name}'s for lp_layer's shapes")
-                eng.lps_w[s].copy_(torch.as_tensor(ck["state_dict"]["weight"]).float())
-                eng.lps_b[s].copy_(torch.as_tensor(ck["state_dict"]["bias"]).float())
-        if all(has):
-            self._steps = max(1, max(int(ck.get("steps", 1)) for ck in got))
-        self.epoch = epochs[0]
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-        self._opt.set_epoch(self.epoch)
-        if self._found_inf is not None:                                  # the skip counts are the resumed run's own
-            self._found_inf.zero_()
-        self._graph = None
+        the learning rates (what `LP.resume_model` restores; `load_model` is this trainer's name for it).  One loop runs all
+        members: files of different epochs are refused, and so is a mix of files with and without optimiser state, before
+        anything is applied."""
+        self._resume(directories, epoch, "load_model")

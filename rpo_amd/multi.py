@@ -14,17 +14,19 @@ per member and interchangeable with a standalone ``RPO``'s.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import members as _members
 from . import optim as _optim
-from .config import RPOConfig, refuse_long_grid
-from .custom_clip import init_prompts, refuse_rn
-from .loop import EvalMixin, epoch_indices
-from .trainer import OptimConfig, checkpoint_dict, load_checkpoint_file, lr_at_epoch, write_checkpoint
+from .config import refuse_long_grid
+from .custom_clip import refuse_rn
+from .loop import EvalMixin
+from .members import (MemberLoopMixin, member_batches, member_checkpoint,  # noqa: F401  (importable from here, where they
+                      read_member_checkpoint, seeded_prompts)               # were written, under their names)
+from .trainer import OptimConfig, lr_at_epoch, write_checkpoint
 
 
 def _one_of(values, what: str):
@@ -38,144 +40,14 @@ def _one_of(values, what: str):
     return values
 
 
-def seeded_prompts(state_dict: Dict[str, np.ndarray], cfg: RPOConfig, seeds: Sequence[int]) -> List[tuple]:
-    """Member s's initial (text_prompt, img_prompt) as ``RPO`` draws them under ``torch.manual_seed(seeds[s])``: the same
-    draws from the global CPU generator in the same order (custom_clip.init_prompts).  Leaves the global generator where
-    the last member's construction would."""
-    out = []
-    for seed in seeds:
-        torch.manual_seed(int(seed))
-        out.append(init_prompts(state_dict, cfg.K, cfg.d_t, cfg.d_v))
-    return out
+_WHY_NO_DP = "the members fill the card that data parallelism would split"
 
 
-def member_batches(set_sizes: Sequence[int], batch_size: int, generators: Sequence[Optional[torch.Generator]],
-                   who: str = "RPOMulti") -> List[list]:
-    """Per member, the index batches of one epoch: `epoch_indices` with that member's set size and generator, i.e. exactly
-    the order a standalone run sees.  Every member must get the same number of batches (a step advances all of them)."""
-    if len(set_sizes) != len(generators):
-        raise ValueError(f"{len(set_sizes)} image sets for {len(generators)} generators")
-    nbs = [n // batch_size for n in set_sizes]
-    if any(nb != nbs[0] for nb in nbs) or nbs[0] == 0:
-        raise ValueError(f"{who}.run_epoch: the members' sets have {list(set_sizes)} images = {nbs} batches of {batch_size}; "
-                         "every member must have the same, non-zero number of batches per epoch (a step advances all members)")
-    return [epoch_indices(n, batch_size, g) for n, g in zip(set_sizes, generators)]
-
-
-def member_checkpoint(flat_params: torch.Tensor, flat_mom: Optional[torch.Tensor], cfg: RPOConfig, epoch: int,
-                      oc: OptimConfig, lr: float, steps: int, val_result: Optional[float] = None,
-                      optimizer: Optional[dict] = None) -> dict:
-    """The dict a standalone ``RPO.save_model`` pickles for a run whose flat [text | img] parameters / momentum (or
-    `optimizer` entry) are these."""
-    nt = cfg.K * cfg.d_t
-    p = flat_params.detach().cpu()
-    state = {"text_prompt": p[:nt].reshape(cfg.K, cfg.d_t), "img_prompt": p[nt:].reshape(cfg.K, cfg.d_v)}
-    return checkpoint_dict(state, epoch, flat_mom, oc, lr, steps, nt, val_result, optimizer)
-
-
-def read_member_checkpoint(directory: str, epoch: Optional[int], cfg: RPOConfig):
-    """(flat params, checkpoint dict) of a file ``RPO.save_model`` / ``RPOMulti.save_model`` wrote."""
-    model_file = "model-best.pth.tar" if epoch is None else f"model.pth.tar-{epoch}"
-    model_path = os.path.join(directory, "prompt_learner", model_file)
-    if not os.path.exists(model_path):
-        raise FileNotFoundError(f'Model not found at "{model_path}"')
-    ck = load_checkpoint_file(model_path)
-    sd = ck["state_dict"]
-    tp, ip = sd["text_prompt"].float(), sd["img_prompt"].float()
-    if tuple(tp.shape) != (cfg.K, cfg.d_t) or tuple(ip.shape) != (cfg.K, cfg.d_v):
-        raise ValueError(f"{model_path}: prompts {tuple(tp.shape)} / {tuple(ip.shape)}, this trainer has K = {cfg.K}, "
-                         f"widths {cfg.d_t} / {cfg.d_v}")
-    flat = torch.cat([tp.reshape(-1), ip.reshape(-1)])
-    return flat, ck
-
-
-class MemberLoopMixin:
-    """The member-major batch and epoch loop of a trainer that advances S members of `batch_size` images by one
-    `step_async(image [S*B], label [S*B])` (`RPOMulti`, `RPOSweep`, `CoCoOpMulti`): needs `n_runs`, `batch_size`, `num_batches`,
-    `batch_idx`, `cfg`, `device`, `_image` (the step's own [S*B] image buffer), `update_lr`."""
-
-    _loop_name = "RPOMulti"                             # who the refusals of the loop name
-
-    def parse_batch_train(self, batches: Sequence[dict]):
-        """S Dassl-style batches {"img": float [B, 3, H, W], "label": [B]} -> one member-major device batch."""
-        if len(batches) != self.n_runs:
-            raise ValueError(f"{len(batches)} batches for {self.n_runs} members")
-        n = self.cfg.n_cls
-        for s, b in enumerate(batches):
-            lab = torch.as_tensor(b["label"])
-            if not lab.is_cuda and lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= n):
-                raise IndexError(f"member {s}: target out of bounds (n_cls = {n}; labels must be renumbered after the "
-                                 "base/new split)")
-        img = torch.cat([torch.as_tensor(b["img"]).to(self.device, dtype=torch.float32) for b in batches]).contiguous()
-        label = torch.cat([torch.as_tensor(b["label"]).to(self.device, dtype=torch.int64) for b in batches]).contiguous()
-        return img, label
-
-    def _loop_advance(self) -> None:
-        if (self.batch_idx + 1) == self.num_batches:
-            self.update_lr()
-            self.batch_idx = 0
-        else:
-            self.batch_idx += 1
-
-    # ------------------------------------------------------------------ the epoch loop
-    def run_epoch(self, image_sets, generators: Optional[Sequence[Optional[torch.Generator]]] = None,
-                  plans=None) -> Dict[str, object]:
-        """One epoch of every member over its own resident set (`image_sets`: one `DeviceImageSet` per member, or one
-        shared set) in the order `epoch_indices` gives a standalone run with that member's generator.  `plans`: per member,
-        per batch, the `SamplePlan`s of its images (default: drawn by the transform, member by member within a step).
-        As `loop.LoopMixin.run_epoch`: no device scalar is read, and batch t + 1 is in its buffer before step t is
-        enqueued.  Returns {"loss": float32 [num_batches, S] on the device, "indices": per member, the batches}."""
-        S, B = self.n_runs, self.batch_size
-        sets = list(image_sets) if isinstance(image_sets, (list, tuple)) else [image_sets] * S
-        if len(sets) != S:
-            raise ValueError(f"{len(sets)} image sets for {S} members")
-        gens = list(generators) if generators is not None else [None] * S
-        batches = member_batches([len(ds) for ds in sets], B, gens, self._loop_name)
-        nb = len(batches[0])
-        if nb != self.num_batches:
-            raise ValueError(f"the sets give {nb} batches of {B} per member; the trainer was built with num_batches = "
-                             f"{self.num_batches} (its LR schedule counts on it)")
-        if self.batch_idx != 0:
-            raise RuntimeError("run_epoch starts at an epoch boundary (batch_idx != 0: forward_backward is mid-epoch)")
-        for ds in set(sets):
-            ds.check_labels(self.cfg.n_cls)
-        with torch.cuda.device(self.device):
-            if getattr(self, "_loop_bufs", None) is None:
-                self._loop_bufs = [torch.zeros_like(self._image) for _ in range(2)]
-            # one transform (= one pair of descriptor slots) per MEMBER, also when members share a set: a slot is reused
-            # only after its call of two turns ago has been read, so with one transform for several members the host would
-            # wait for the step before inside every fill and the one-batch lookahead would be gone.  (A shared set's spill
-            # tail is guarded by the set's own events and every call is on one stream.)  The transforms hold no set.
-            if getattr(self, "_member_tfs", None) is None:
-                from .input_pipeline import DeviceTransform, InputConfig
-                icfg = InputConfig(SIZE=(self.cfg.image_size, self.cfg.image_size))
-                self._member_tfs = [DeviceTransform(icfg, True, self.device, B, max_image_bytes=16) for _ in range(S)]
-            tfs = self._member_tfs
-            labels = torch.stack([ds.labels_dev[torch.tensor(bt, dtype=torch.int64).to(self.device)]
-                                  for ds, bt in zip(sets, batches)], 1).reshape(nb, S * B)      # [nb, S*B] member-major
-            losses = torch.zeros(nb, S, dtype=torch.float32, device=self.device)
-
-            def fill(t, out):
-                for s in range(S):
-                    tfs[s].from_set(sets[s], batches[s][t], None if plans is None else plans[s][t], out=out[s * B:(s + 1) * B])
-
-            fill(0, self._loop_bufs[0])
-            for t in range(nb):
-                cur = self._loop_bufs[t & 1]
-                if t + 1 < nb:
-                    fill(t + 1, self._loop_bufs[(t + 1) & 1])
-                loss = self.step_async(cur, labels[t])
-                losses[t].copy_(loss, non_blocking=True)
-                self._loop_advance()
-        return {"loss": losses, "indices": batches}
-
-
-class RPOMulti(MemberLoopMixin, EvalMixin):
+class RPOMulti(_members.MemberMixin, MemberLoopMixin, EvalMixin):
     _found_inf = None                                   # amp is refused here; `RPOSweep` has one verdict per member
     _features_why_not = ("RPO's image rows read its members' prompts, so no image feature outlives a step; what an image set "
                          "can cache for RPO is the frozen rows' K / V: FrozenImageKV.build(engine, image_set) and "
                          "test_all(..., frozen=...)")
-    _one_counter = " (one step counter covers every member)"     # why a mix of files with and without state is refused
     captures = 0                                        # HIP graphs of the step captured so far (one per distinct learning rate)
 
     def __init__(self, cfg, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None, n_runs: int = 1,
@@ -189,9 +61,7 @@ class RPOMulti(MemberLoopMixin, EvalMixin):
         if amp:
             raise NotImplementedError("RPOMulti: amp=True is not supported (GradScaler's skip is one verdict per optimiser "
                                       "step; the members would need one each): run amp members as separate RPO trainers")
-        if world_size != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("RPOMulti: world_size > 1 is not supported (the members fill the card that data "
-                                      "parallelism would split); run one RPOMulti per GPU with different members")
+        _members.refuse_world_size("RPOMulti", world_size, _WHY_NO_DP)
         S, B = int(n_runs), int(batch_size)
         if S < 1 or B < 1:
             raise ValueError(f"RPOMulti: n_runs = {n_runs}, batch_size = {batch_size}: both must be >= 1")
@@ -246,44 +116,20 @@ class RPOMulti(MemberLoopMixin, EvalMixin):
         eng.m_params.copy_(host)
         self._eval_member = None
 
-    # ------------------------------------------------------------------ the step
+    # ------------------------------------------------------------------ the step: `MemberLoopMixin.step_async` enqueues these
+    def _forward_backward(self, image: torch.Tensor, label: torch.Tensor) -> None:
+        self.engine.multi_forward_backward(image, label)
+
     def _enqueue(self, image: torch.Tensor, label: torch.Tensor) -> None:
         eng = self.engine
-        eng.multi_forward_backward(image, label)
+        self._forward_backward(image, label)
         self._opt.step(eng.m_params, eng.m_grads, self._found_inf, first_step=(self._steps == 0))
 
-    def step_async(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-        """One optimisation step of every member, nothing synchronised: image [S*B, 3, H, W] and label [S*B], member-major
-        (member s owns rows [s B, (s+1) B)).  Returns loss [S] on the device.  With use_graph the whole step -- both
-        towers, the grouped head, both backward chains, the SGD launch -- is ONE HIP graph, captured after the first
-        (eager) step and again whenever the optimiser's `graph_key` changes (plain SGD: the learning rate, a kernel argument)."""
-        assert torch.cuda.current_device() == self.device.index, "set the trainer's device current (torch.cuda.set_device)"
-        SB = self.n_runs * self.batch_size
-        assert image.shape[0] == SB and label.shape == (SB,), f"step_async takes S * B = {SB} images, member-major"
-        if image.data_ptr() != self._image.data_ptr():
-            self._image.copy_(image, non_blocking=True)
-        self._label.copy_(label, non_blocking=True)
-        self._opt.set_epoch(self.epoch)                 # (in front of the step, on its stream; nothing within an epoch)
-        key = self._opt.graph_key()                     # what a captured step has baked in besides addresses
-        if not self.use_graph or self._steps == 0:
-            self._enqueue(self._image, self._label)
-            self._warm = True
-        else:
-            if self._graph is None or self._graph[1] != key:
-                if not self._warm:                      # (a resumed run: kernel attributes are set by an eager launch, not in
-                    self.engine.multi_forward_backward(self._image, self._label)    # a capture; it writes only what the step
-                    self._warm = True                                                 # overwrites)
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._enqueue(self._image, self._label)
-                self._graph = (g, key)                 # (capture does not execute: the replay below is this step)
-                self.captures += 1
-            self._graph[0].replay()
-        self._steps += 1
-        self._eval_member = None
-        self.engine.text_f_version = -1
+    def _loop_loss(self) -> torch.Tensor:
         return self.engine.m_loss
+
+    def _after_step(self) -> None:
+        self.engine.text_f_version = -1
 
     def forward_backward(self, batches: Sequence[dict]) -> List[Dict[str, float]]:
         """trainers/rpo.py:290-316 for every member: a list of S batches in, a list of S {"loss", "acc"} out."""
@@ -304,8 +150,7 @@ class RPOMulti(MemberLoopMixin, EvalMixin):
 
     # ------------------------------------------------------------------ evaluation: the single-run path, one member
     def _select(self, member: int) -> None:
-        if not 0 <= member < self.n_runs:
-            raise IndexError(f"member {member} of {self.n_runs}")
+        self._check_member(member)
         if self._eval_member != member:
             self.engine.multi_load_member(member)
             self._eval_member = member
@@ -381,8 +226,7 @@ class RPOMulti(MemberLoopMixin, EvalMixin):
     def save_model(self, directories: Sequence[str], epoch: Optional[int] = None, is_best: bool = False,
                    val_results: Optional[Sequence[Optional[float]]] = None) -> List[str]:
         """Per member, the file a standalone `RPO.save_model(directories[s])` writes (same keys, Dassl layout, momentum)."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
+        self._check_directories(directories)
         epoch = self.epoch if epoch is None else epoch
         p = self.engine.m_params.detach().cpu()
         n, shapes, out = p.shape[1], [(self.cfg.K, self.cfg.d_t), (self.cfg.K, self.cfg.d_v)], []
@@ -396,17 +240,14 @@ class RPOMulti(MemberLoopMixin, EvalMixin):
     def load_model(self, directories: Sequence[str], epoch: Optional[int] = None) -> None:
         """Reads S files written by standalone runs (or by `save_model`): prompts, momentum, epoch (trainers/rpo.py:325-357).
         The members share the schedule: files of different epochs are refused."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
+        self._check_directories(directories)
         got = [read_member_checkpoint(d, epoch, self.cfg) for d in directories]
-        epochs = [int(ck.get("epoch", 0)) for _, ck in got]
-        if any(e != epochs[0] for e in epochs):
-            raise ValueError(f"RPOMulti.load_model: the checkpoints are of epochs {epochs}; the members share one schedule")
+        ep = self._files_epoch([ck for _, ck in got], "load_model", "the members share one schedule")
         eng, n = self.engine, self.engine.m_params.shape[1]
         shapes = [(self.cfg.K, self.cfg.d_t), (self.cfg.K, self.cfg.d_v)]
         self._load_states(got, lambda s: dict(param_shapes=shapes, scatter=lambda d, r: d[s * n:(s + 1) * n].copy_(r)))
         eng.m_params.copy_(torch.stack([p for p, _ in got]))
-        self.epoch = epochs[0]
+        self.epoch = ep
         self.lr = lr_at_epoch(self.optim_cfg, self.epoch)
         self._opt.set_epoch(self.epoch)
         self._eval_member = None
@@ -417,9 +258,6 @@ class RPOMulti(MemberLoopMixin, EvalMixin):
         one -- then `_steps` is the files' -- or none has; a mix is refused."""
         have = [self._opt.load_state_dict(ck.get("optimizer"), steps=ck.get("steps", 1), **member_kw(s))
                 for s, (_, ck) in enumerate(got)]
-        if any(have) != all(have):
-            raise ValueError(f"{type(self).__name__}.load_model: some checkpoints carry "
-                             + ("optimiser state and some do not" + self._one_counter if self._opt.table_driven else
-                                "momentum and some do not (one first-step flag covers every member)"))
-        if all(have):
-            self._steps = max(1, max(int(ck.get("steps", 1)) for _, ck in got))
+        steps = self._files_steps([ck for _, ck in got], have, "load_model")
+        if steps is not None:
+            self._steps = steps

@@ -21,15 +21,15 @@ goes through the shared prompt-row pass with that member's K, and a member's che
 from __future__ import annotations
 
 import dataclasses
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import members as _members
 from . import optim as _optim
 from .custom_clip import init_prompts, refuse_rn
-from .multi import RPOMulti, member_checkpoint, read_member_checkpoint
+from .multi import _WHY_NO_DP, RPOMulti
 from .trainer import OptimConfig, lr_at_epoch, write_checkpoint
 
 
@@ -81,7 +81,7 @@ def _shared(members: Sequence[dict], key: str, default, what: str):
     return ref
 
 
-class RPOSweep(RPOMulti):
+class RPOSweep(_members.MemberScheduleMixin, RPOMulti):
     _one_counter = ""
 
     def __init__(self, cfg, state_dict: Dict[str, np.ndarray], tokens: Optional[np.ndarray] = None,
@@ -97,9 +97,7 @@ class RPOSweep(RPOMulti):
             raise ValueError(f"RPOSweep: {S} members, batch_size = {batch_size}: both must be >= 1")
         cfg = _shared(members, "cfg", cfg, "CLIP / class set / backbone (config)")
         refuse_rn(cfg, "RPOSweep")
-        if world_size != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("RPOSweep: world_size > 1 is not supported (the members fill the card that data "
-                                      "parallelism would split); run one RPOSweep per GPU with different members")
+        _members.refuse_world_size("RPOSweep", world_size, _WHY_NO_DP)
         _shared(members, "batch_size", B, "batch size")
         act_dtype = _shared(members, "act_dtype", act_dtype, "storage mode (act_dtype)")
         for s, m in enumerate(members):
@@ -108,13 +106,7 @@ class RPOSweep(RPOMulti):
             if "K" not in m or int(m["K"]) < 1:
                 raise ValueError(f"RPOSweep: member {s} has K = {m.get('K')}: every member names its own K >= 1")
             m["K"] = int(m["K"])
-            m["optim"] = m.get("optim") or OptimConfig()
-            _optim.validate(m["optim"])
-        self.optim_cfgs = [m["optim"] for m in members]
-        epochs = [oc.max_epoch for oc in self.optim_cfgs]
-        if any(e != epochs[0] for e in epochs):
-            raise ValueError(f"RPOSweep: the members differ in max_epoch ({epochs}): one loop runs all members, and the cosine "
-                             "schedule counts on its length -- run schedules of different lengths as separate trainers")
+        self.optim_cfgs = _members.member_optim_configs("RPOSweep", members, OptimConfig, "the cosine schedule counts")
         self.member_K = [m["K"] for m in members]
         for s, m in enumerate(members):
             if m.get("prompts") is not None:
@@ -152,30 +144,13 @@ class RPOSweep(RPOMulti):
         self.engine.text_f_version = -1
         self._eval_member = None
 
-    def skipped_steps(self) -> List[int]:
-        """amp: per member, the steps skipped so far because its own used gradients held Inf / NaN (one D2H read)."""
-        if self._found_inf is None:
-            return [0] * self.n_runs
-        return [int(v) for v in self._found_inf[:, 1].tolist()]
-
     # ------------------------------------------------------------------ the step: `RPOMulti`'s (the rates are device data)
-    def update_lr(self) -> None:
-        self.epoch += 1
-        self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
-
     def train(self, image_sets, max_epoch: Optional[int] = None, generators=None, directories: Optional[Sequence[str]] = None,
               verbose: bool = True) -> List[dict]:
         """`run_epoch` until `max_epoch` (default: the members' shared one); the last epoch's models are saved to
         `directories`.  One record per epoch: the members' mean losses (one read per epoch)."""
-        max_epoch = self.optim_cfgs[0].max_epoch if max_epoch is None else max_epoch
-        history = []
-        while self.epoch < max_epoch:
-            res = self.run_epoch(image_sets, generators)
-            rec = {"epoch": self.epoch, "loss": res["loss"].mean(0).tolist()}
-            if verbose:
-                print("epoch [{}/{}] loss ".format(self.epoch, max_epoch) + " ".join(f"{v:.4f}" for v in rec["loss"]))
-            history.append(rec)
-        if directories:
+        history = self._train_members(max_epoch, lambda i: self.run_epoch(image_sets, generators), verbose=verbose)
+        if directories:                               # (no validation, no per-epoch save: once, also when no epoch ran)
             self.save_model(directories)
         return history
 
@@ -190,8 +165,7 @@ class RPOSweep(RPOMulti):
                                   "member's K_s; train the member as an RPO / RPOMulti run, or load its checkpoint into one")
 
     def _member_sides(self, member: int):
-        if not 0 <= member < self.n_runs:
-            raise IndexError(f"member {member} of {self.n_runs}")
+        self._check_member(member)
         eng, rows = self.engine, self.cfg.n_cls * self.cfg.K
         text_f = eng.multi_text_features()[member * rows:(member + 1) * rows]
         return eng.m_img_prompt[member:member + 1], text_f, eng.m_k_used[member:member + 1]
@@ -230,34 +204,30 @@ class RPOSweep(RPOMulti):
                    val_results: Optional[Sequence[Optional[float]]] = None) -> List[str]:
         """Per member, the file a standalone `RPO(cfg.K = K_s, optim_s).save_model(directories[s])` writes: prompts
         [K_s, d], momentum in its flat order, the member's own learning rate and optimiser settings."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
+        self._check_directories(directories)
         epoch = self.epoch if epoch is None else epoch
         p = self.engine.m_params.detach().cpu()
         out = []
         for s, d in enumerate(directories):
             entry = self._opt.state_dict(self._shapes(s), s=s, lr=self.lr[s], steps=self._steps,
                                          gather=lambda row: member_row_to_flat(row, *self._dims(s)))
-            ck = member_checkpoint(member_row_to_flat(p[s], *self._dims(s)), None, self.member_cfgs[s], epoch,
-                                   self.optim_cfgs[s], self.lr[s], self._steps, None if val_results is None else val_results[s],
-                                   entry)
+            ck = _members.member_checkpoint(member_row_to_flat(p[s], *self._dims(s)), None, self.member_cfgs[s], epoch,
+                                            self.optim_cfgs[s], self.lr[s], self._steps,
+                                            None if val_results is None else val_results[s], entry)
             out.append(write_checkpoint(d, ck, epoch, is_best))
         return out
 
     def load_model(self, directories: Sequence[str], epoch: Optional[int] = None) -> None:
         """Reads S files written by standalone `RPO(cfg.K = K_s)` runs (or by `save_model`).  One loop runs all members:
         files of different epochs are refused."""
-        if len(directories) != self.n_runs:
-            raise ValueError(f"{len(directories)} directories for {self.n_runs} members")
-        got = [read_member_checkpoint(d, epoch, self.member_cfgs[s]) for s, d in enumerate(directories)]
-        epochs = [int(ck.get("epoch", 0)) for _, ck in got]
-        if any(e != epochs[0] for e in epochs):
-            raise ValueError(f"RPOSweep.load_model: the checkpoints are of epochs {epochs}; one loop runs all members")
+        self._check_directories(directories)
+        got = [_members.read_member_checkpoint(d, epoch, self.member_cfgs[s]) for s, d in enumerate(directories)]
+        ep = self._files_epoch([ck for _, ck in got], "load_model")
         self._load_states(got, lambda s: dict(param_shapes=self._shapes(s), s=s,
                                               scatter=lambda d, r: d.copy_(flat_to_member_row(r, *self._dims(s)))))
         eng = self.engine
         eng.m_params.copy_(torch.stack([flat_to_member_row(p, *self._dims(s)) for s, (p, _) in enumerate(got)]))
-        self.epoch = epochs[0]
+        self.epoch = ep
         self.lr = [lr_at_epoch(oc, self.epoch) for oc in self.optim_cfgs]
         self._opt.set_epoch(self.epoch)
         if self._found_inf is not None:                         # the skip counts are the resumed run's own
