@@ -333,7 +333,21 @@ int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* k, const vo
                         void* out, int64_t ldo, int dtype, int B, int H, int N, int Kp, int sets,
                         const int32_t* first_image, float scale, void* stream);
 
-/* Backward of the above for the prompt rows only: dq[B*Kp, lddq] given da[B*Kp, ldda].
+/* (ABI 8 addition) The backward twin of rpo_attn_prompt_fwd: the prompt queries of `sets` prompt sets that were trained on
+ * ONE shared batch (rpo_amd/engine_prompt_train.py).  dq = scale * (U - delta W) given da = d(loss)/d(out), with P recomputed
+ * from q and K -- nothing saved by the forward -- and no dK / dV: the keys and values belong to frozen tokens.
+ *   q_rows, da, dq : [sets * B * Kp, ldq / ldda / lddq] act dtype, set-major as in rpo_attn_prompt_fwd
+ *   k, v, ldkv, first_image : as in rpo_attn_prompt_fwd (first_image is read on the device; NULL = 0)
+ * One workgroup per (image, head) stages the image's K / V once and serves the 32-query tiles of all sets, one wave per
+ * tile walking all key tiles (no cross-wave partials; fixed summation order, no atomics).  Per query the bits do not depend
+ * on `sets`, on the query's place in a tile or on the other queries of the launch.  head_dim 64, N <= 288 (above:
+ * RPO_E_SHAPE, nothing launched), any sets * Kp within rpo_attn_prompt_fwd's limits.  Columns [H * 64, lddq) of `dq` are
+ * not touched. */
+int rpo_attn_prompt_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                        const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype,
+                        int B, int H, int N, int Kp, int sets, const int32_t* first_image, float scale, void* stream);
+
+/* Backward of rpo_attn_readonly_fwd for the prompt rows only: dq[B*Kp, lddq] given da[B*Kp, ldda].
  * q_rows points at the first PROMPT row of q; k, v at the first frozen row.  dK/dV are not
  * produced: keys/values belong to frozen tokens.  Kp <= 128, N <= 1025 (N > 288: the keys in chunks of 256, one pass for
  * the row statistics and one for delta and dS.K; fixed summation order, no atomics). */

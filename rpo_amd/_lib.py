@@ -146,6 +146,8 @@ SIGNATURES = {
                                       c_f32, c_i32, c_vp]),
     "rpo_attn_prompt_fwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                     c_vp, c_f32, c_vp]),
+    "rpo_attn_prompt_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                    c_i32, c_vp, c_f32, c_vp]),
     "rpo_attn_readonly_bwd_proj": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32,
                                            c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "rpo_attn_readonly_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32,

@@ -1862,6 +1862,151 @@ int launch_prompt_fwd(const void* q, int64_t ldq, const void* k, const void* v, 
   return rpo_launch_status();
 }
 
+// ---- backward, prompt queries of SEVERAL prompt sets over one image's frozen K / V (rpo_attn_prompt_bwd) ----------------
+// The backward twin of attn_prompt_fwd_kernel, same row layout (set-major: row (s B + b) Kp + j) and the same `first`:
+// dq = scale * (U - delta W) as attn_bwd_body defines it, P recomputed from q and K, nothing saved by the forward, no dK / dV
+// (the keys and values belong to frozen tokens).  One workgroup of eight waves per (image, head) stages that image's K and V
+// row-major ONCE (16-bit: rows padded to 144 B, 2 x K_BYTES = 82 944 B at NT = 9; f32: [NPAD][65] floats twice, 149 760 B)
+// and serves the sets * Kp queries of the image as 32-query tiles.
+// Shape, ALL storage types: one wave walks ALL key tiles of its own query tile -- twice: the row maximum, the row sum and
+// delta = sum P o dP online, then dS = P o (dP - delta) and its contraction with K -- so everything of a query is complete in
+// the wave's registers.  dS . K IS U - delta W; with delta known before the contraction the 16-bit modes round P o (dP - delta)
+// ONCE instead of rounding P o dP and P separately and cancelling U against delta W afterwards (that arrangement measured
+// 2.97e-3 of the reference's maximum in f16 at N = 5, Kp = 1, outside the op-level bound of 2e-3), and W's accumulators and
+// MFMAs are not needed: the second dP product of pass 1 costs what W's contraction cost.  attn_bwd_body instead spreads the key
+// tiles of ONE query tile over four waves and combines their partials (66 560 B) through the dead staging area; here the
+// staging must stay live across the query tiles.  In the 16-bit modes the partials would fit beside it (149 504 B), in f32 at
+// NT = 9 they do not, and with the query tiles of several sets to hand out the waves are busy without splitting a tile:
+// no partials, no barrier after the staging one, one code path for the three storage types.  (One set of Kp <= 32 is one
+// busy wave per workgroup: the single-set step keeps rpo_attn_readonly_bwd.)
+// A lane holds ONE query (S^T = K . Q^T; the columns of every MFMA here are queries), the key loop's trip count depends on N
+// alone and no branch looks at another lane's data: a query's bits depend neither on `sets`, nor on its position in a tile,
+// nor on its neighbours -- set s of a launch is bit for bit the launch of that set alone.  Fixed summation order (key tiles
+// ascending), no atomics.
+template <typename T, int NT>
+__global__ __launch_bounds__(512) void attn_prompt_bwd_kernel(const T* q, int64_t ldq, const T* k, const T* v, int64_t ldkv,
+                                                           const T* da, int64_t ldda, T* dq, int64_t lddq, int B, int H,
+                                                           int N, int Kp, int sets, const int32_t* first, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using L = AL<T, NT>;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, l31 = lane & 31;
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const int64_t img = (int64_t)(first != nullptr ? *first : 0) + b;
+  const T* kb = k + img * N * ldkv + h * 64;
+  const T* vb = v + img * N * ldkv + h * 64;
+  char* ks = smem;
+  char* vs = smem + L::K_BYTES;
+  const int Q = sets * Kp;                               // this image's queries, set-major
+  const int qt_end = (Q + 31) >> 5;
+  auto qrow = [&](int qt) -> int64_t {                   // (queries past Q: the last one again, computed and not stored)
+    const int vq = min(qt * 32 + l31, Q - 1);
+    const int s = vq / Kp, j = vq - s * Kp;
+    return ((int64_t)s * B + b) * Kp + j;
+  };
+  RowFrag<T> qf, df;
+  if constexpr (sizeof(T) == 2) {                        // the first tile's operands ride in the staging loads' round trip
+    const int64_t r0 = qrow(wave);
+    qf.load(q + r0 * ldq + h * 64, half);
+    df.load(da + r0 * ldda + h * 64, half);
+    stage2_bf16<NT, 512>(ks, vs, reinterpret_cast<const bf16_t*>(kb), reinterpret_cast<const bf16_t*>(vb), ldkv, N, tid);
+  } else {
+    stage_rows_f32<NT, 512>(reinterpret_cast<float*>(ks), kb, ldkv, N, tid);
+    stage_rows_f32<NT, 512>(reinterpret_cast<float*>(vs), vb, ldkv, N, tid);
+  }
+  __syncthreads();                                       // the only barrier: K / V are read-only from here on
+  bf16x8_t i0, i1;
+  if constexpr (sizeof(T) == 2) { i0 = ident_frag<T>(0, l31, half); i1 = ident_frag<T>(1, l31, half); }
+  const int nkt = min(NT, (N + 31) >> 5);                // key tiles that hold a key (rows past N are staged as zeros)
+  for (int qt = wave; qt < qt_end; qt += 8) {
+    int l31v = l31;                                      // (keeps the K / V ds_reads inside the loops: attn_fwd_kernel)
+    asm volatile("" : "+v"(l31v));
+    const int vq = qt * 32 + l31;
+    const int64_t grow = qrow(qt);
+    if (sizeof(T) != 2 || qt != wave) {
+      qf.load(q + grow * ldq + h * 64, half);
+      df.load(da + grow * ldda + h * 64, half);
+    }
+    // pass 1: row maximum, sum of the scores and delta = sum P o dP (dP = da . V^T), online over the key tiles in ascending order
+    float m = -INFINITY, l = 0.f, dsum = 0.f;
+#pragma unroll 1
+    for (int t = 0; t < nkt; ++t) {
+      f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
+      const f32x16_t dp = tile_times_frag<T>(vs, t, df, l31v, half);   // (V rows past N are zeros: finite)
+      const float mn = fmaxf(m, mask_and_max(sc, t, N, half));     // finite from tile 0 on (N >= 1)
+      const float alpha = exp_scalar<T>(m - mn, scale);            // first tile: exp(-inf) = 0
+      l = l * alpha + exp_tile<T>(sc, mn, scale);
+      float dt_ = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dt_ = fmaf(sc[r], dp[r], dt_);  // (exp = 0 on padded keys)
+      dsum = dsum * alpha + dt_;
+      m = mn;
+    }
+    l += __shfl_xor(l, 32, 64);
+    dsum += __shfl_xor(dsum, 32, 64);
+    const float inv = 1.0f / l;
+    const float delta = dsum * inv;
+    // pass 2: dS = P o (dP - delta) in fp32, rounded ONCE to the storage type (16-bit modes), and U' = dS . K
+    f32x16_t u[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) u[dt][r] = 0.f;
+#pragma unroll 1
+    for (int t = 0; t < nkt; ++t) {
+      f32x16_t pt = tile_times_frag<T>(ks, t, qf, l31v, half);
+      (void)mask_and_max(pt, t, N, half);
+      (void)exp_tile<T>(pt, m, scale);
+      const f32x16_t dp = tile_times_frag<T>(vs, t, df, l31v, half);
+      if constexpr (sizeof(T) == 2) {
+        const char* krow = ks + (32 * t + l31v) * 144 + half * 16;
+        bf16x8_t krows[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) krows[kk] = *reinterpret_cast<const bf16x8_t*>(krow + kk * 32);
+        float ds[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ds[r] = (pt[r] * inv) * (dp[r] - delta);   // (P = 0 on padded keys)
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          bf16x8_t ktf[2];
+          transpose_tile<T>(krows, dt, i0, i1, ktf);     // K^T fragments of this key tile, in registers
+#pragma unroll
+          for (int g2 = 0; g2 < 2; ++g2) u[dt] = mfma16<T>(ktf[g2], pack8<T>(ds + 8 * g2), u[dt]);
+        }
+      } else {
+        f32x16_t ds;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ds[r] = (pt[r] * inv) * (dp[r] - delta);
+        contract_keys<T, NT>(ks, t, ds, u, l31v, half);
+      }
+    }
+    if (vq < Q) {
+      T* orow = dq + grow * lddq + h * 64;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, scale * u[dt][4 * g], scale * u[dt][4 * g + 1],
+                        scale * u[dt][4 * g + 2], scale * u[dt][4 * g + 3]);
+    }
+  }
+}
+
+template <typename T, int NT>
+int launch_prompt_bwd(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* da, int64_t ldda,
+                      void* dq, int64_t lddq, int B, int H, int N, int Kp, int sets, const int32_t* first, float scale,
+                      hipStream_t s) {
+  static rpo_lds_mask_t lds_ok{0};
+  auto kern = attn_prompt_bwd_kernel<T, NT>;
+  constexpr int bytes = AL<T, NT>::BWD_STAGE;
+  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
+  hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), bytes, s, static_cast<const T*>(q), ldq, static_cast<const T*>(k),
+                     static_cast<const T*>(v), ldkv, static_cast<const T*>(da), ldda, static_cast<T*>(dq), lddq, B, H, N, Kp,
+                     sets, first, scale);
+  return rpo_launch_status();
+}
+
 template <typename T, int NT>
 int launch_bwd(const void* qr, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* da,
                int64_t ldda, void* dq, int64_t lddq, int B, int H, int N, int Kp, float scale, hipStream_t s) {
@@ -2178,6 +2323,32 @@ extern "C" int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* 
   }
   if (N <= 224) return launch_prompt_fwd<float, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
   return launch_prompt_fwd<float, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+}
+
+extern "C" int rpo_attn_prompt_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
+                                   const void* da, int64_t ldda, void* dq, int64_t lddq, int dtype, int B, int H, int N,
+                                   int Kp, int sets, const int32_t* first_image, float scale, void* stream) {
+  if (!q_rows || !k || !v || !da || !dq || B <= 0 || H <= 0 || N <= 0 || Kp <= 0 || sets <= 0) return RPO_E_BADARG;
+  if (N > 288 || (int64_t)sets * Kp > (1 << 24) || (int64_t)sets * Kp * B > INT32_MAX || (int64_t)B * H > INT32_MAX)
+    return RPO_E_SHAPE;
+  if (dtype != RPO_F32 && dtype != RPO_BF16 && dtype != RPO_F16) return RPO_E_DTYPE;
+  const int esz = dtype == RPO_F32 ? 4 : 2;
+  if (!aligned16(q_rows) || !aligned16(k) || !aligned16(v) || !aligned16(da) || !ok_ld(ldq, esz) || !ok_ld(ldkv, esz) ||
+      !ok_ld(ldda, esz) || reinterpret_cast<uintptr_t>(dq) % (4 * esz) || (lddq * esz) % (4 * esz) ||
+      reinterpret_cast<uintptr_t>(first_image) % 4) return RPO_E_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define RPO_PB(T_, NT_) return launch_prompt_bwd<T_, NT_>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, sets, first_image, scale, s)
+  if (dtype == RPO_BF16) {
+    if (N <= 224) RPO_PB(bf16_t, 7);
+    RPO_PB(bf16_t, 9);
+  }
+  if (dtype == RPO_F16) {
+    if (N <= 224) RPO_PB(f16_t, 7);
+    RPO_PB(f16_t, 9);
+  }
+  if (N <= 224) RPO_PB(float, 7);
+  RPO_PB(float, 9);
+#undef RPO_PB
 }
 
 extern "C" int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v,

@@ -40,6 +40,7 @@ from .engine_coop_sweep import CoopSweepEngineMixin
 from .engine_lp import LpEngineMixin
 from .engine_multi import MultiEngineMixin
 from .engine_prompt_rows import PromptRowsEngineMixin
+from .engine_prompt_train import PromptTrainEngineMixin
 from .engine_rn import RnEngineMixin
 from .engine_text import TextEncodeEngineMixin
 
@@ -78,7 +79,8 @@ class _Block:
 
 
 class Engine(CoopEngineMixin, PrefixTrainEngineMixin, ConditionalEvalEngineMixin, CocoopMultiEngineMixin, CoopSweepEngineMixin,
-             LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, TextEncodeEngineMixin, ClassSetEngineMixin):
+             LpEngineMixin, RnEngineMixin, MultiEngineMixin, PromptRowsEngineMixin, PromptTrainEngineMixin, TextEncodeEngineMixin,
+             ClassSetEngineMixin):
     """The product engine: the RPO step, its eval branch, plain CLIP, and (engine_coop.CoopEngineMixin) the sibling
     trainers.  The measured-slower experiments of rounds 3 / 4 are NOT here: rpo_amd/experimental.py subclasses this class
     and overrides the hooks marked "experiment hook" below; `make_engine` returns that subclass only under

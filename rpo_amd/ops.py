@@ -429,6 +429,24 @@ def attn_prompt_fwd(q_rows, k, v, out, B: int, H: int, N: int, Kp: int, sets: in
     return out
 
 
+def attn_prompt_bwd(q_rows, k, v, da, dq, B: int, H: int, N: int, Kp: int, sets: int, first_image=None, scale: float = 0.125,
+                    kv_images: Optional[int] = None):
+    """The backward twin of `attn_prompt_fwd` (rpo_attn_prompt_bwd): dq of the prompt queries of `sets` prompt sets (q_rows /
+    da / dq: [sets*B*Kp, .], set-major) over the frozen K / V of images first_image[0] + b; no dK / dV.  The caller vouches
+    that first_image + B <= kv_images, as there."""
+    assert q_rows.dtype == k.dtype == v.dtype == da.dtype == dq.dtype and _ld(k) == _ld(v)
+    rows = sets * B * Kp
+    assert q_rows.shape[0] >= rows and da.shape[0] >= rows and dq.shape[0] >= rows
+    assert min(q_rows.shape[1], da.shape[1], dq.shape[1], k.shape[1], v.shape[1]) >= H * 64
+    kv_images = min(k.shape[0], v.shape[0]) // N if kv_images is None else kv_images
+    assert B <= kv_images and min(k.shape[0], v.shape[0]) >= kv_images * N, "k / v hold fewer than B images of N rows"
+    assert first_image is None or (first_image.dtype == torch.int32 and first_image.is_cuda and first_image.numel() == 1)
+    check(_lib.load().rpo_attn_prompt_bwd(q_rows.data_ptr(), _ld(q_rows), k.data_ptr(), v.data_ptr(), _ld(k), da.data_ptr(),
+                                          _ld(da), dq.data_ptr(), _ld(dq), dtype_code(dq.dtype), B, H, N, Kp, sets,
+                                          _p(first_image), scale, _stream()), "rpo_attn_prompt_bwd")
+    return dq
+
+
 def attn_readonly_bwd_proj(q_rows, k, v, dx, w_out_t, dq, B: int, H: int, N: int, Kp: int, scale: float = 0.125):
     """attn_readonly_bwd with the d out-proj GEMM folded in: dx = gradient of the out-proj output (act dtype)."""
     assert q_rows.dtype == k.dtype == v.dtype == dx.dtype == w_out_t.dtype == dq.dtype
