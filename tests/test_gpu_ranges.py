@@ -799,13 +799,34 @@ def _trained_like(sd, cfg):
         sd[key][[d // 3, 2 * d // 3 + 1]] *= 0.05
 
 
+def block0_regime(ref, cfg, image):
+    """The regime, from the oracle's block-0 values of the image tower on the first two images: (residual channels whose
+    largest |value| after block 0 exceeds 100, the largest |value|, share of attention rows with a maximum weight above
+    0.9)."""
+    import torch.nn.functional as F
+    from oracle.rpo_oracle import layer_norm, res_block
+    with torch.no_grad():
+        img = torch.from_numpy(image)[:2]
+        emb = F.conv2d(img, ref.sd["visual.conv1.weight"], stride=cfg.patch).flatten(2).permute(0, 2, 1)
+        x = torch.cat([ref.sd["visual.class_embedding"].repeat(2, 1, 1), emb], 1) + ref.sd["visual.positional_embedding"]
+        x = torch.cat([x, ref.img_prompt.detach().repeat(2, 1, 1)], 1)
+        x = layer_norm(x, ref.sd["visual.ln_pre.weight"], ref.sd["visual.ln_pre.bias"]).permute(1, 0, 2)
+        blk = ref.img_blocks[0]
+        h = layer_norm(x, blk["ln_1.weight"], blk["ln_1.bias"])
+        qk = h @ blk["attn.in_proj_weight"][:2 * cfg.d_v].t() + blk["attn.in_proj_bias"][:2 * cfg.d_v]
+        qh = qk[..., :cfg.d_v].reshape(qk.shape[0], -1, HD).transpose(0, 1)
+        kh = qk[..., cfg.d_v:].reshape(qk.shape[0], -1, HD).transpose(0, 1)
+        pmax = torch.softmax(qh @ kh.transpose(1, 2) * SCALE + ref.visual_mask, -1).amax(-1)
+        x1 = res_block(x, blk, ref.heads_v, ref.visual_mask)
+    return int((x1.abs().amax((0, 1)) > 100).sum()), x1.abs().max().item(), float((pmax > 0.9).float().mean())
+
+
 @pytest.mark.parametrize("B", [4, 32])
 def test_model_in_trained_regime(B):
     """CustomCLIP against OracleRPO (loss, both prompt gradients, eval logits) in f32 / bf16 / f16 at the model tests'
     bounds, on weights perturbed into the trained regime; the oracle's own block-0 values first show that the regime is
     real (residual channels above 100, attention rows with a maximum weight above 0.9)."""
-    import torch.nn.functional as F
-    from oracle.rpo_oracle import OracleRPO, layer_norm, res_block
+    from oracle.rpo_oracle import OracleRPO
     from rpo_amd import synth
     from rpo_amd.config import vit_b16
     from rpo_amd.custom_clip import CustomCLIP
@@ -820,22 +841,8 @@ def test_model_in_trained_regime(B):
     ref.set_prompts(tp, ip)
     assert ref.len_prompts.numel() == 19
     # the regime, from the oracle's block-0 values of the image tower
-    with torch.no_grad():
-        img = torch.from_numpy(image)[:2]
-        emb = F.conv2d(img, ref.sd["visual.conv1.weight"], stride=cfg.patch).flatten(2).permute(0, 2, 1)
-        x = torch.cat([ref.sd["visual.class_embedding"].repeat(2, 1, 1), emb], 1) + ref.sd["visual.positional_embedding"]
-        x = torch.cat([x, ref.img_prompt.detach().repeat(2, 1, 1)], 1)
-        x = layer_norm(x, ref.sd["visual.ln_pre.weight"], ref.sd["visual.ln_pre.bias"]).permute(1, 0, 2)
-        blk = ref.img_blocks[0]
-        h = layer_norm(x, blk["ln_1.weight"], blk["ln_1.bias"])
-        qk = h @ blk["attn.in_proj_weight"][:2 * cfg.d_v].t() + blk["attn.in_proj_bias"][:2 * cfg.d_v]
-        qh = qk[..., :cfg.d_v].reshape(qk.shape[0], -1, HD).transpose(0, 1)
-        kh = qk[..., cfg.d_v:].reshape(qk.shape[0], -1, HD).transpose(0, 1)
-        pmax = torch.softmax(qh @ kh.transpose(1, 2) * SCALE + ref.visual_mask, -1).amax(-1)
-        x1 = res_block(x, blk, ref.heads_v, ref.visual_mask)
-    big = int((x1.abs().amax((0, 1)) > 100).sum())
-    sharp = float((pmax > 0.9).float().mean())
-    print(f"[trained regime B{B}] block 0: {big} residual channels above 100, max |x| {x1.abs().max().item():.1f}; "
+    big, xmax, sharp = block0_regime(ref, cfg, image)
+    print(f"[trained regime B{B}] block 0: {big} residual channels above 100, max |x| {xmax:.1f}; "
           f"{100 * sharp:.1f} % of attention rows with a max weight above 0.9")
     assert big >= 1 and sharp > 0.0
     out, gt, gi = ref.loss_and_grads(image, label)
