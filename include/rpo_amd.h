@@ -368,7 +368,9 @@ int rpo_attn_readonly_bwd_proj(const void* q_rows, int64_t ldq, const void* k, c
  * causal = 0: every row reads keys [0, len[c])            (prompt rows, trainers/rpo.py:146-149:
  *             causal AND col < len_c, and prompts sit at positions >= len_c)
  * causal = 1: row t reads keys [0, min(t + 1, len[c]))     (the one-off pass over the frozen tokens)
- * len: int32 device array [n_cls].  Lmax <= 128.
+ * len: int32 device array [n_cls].  Lmax <= 128.  len[c] >= 1 is the caller's duty: an empty class has no key to
+ * normalise over and both kernels write NaN rows for it (no trainer forms one: every prompt holds SOS and EOT).
+ * len[c] > Lmax reads as Lmax (both kernels clamp it; the cache has no row past Lmax).
  * Kernels: 16-bit storage, causal = 0, rows <= 64, Lmax <= 96, 16-byte aligned rows -- the training path's shapes -- run as
  * ONE WAVE per (class, head) on the matrix cores (fp32 accumulation and softmax; P and dS rounded to the storage type for
  * the second contraction, as in rpo_attn_readonly_fwd); everything else as fp32 VALU arithmetic.  Same meaning either way. */
