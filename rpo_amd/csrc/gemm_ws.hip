@@ -39,19 +39,47 @@
 
 namespace {
 
+constexpr int WS_MAX_SPLIT = 4;          // k-splits whose chunk bounds fit WsParams::kb (the engine uses 1 .. 4)
+
+// The front of the block is everything a workgroup needs before its first operand request, laid out contiguously so that
+// the kernel fetches it with one group of scalar loads behind one wait.  Whatever is the same for every workgroup of a
+// launch is computed HERE, once, by the launcher (ws_prepare / ws_launch_t): the prologue is a dependent scalar chain in
+// front of the first round trip of a launch that is mostly latency, and it used to hold six integer divisions (two of them
+// 64-bit) and three kernel-argument round trips.
 struct WsParams {
-  const char* A; int64_t lda;            // [M, K] act dtype, row-major; lda in elements
+  const char* A;                         // [M, K] act dtype, row-major
   const char* Wp;                        // packed weights (rpo_gemm_ws_pack)
-  char* C; int64_t ldc;
+  uint32_t lda2;                         // row stride of A in bytes
+  uint32_t a_last;                       // (M - 1) * lda2: byte offset of the last row (the clamp of a partial m-tile)
+  uint32_t wstride;                      // K * 64: bytes between the packed 32-row weight blocks
+  uint32_t nb_last;                      // N / 32 - 1
+  uint32_t tiles_m, tiles_n;
+  uint32_t rcp_m, rcp_n;                 // ws_rcp(tiles_m), ws_rcp(tiles_n): see ws_divmod
+  uint32_t nwg, xcd_q, xcd_r;            // grid size, nwg / 8, nwg % 8
+  uint32_t kb[WS_MAX_SPLIT + 1];         // 64-deep k-chunk bounds of the k-splits: kb[s] = (K / 64) * s / split_k
   int M, N, K;
-  int tiles_m, tiles_n, split_k; int64_t split_stride;
+  int ln_groups;                         // K / ln_group (LN fold, consumer side)
+  char* C; int64_t ldc;
+  int64_t split_stride;
   const float* bias;
   const float* resid; int64_t ldr;
   char* aux; int64_t ldaux; int aux_row0; int aux_mode;   // as rpo_gemm_args (aux_mode 1: 16-bit derivative)
   char* out2; int64_t ldout2; float* stats_out;            // BIAS_RESID producer side of the LayerNorm fold (64-col groups)
-  const float* stats_in; const float* ln_colsum; float ln_eps; int ln_group;
+  const float* stats_in; const float* ln_colsum; float ln_eps;
   const char* pf_ptr; int64_t pf_bytes;
+  int split_k;                           // launcher only (the kernel reads kb)
 };
+
+// x / d and x % d for a launch constant d without a division on the device: the launcher passes r = floor(2^32 / d)
+// (2^32 - 1 for d = 1), and mulhi(x, r) is x / d or one less for EVERY 32-bit x and d >= 1 -- with 2^32 = r d + e,
+// 0 <= e <= d, x r / 2^32 = x / d - x e / (d 2^32) and the last term is below x / 2^32 < 1 -- so one compare-and-fix
+// makes it exact.  Uniform operands: s_mul_hi_u32 + s_mul_i32 + four more SALU.
+static inline uint32_t ws_rcp(uint32_t d) { return d <= 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / d); }
+__device__ __forceinline__ void ws_divmod(uint32_t x, uint32_t d, uint32_t rcp, uint32_t& quot, uint32_t& rem) {
+  uint32_t qq = __umulhi(x, rcp), rr = x - qq * d;
+  if (rr >= d) { rr -= d; ++qq; }
+  quot = qq; rem = rr;
+}
 
 template <int N> __device__ __forceinline__ void ws_wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -103,26 +131,47 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const WsParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
   RPO_STAMP(0); RPO_STAMP_RT(62);
+  constexpr bool IS_LN = EPI == RPO_EPI_LN_BIAS || EPI == RPO_EPI_LN_BIAS_QGELU;
+  constexpr bool IS_QG = EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_LN_BIAS_QGELU;
+  constexpr bool HAS_BIAS = EPI == RPO_EPI_BIAS || EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_BIAS_RESID || IS_LN;
+  constexpr bool PRE_F32 = EPI == RPO_EPI_BIAS_RESID;               // second [M, N] operand of the epilogue: the residual,
+  constexpr bool PRE_AUX = EPI == RPO_EPI_QGELU_BWD;                // or the saved QuickGELU operand
+
+  // ---- ONE kernel-argument fetch.  Every scalar that a request of the prologue depends on -- the k-loop's operands and the
+  //      epilogue's, which are requested first -- is an input of one empty asm statement at the top, so the compiler has
+  //      all of them in scalar registers behind ONE wait.  Left to itself it fetches the block in up to three groups, each
+  //      behind its own wait, the later ones where a first use happens to be (p.A: inside the chunk-count branches below).
+  //      What an instance does not read is a constant here (a move, no fetch).  Inputs only: the values stay what the
+  //      compiler knows them to be (kernel-argument pointers = global memory).
+  static_assert(WS_MAX_SPLIT == 4, "the statement below names kb[0 .. 4]");
+  asm volatile("" ::"s"(p.A), "s"(p.Wp), "s"(p.lda2), "s"(p.a_last), "s"(p.wstride), "s"(p.nb_last), "s"(p.tiles_m),
+               "s"(p.tiles_n), "s"(p.rcp_m), "s"(p.rcp_n), "s"(p.xcd_q), "s"(p.xcd_r), "s"(p.kb[0]), "s"(p.kb[1]), "s"(p.kb[2]),
+               "s"(p.kb[3]), "s"(p.kb[4]), "s"(p.M), "s"(p.N), "s"(IS_LN ? p.ln_groups : 0), "s"(HAS_BIAS ? p.bias : nullptr),
+               "s"(IS_LN ? p.ln_colsum : nullptr), "s"(IS_LN ? p.stats_in : nullptr),
+               "s"(PRE_F32 ? reinterpret_cast<const char*>(p.resid) : PRE_AUX ? p.aux : nullptr),
+               "s"(PRE_F32 ? p.ldr : PRE_AUX ? p.ldaux : (int64_t)0), "s"(PRE_AUX ? p.aux_mode : 0));
 
   // ---- workgroup -> (m-tile, n-tile, k-split): XCD x = bid % 8 takes a contiguous run of the linear order
   //      ((split, n-tile), m-tile), m fastest
-  int tile_m, tile_n, ksl;
+  //      (XCD x starts at x * (nwg / 8) + min(x, nwg % 8)).  All of it scalar, on launch constants and blockIdx.x.
+  uint32_t tile_m, tile_n, ksl;
   {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-    const int wg = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-    tile_m = wg % p.tiles_m;
-    const int rest = wg / p.tiles_m;
-    tile_n = rest % p.tiles_n;
-    ksl = rest / p.tiles_n;
+    const uint32_t bid = blockIdx.x, xcd = bid & 7;
+    const uint32_t wg = xcd * p.xcd_q + min(xcd, p.xcd_r) + (bid >> 3);
+    uint32_t rest;
+    ws_divmod(wg, p.tiles_m, p.rcp_m, rest, tile_m);
+    ws_divmod(rest, p.tiles_n, p.rcp_n, ksl, tile_n);
   }
-  const int m0 = tile_m * CF::BM, n0 = tile_n * CF::BN;
-  // k-chunks (64 deep) of this workgroup, then of this wave
-  const int nch_all = p.K >> 6;
-  const int wc0 = (int)(((int64_t)nch_all * ksl) / p.split_k), wc1 = (int)(((int64_t)nch_all * (ksl + 1)) / p.split_k);
-  const int nwc = wc1 - wc0;
-  const int c_lo = wc0 + (nwc * wave) / 4, c_hi = wc0 + (nwc * (wave + 1)) / 4;
+  const int m0 = (int)(tile_m * CF::BM), n0 = (int)(tile_n * CF::BN);
+  // k-chunks (64 deep) of this workgroup (the launcher's table, picked by compares: no dependent load), then of this wave
+  uint32_t wc0 = p.kb[0], wc1 = p.kb[1];
+#pragma unroll
+  for (uint32_t s = 1; s < (uint32_t)WS_MAX_SPLIT; ++s)
+    if (ksl >= s) { wc0 = p.kb[s]; wc1 = p.kb[s + 1]; }
+  const uint32_t nwc = wc1 - wc0, uwave = (uint32_t)wave;
+  const int c_lo = (int)(wc0 + ((nwc * uwave) >> 2)), c_hi = (int)(wc0 + ((nwc * (uwave + 1)) >> 2));
   const int nc = c_hi - c_lo;
+  const int G = IS_LN ? p.ln_groups : 1;
 
   // ---- addresses -----------------------------------------------------------------------------------------------
   // activation chunk: load j covers tile rows 8j .. 8j+7; lane -> row 8j + (lane >> 3), 16-B chunk lane & 7 of the
@@ -130,18 +179,21 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const WsParams p) {
   uint32_t aoff[CF::DA];
   const int arow = lane >> 3;
   const uint32_t apark = (uint32_t)(arow * 128 + (((lane & 7) ^ ((arow >> 1) & 7)) << 4));   // (8j keeps (row >> 1) & 3; see below)
+  // Rows past M re-read row M - 1: min(row, M - 1) * lda2 = min(row * lda2, a_last), so ONE per-lane multiply forms the
+  // first row's offset and the others are an add and a min away (the launcher keeps (M + 95) * lda2 below 2^32)
+  {
+    const uint32_t r0 = min((uint32_t)(m0 + arow) * p.lda2, p.a_last), step = 8 * p.lda2, col = (uint32_t)(lane & 7) * 16;
 #pragma unroll
-  for (int j = 0; j < CF::DA; ++j)
-    aoff[j] = (uint32_t)min(m0 + 8 * j + arow, p.M - 1) * (uint32_t)(p.lda * 2) + (lane & 7) * 16;
+    for (int j = 0; j < CF::DA; ++j) aoff[j] = min(r0 + (uint32_t)j * step, p.a_last) + col;
+  }
   char* const ring = smem + wave * CF::WAVE_RING;
-  // weight fragments: block nb = n0 / 32 + tn (clamped: a partial last n-tile recomputes the last block), k-step ks
-  const int KS = p.K >> 4;
+  // weight fragments: block nb = n0 / 32 + tn (clamped: a partial last n-tile recomputes the last block), k-step ks.
+  // One 64-bit base for block n0 / 32 (scalar), then a clamped 32-bit offset per tn (tn * wstride < 2^32: ws_prepare)
+  const uint32_t nb0 = tile_n * NT, nb_room = p.nb_last - nb0;
+  const char* const wb0 = p.Wp + (uint64_t)nb0 * p.wstride + (uint32_t)lane * 16;
   const char* wb[NT];
 #pragma unroll
-  for (int tn = 0; tn < NT; ++tn) {
-    const int nb = min(n0 / 32 + tn, p.N / 32 - 1);
-    wb[tn] = p.Wp + ((int64_t)nb * KS * 64 + lane) * 16;
-  }
+  for (int tn = 0; tn < NT; ++tn) wb[tn] = wb0 + min((uint32_t)tn, nb_room) * p.wstride;
   // fragment reads: tile row 32 tm + l31, k-step s of the chunk = 16-B chunks (2 s + half) ^ swizzle
   const int sw = (l31 >> 1) & 7;
   uint32_t frag_off[4];
@@ -158,13 +210,9 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const WsParams p) {
 
   // ---- prologue.  Everything the epilogue wants from memory is requested FIRST (it is then older than every load of the
   //      k-loop, whose counted waits retire it on the way), then the ring, then the first weight chunk.
-  constexpr bool IS_LN = EPI == RPO_EPI_LN_BIAS || EPI == RPO_EPI_LN_BIAS_QGELU;
-  constexpr bool IS_QG = EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_LN_BIAS_QGELU;
-  constexpr bool HAS_BIAS = EPI == RPO_EPI_BIAS || EPI == RPO_EPI_BIAS_QGELU || EPI == RPO_EPI_BIAS_RESID || IS_LN;
   float2* const row_stats = reinterpret_cast<float2*>(smem + CF::SMEM - CF::STATS_BYTES);
   // LayerNorm fold, consumer side: the producer's partial statistics of tile row `tid` (<= 16 groups), finished after the loop
   float2 lnp[IS_LN ? 16 : 1];
-  const int G = IS_LN ? p.K / p.ln_group : 1;
   if constexpr (IS_LN) {
     if (tid < CF::BM) {
       const float2* ps = reinterpret_cast<const float2*>(p.stats_in) + (int64_t)min(m0 + tid, p.M - 1) * G;
@@ -176,8 +224,6 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const WsParams p) {
   // of every 32-column group j)
   const int row8 = lane >> 3, c8 = lane & 7;
   // second [M, N] operand of the epilogue (residual / saved QuickGELU operand)
-  constexpr bool PRE_F32 = EPI == RPO_EPI_BIAS_RESID;
-  constexpr bool PRE_AUX = EPI == RPO_EPI_QGELU_BWD;
   // raw bits: a float4 of fp32 values (residual / fp32 pre-activation: all four words) or four 16-bit derivatives (.x, .y)
   typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
   typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
@@ -314,7 +360,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ws_kernel(const WsParams p) {
     const bool has = p.pf_ptr != nullptr;
     const char* base = has ? p.pf_ptr : p.Wp;
     const int64_t lines = has ? max(p.pf_bytes >> 7, (int64_t)1) : 1;
-    const int64_t stride = (int64_t)gridDim.x * CF::THREADS;
+    const int64_t stride = (int64_t)p.nwg * CF::THREADS;
     const int64_t i0 = (int64_t)blockIdx.x * CF::THREADS + tid;
     const char* t0 = base + (min(i0, lines - 1) << 7);
     const char* t1 = base + (min(i0 + stride, lines - 1) << 7);
@@ -486,9 +532,13 @@ int ws_launch_t(WsParams& p, hipStream_t s) {
   static rpo_lds_mask_t lds_ok{0};
   auto kern = gemm_ws_kernel<T, TOut, EPI, CF>;
   if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), CF::SMEM, &lds_ok)) return rc;
-  p.tiles_m = (p.M + CF::BM - 1) / CF::BM;
-  p.tiles_n = (p.N + CF::BN - 1) / CF::BN;
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n * p.split_k), dim3(CF::THREADS), CF::SMEM, s, p);
+  p.tiles_m = (uint32_t)((p.M + CF::BM - 1) / CF::BM);
+  p.tiles_n = (uint32_t)((p.N + CF::BN - 1) / CF::BN);
+  const uint64_t nwg = (uint64_t)p.tiles_m * p.tiles_n * (uint32_t)p.split_k;
+  if (nwg > 0x7fffffffull) return RPO_E_SHAPE;                      // (the grid limit; ws_divmod is exact below 2^32)
+  p.rcp_m = ws_rcp(p.tiles_m); p.rcp_n = ws_rcp(p.tiles_n);
+  p.nwg = (uint32_t)nwg; p.xcd_q = p.nwg >> 3; p.xcd_r = p.nwg & 7;
+  hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(CF::THREADS), CF::SMEM, s, p);
   return rpo_launch_status();
 }
 
@@ -531,7 +581,10 @@ static int ws_prepare(const rpo_gemm_args* a, WsParams& p, WsPlan& q) {
   const bool out16 = a->out_dtype == RPO_BF16 || a->out_dtype == RPO_F16;
   if (!in16 || (out16 && a->out_dtype != a->in_dtype) || (!out16 && a->out_dtype != RPO_F32)) return RPO_E_DTYPE;
   if (a->K % 64 != 0 || a->N % 32 != 0) return RPO_E_SHAPE;
-  if ((int64_t)a->M * a->lda * 2 >= (1ll << 32)) return RPO_E_SHAPE;             // 32-bit row offsets of the DMA
+  // 32-bit row offsets of the activation loads, formed by adding row steps up to the end of a partial last m-tile (at
+  // most 95 rows past M) before the clamp; 32-bit offsets between the weight blocks of a tile (at most two of K * 64 B)
+  if (a->lda < 0 || a->lda >= (1ll << 31) || ((int64_t)a->M + 95) * a->lda * 2 >= (1ll << 32)) return RPO_E_SHAPE;
+  if (a->K >= (1 << 24)) return RPO_E_SHAPE;
   const int epi = a->epilogue;
   const bool is_ln = epi == RPO_EPI_LN_BIAS || epi == RPO_EPI_LN_BIAS_QGELU;
   const bool needs_bias = epi == RPO_EPI_BIAS || epi == RPO_EPI_BIAS_QGELU || epi == RPO_EPI_BIAS_RESID || is_ln;
@@ -539,7 +592,8 @@ static int ws_prepare(const rpo_gemm_args* a, WsParams& p, WsPlan& q) {
   if (a->skip_row0 >= 0 || a->resid_hi != nullptr || a->resid_lo != nullptr || a->out_lo != nullptr || a->c_row0 != 0 ||
       a->seg_rows0 != 0 || a->seg_rows1 != 0) return RPO_E_SHAPE;
   const int split = a->split_k <= 1 ? 1 : a->split_k;
-  if (split > 1 && (epi != RPO_EPI_NONE || out16 || split > a->K / 64 || a->split_stride % 4 != 0)) return RPO_E_SHAPE;
+  if (split > 1 && (epi != RPO_EPI_NONE || out16 || split > a->K / 64 || split > WS_MAX_SPLIT || a->split_stride % 4 != 0))
+    return RPO_E_SHAPE;
   if (needs_bias && (a->bias == nullptr || !aligned16(a->bias))) return RPO_E_BADARG;
   if (is_ln) {
     const int g = a->ln_group == 0 ? 64 : a->ln_group;
@@ -566,18 +620,20 @@ static int ws_prepare(const rpo_gemm_args* a, WsParams& p, WsPlan& q) {
   q = ws_choose(a->M, a->N, a->K, split, epi, wants_stats, a->tile_config);
   if (q.mt == 0 || (wants_stats && q.nt != 2)) return RPO_E_SHAPE;
   p = WsParams{};
-  p.A = static_cast<const char*>(a->A); p.lda = a->lda;
-  p.Wp = static_cast<const char*>(a->W);
+  p.A = static_cast<const char*>(a->A); p.lda2 = (uint32_t)(a->lda * 2); p.a_last = (uint32_t)(a->M - 1) * p.lda2;
+  p.Wp = static_cast<const char*>(a->W); p.wstride = (uint32_t)a->K * 64; p.nb_last = (uint32_t)(a->N / 32 - 1);
   p.C = static_cast<char*>(a->C); p.ldc = a->ldc;
   p.M = a->M; p.N = a->N; p.K = a->K;
   p.split_k = split; p.split_stride = a->split_stride;
+  // workgroup ksl of split_k takes the 64-deep chunks kb[ksl] .. kb[ksl + 1]; the entries past split_k repeat the end
+  for (int s = 0; s <= WS_MAX_SPLIT; ++s) p.kb[s] = (uint32_t)(((int64_t)(a->K >> 6) * (s < split ? s : split)) / split);
   p.bias = a->bias; p.resid = a->resid; p.ldr = a->ldr;
   p.aux = static_cast<char*>(a->aux); p.ldaux = a->ldaux; p.aux_row0 = a->aux_row0;
   p.aux_mode = (a->aux != nullptr && a->aux_dtype != RPO_F32) ? 1 : 0;
   p.out2 = static_cast<char*>(a->out2); p.ldout2 = a->ldout2;
   p.stats_out = wants_stats ? a->ln_stats : nullptr;
   p.stats_in = is_ln ? a->ln_stats : nullptr;
-  p.ln_colsum = a->ln_colsum; p.ln_eps = a->ln_eps; p.ln_group = a->ln_group == 0 ? 64 : a->ln_group;
+  p.ln_colsum = a->ln_colsum; p.ln_eps = a->ln_eps; p.ln_groups = a->K / (a->ln_group == 0 ? 64 : a->ln_group);
   p.pf_ptr = static_cast<const char*>(a->prefetch);
   p.pf_bytes = a->prefetch == nullptr ? 0 : a->prefetch_bytes;
   if (p.pf_bytes < 0 || (p.pf_ptr != nullptr && reinterpret_cast<uintptr_t>(p.pf_ptr) % 4 != 0)) return RPO_E_BADARG;
