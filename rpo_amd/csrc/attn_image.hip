@@ -195,22 +195,12 @@ template <> struct RowFrag<float> {
 };
 
 // one 32x32 tile:  D[i][q] = M[32t + i][:] . frag[q][:]   (M = K or V rows, row-major in LDS)
-// SW (16-bit): rows of 128 B without padding, 16-B chunk c of row r at slot c ^ ((r >> 1) & 7) -- the layout an LDS-DMA
-// (lane-linear 1 KiB per wave instruction) can write; conflict-free for these reads as in gemm.hip
-template <typename T, bool SW = false>
+template <typename T>
 __device__ __forceinline__ f32x16_t tile_times_frag(const char* lds, int t, const RowFrag<T>& fr, int l31, int half) {
   f32x16_t acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  if constexpr (sizeof(T) == 2 && SW) {
-    const int row = 32 * t + l31, sw = (row >> 1) & 7;
-    const char* rowp = lds + row * 128;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(rowp + (((2 * ks + half) ^ sw) << 4));
-      acc = mfma16<T>(a, fr.f[ks], acc);
-    }
-  } else if constexpr (sizeof(T) == 2) {
+  if constexpr (sizeof(T) == 2) {
     const char* rowp = lds + (32 * t + l31) * 144 + half * 16;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -322,21 +312,12 @@ __device__ __forceinline__ void contract_keys(const char* m_lds, int t, const f3
 //    exps, sums and conversions of the others and the P.V MFMAs of a 16-key half without live keys are not issued
 //    (rem = 5: 4 of 16 v_exp, 2 of 4 P.V MFMAs); key tiles past N (N < 32 (NT - 1)) are skipped.  What is skipped is
 //    arithmetic on exact zeros (exp2(-inf) = 0, 0 x v, alpha = 1), so the result is BIT-IDENTICAL to the round-5 kernel.
-//  * -DRPO_ATTN_LAZY (A/B build, NOT the default): lazy rescale -- the running maximum m as a reference point that is moved
-//    (and l and the output tile rescaled: 18 multiplies + one v_exp) only when some row of the wave has outgrown it by more
-//    than TAU = 8 in log2 units.  Measured (profiles/r06_attn_variants.txt): kernel 15.6 vs 16.0 us, step -0.4 %; but the
-//    largest weight of a row is then no longer exactly 1.0 in the 16-bit P, and the op's max abs error grows 1.7x (bf16
-//    6.6e-3 vs 3.8e-3 on |out| <= 1.3; model-level logits error unchanged) -- not worth a looser op-level bound.
-#ifdef RPO_ATTN_LAZY
-constexpr float ATTN_TAU = 8.0f;
-#endif
+// (The build-time arms of rounds 4 to 6 -- lazy rescale, two key tiles per trip, K by LDS-DMA, the two-pass softmaxes, split
+//  units -- were measured and not adopted: DESIGN.md 5c and the profiles named there; git history has their code.)
 
 // moves the running maximum m to cover this tile's row maximum tm; returns the factor the running sum / output carry
 template <typename T>
 __device__ __forceinline__ float move_max(float tm, float scale, float& m, f32x16_t (&o)[2]) {
-#ifdef RPO_ATTN_LAZY
-  if (!__any((tm - m) * (scale * LOG2E) > ATTN_TAU)) return 1.0f;      // wave-uniform; (tm - m) = +inf on the first tile
-#endif
   const float mn = fmaxf(m, tm);                            // finite from the first tile on (N >= 1)
   const float alpha = exp_scalar<T>(m - mn, scale);         // first tile: exp(-inf) = 0
 #pragma unroll
@@ -349,10 +330,10 @@ __device__ __forceinline__ float move_max(float tm, float scale, float& m, f32x1
 
 // the PARTIAL key tile: rem = N - 32 t valid keys, G = ceil(rem / 8) live register groups of four (wave-uniform branches:
 // one code path for every G -- four template instances of it spilled 35 registers around a switch)
-template <typename T, int NT, bool SW = false>
+template <typename T, int NT>
 __device__ __forceinline__ void fwd_tile_tail(const char* ks, const char* vs, int t, int rem, const RowFrag<T>& qf,
                                               float scale, float& m, float& l, f32x16_t (&o)[2], int l31, int half) {
-  f32x16_t sc = tile_times_frag<T, SW>(ks, t, qf, l31, half);  // (K rows >= N hold zeros / a copy of row N-1: finite scores)
+  f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31, half);      // (K rows >= N hold zeros: finite scores)
   const int G = (rem + 7) >> 3;
   float tm = -INFINITY;
 #pragma unroll
@@ -397,43 +378,148 @@ __device__ __forceinline__ void fwd_tile_tail(const char* ks, const char* vs, in
   }
 }
 
+// ---- forward: the pieces every forward kernel is made of ---------------------------------------------------------------
+// Online softmax of one query tile over the staged key tiles [ta, tb): running maximum m, running sum l, output tile o
+// rescaled when m grows -- only one score tile is live, so the kernels fit 128 VGPRs and TWO workgroups share a CU.
+// m, l and o carry over from call to call (the two-phase kernel's phases, the long kernel's chunks).
+//   16-bit: full tiles (no key to mask), then, if rem > 0, the partial tile tb with its rem keys (fwd_tile_tail);
+//   f32   : every tile masked against N (rem unused).
+// l31 must be an opaque copy made inside the caller's query-tile loop: K / V in LDS do not depend on the query tile, and
+// without the copy the compiler hoists all of their ds_reads out of that loop and spills them to scratch.
+template <typename T, int NT>
+__device__ __forceinline__ void fwd_walk_keys(const char* ks, const char* vs, int ta, int tb, int rem, int N,
+                                              const RowFrag<T>& qf, float scale, float& m, float& l, f32x16_t (&o)[2],
+                                              int l31, int half) {
+  if constexpr (sizeof(T) == 2) {
+#pragma unroll 1
+    for (int t = ta; t < tb; ++t) {
+      f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31, half);
+      float tm = sc[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
+      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+      const float alpha = move_max<T>(tm, scale, m, o);
+      l = l * alpha + exp_tile<T>(sc, m, scale);
+      contract_keys<T, NT>(vs, t, sc, o, l31, half);
+    }
+    if (rem > 0) fwd_tile_tail<T, NT>(ks, vs, tb, rem, qf, scale, m, l, o, l31, half);
+  } else {
+#pragma unroll 1
+    for (int t = ta; t < tb; ++t) {
+      // (issuing the score tile of key tile t+1 before the softmax arithmetic of tile t -- one more live tile, 118 VGPRs --
+      //  measured nothing: loop 9.5 k vs 9.7 k cycles per workgroup, in-step 14.7 vs 13.6 us, step 3.008 vs 3.009 ms)
+      f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31, half);
+      const float mn = fmaxf(m, mask_and_max(sc, t, N, half));     // finite from the first tile that holds a key on
+      const float alpha = exp_scalar<T>(m - mn, scale);           // first tile: exp(-inf) = 0
+      l = l * alpha + exp_tile<T>(sc, mn, scale);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+      contract_keys<T, NT>(vs, t, sc, o, l31, half);
+      m = mn;
+    }
+  }
+}
+__device__ __forceinline__ void fwd_reset(float& m, float& l, f32x16_t (&o)[2]) {
+  m = -INFINITY; l = 0.f;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+}
+
+// row <- mul * tile: lane (l31, half) holds elements 32 dt + 8 g + 4 half + {0..3} of its query's row
+template <typename T>
+__device__ __forceinline__ void store_tile(T* orow, const f32x16_t (&o)[2], float mul, int half) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * mul, o[dt][4 * g + 1] * mul, o[dt][4 * g + 2] * mul,
+                    o[dt][4 * g + 3] * mul);
+}
+// the end of a query tile: the row sum over both lane halves, out row = o / l if this lane's query is wanted
+template <typename T>
+__device__ __forceinline__ void fwd_store_tile(T* orow, const f32x16_t (&o)[2], float l, bool wanted, int half) {
+  l += __shfl_xor(l, 32, 64);
+  const float inv = 1.0f / l;
+  if (wanted) store_tile<T>(orow, o, inv, half);
+}
+
+// V^T fragments of key tile t from its 32 rows (vrows: row l31's four 16-B pieces of this lane's half): transposed on the
+// matrix core and parked fragment-major, [NT][2 dt][2 g2][64 lanes][16 B], where contract_keys / fwd_tile_tail read them
+template <typename T>
+__device__ __forceinline__ void stage_vt(char* vs, int t, const bf16x8_t (&vrows)[4], const bf16x8_t& i0,
+                                         const bf16x8_t& i1, int lane) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    bf16x8_t fr[2];
+    transpose_tile<T>(vrows, dt, i0, i1, fr);
+#pragma unroll
+    for (int g2 = 0; g2 < 2; ++g2)
+      *reinterpret_cast<bf16x8_t*>(vs + (((t * 2 + dt) * 2 + g2) * 64 + lane) * 16) = fr[g2];
+  }
+}
+// The V rows of the key tiles wave w transposes (w, w + 8), with ordinary loads: load() only issues them -- the caller puts
+// its other requests behind them -- and park() stages their V^T fragments.  Rows at or past N are zeros.
+template <typename T, int NT> struct VtRows {
+  static constexpr int NVT = (NT + 7) / 8;
+  bf16x8_t rows[NVT][4];
+  __device__ __forceinline__ void load(const T* vb, int64_t ld, int N, int wave, int l31, int half) {
+#pragma unroll
+    for (int ti = 0; ti < NVT; ++ti) {
+      const int key = 32 * (wave + 8 * ti) + l31;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        uint4 z = make_uint4(0, 0, 0, 0);
+        if ((NT % 8 == 0 || wave + 8 * ti < NT) && key < N)
+          z = *reinterpret_cast<const uint4*>(vb + (int64_t)key * ld + kk * 16 + half * 8);
+        rows[ti][kk] = __builtin_bit_cast(bf16x8_t, z);
+      }
+    }
+  }
+  __device__ __forceinline__ void park(char* vs, int wave, int lane, int l31, int half) const {
+    const bf16x8_t i0 = ident_frag<T>(0, l31, half), i1 = ident_frag<T>(1, l31, half);
+#pragma unroll
+    for (int ti = 0; ti < NVT; ++ti) {
+      const int t = wave + 8 * ti;
+      if (NT % 8 == 0 || t < NT) stage_vt<T>(vs, t, rows[ti], i0, i1, lane);
+    }
+  }
+};
+
+// Workgroup i of n -> its (image, head) unit.  Block i runs on XCD i % 8: every XCD takes a contiguous run of (image, head)
+// pairs, i.e. whole images -- the images whose rows the out-proj / c_fc / c_proj kernels around this one handle on the same
+// XCD (row units).
+__device__ __forceinline__ int xcd_unit(int i, int n) {
+  const int qd = n >> 3, rm = n & 7, xcd = i & 7;
+  return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (i >> 3);
+}
+// query s (clamped to the last one, S - 1 = N + Kp - 1) of image b in the engine's row layout: B N frozen rows | B Kp prompt rows
+__device__ __forceinline__ int64_t frozen_prompt_row(int s, int b, int B, int N, int Kp, int S) {
+  const int sc = min(s, S - 1);
+  return sc < N ? (int64_t)b * N + sc : (int64_t)B * N + (int64_t)b * Kp + (sc - N);
+}
+// query vq (clamped to the last one, Q - 1 = sets Kp - 1) of image b in the set-major prompt rows: row (s B + b) Kp + j
+__device__ __forceinline__ int64_t set_major_row(int vq_, int b, int B, int Kp, int Q) {
+  const int vq = min(vq_, Q - 1);
+  const int s = vq / Kp, j = vq - s * Kp;
+  return ((int64_t)s * B + b) * Kp + j;
+}
+
 // ---- forward ---------------------------------------------------------------------------
-template <typename T, int NT, bool TWO_PASS = false>
+template <typename T, int NT>
 __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                        const T* __restrict__ v, int64_t ld, T* out,
                                                        int64_t ldo, int B, int H, int N, int Kp, float scale,
-                                                       int q_first, int split_from) {
+                                                       int q_first) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using L = AL<T, NT>;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, l31 = lane & 31;
-  // Block bid runs on XCD bid % 8: every XCD takes a contiguous run of (image, head) pairs, i.e. whole images -- the
-  // images whose rows the out-proj / c_fc / c_proj kernels around this one handle on the same XCD (row units).
-  // split_from (round 4): the first `split_from` workgroups take one (image, head) unit each, the rest take HALF the query
-  // tiles of a unit (two workgroups per unit, each staging K / V itself) -- the launcher splits just enough units for
-  // the grid to fill both resident slots of every CU (B = 32: 256 whole + 2 x 128 halves = 512 workgroups), so that no
-  // CU hosts two whole units while another hosts one.
-  int unit, qpart = -1;
-  {
-    const int bid = blockIdx.x;
-#ifdef RPO_ATTN_PLAIN_ORDER
-    unit = bid;
-#else
-    auto remap = [&](int i, int n) {
-      const int qd = n >> 3, rm = n & 7, xcd = i & 7;
-      return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (i >> 3);
-    };
-    if (bid < split_from) {
-      unit = remap(bid, split_from);
-    } else {
-      const int j = remap(bid - split_from, (int)gridDim.x - split_from);
-      unit = split_from + (j >> 1);
-      qpart = j & 1;
-    }
-#endif
-  }
-  const int wgid = unit;
-  const int b = wgid / H, h = wgid % H;
+  const int unit = xcd_unit(blockIdx.x, gridDim.x);
+  const int b = unit / H, h = unit % H;
   const T* kb = k + (int64_t)b * N * ld + h * 64;
   const T* vb = v + (int64_t)b * N * ld + h * 64;
   char* ks = smem;
@@ -442,49 +528,18 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const T* __restrict__ 
   RPO_STAMP(0);
   // every HBM round trip of the prologue is issued up front: this wave's first query fragment, its V rows
   // (bf16: the key tile it transposes), then the K staging loads
-  auto qrow = [&](int qt) -> int64_t {
-    const int sc = min(qt * 32 + l31, S - 1);
-    return sc < N ? (int64_t)b * N + sc : (int64_t)B * N + (int64_t)b * Kp + (sc - N);
-  };
+  auto qrow = [&](int qt) { return frozen_prompt_row(qt * 32 + l31, b, B, N, Kp, S); };
   RowFrag<T> qf;
   // q_first > 0: only queries q_first .. S-1 of every image are wanted (last block: the prompt rows); whole
   // 32-query tiles are skipped, the leading queries of the first computed tile are computed but not stored
-  int qt0 = q_first >> 5, qt_end = (S + 31) >> 5;
-  if (qpart >= 0) {                                // this workgroup's half of the query tiles
-    const int mid = qt0 + ((qt_end - qt0 + 1) >> 1);
-    if (qpart == 0) qt_end = mid; else qt0 = mid;
-  }
+  const int qt0 = q_first >> 5, qt_end = (S + 31) >> 5;
   if constexpr (sizeof(T) == 2) qf.load(q + qrow(qt0 + wave) * ld + h * 64, half);   // (f32: 32 live VGPRs too many)
   if constexpr (sizeof(T) == 2) {
-    bf16x8_t vrows[(NT + 7) / 8][4];
-#pragma unroll
-    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
-      const int key = 32 * (wave + 8 * ti) + l31;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        uint4 z = make_uint4(0, 0, 0, 0);
-        if (wave + 8 * ti < NT && key < N) z = *reinterpret_cast<const uint4*>(vb + (int64_t)key * ld + kk * 16 + half * 8);
-        vrows[ti][kk] = __builtin_bit_cast(bf16x8_t, z);
-      }
-    }
+    VtRows<T, NT> vt;
+    vt.load(vb, ld, N, wave, l31, half);
     stage_rows_bf16<NT, 512>(ks, reinterpret_cast<const bf16_t*>(kb), ld, N, tid);
     RPO_STAMP(1);
-    // V^T fragments: wave w transposes key tiles w, w+8 on the matrix core
-    const bf16x8_t i0 = ident_frag<T>(0, l31, half), i1 = ident_frag<T>(1, l31, half);
-#pragma unroll
-    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
-      const int t = wave + 8 * ti;
-      if (t < NT) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          bf16x8_t fr[2];
-          transpose_tile<T>(vrows[ti], dt, i0, i1, fr);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2)
-            *reinterpret_cast<bf16x8_t*>(vs + (((t * 2 + dt) * 2 + g2) * 64 + lane) * 16) = fr[g2];
-        }
-      }
-    }
+    vt.park(vs, wave, lane, l31, half);
   } else {
     stage_rows_f32<NT, 512>(reinterpret_cast<float*>(ks), kb, ld, N, tid);
     stage_rows_f32<NT, 512>(reinterpret_cast<float*>(vs), vb, ld, N, tid);
@@ -492,118 +547,19 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const T* __restrict__ 
   RPO_STAMP(2);
   __syncthreads();
   RPO_STAMP(3);
+  // 16-bit: the full key tiles, the partial one peeled, key tiles past N skipped (see fwd_tile_tail); f32: all NT tiles, masked
+  const int nfull = sizeof(T) == 2 ? min(N >> 5, NT) : NT, rem = nfull < NT ? N - 32 * nfull : 0;
   for (int qt = qt0 + wave; qt < qt_end; qt += 8) {
-    // K/V fragments in LDS do not depend on the query tile; without this opaque copy the
-    // compiler hoists all of their ds_reads out of the loop and spills them to scratch
-    int l31v = l31;
+    int l31v = l31;                                      // (opaque copy: see fwd_walk_keys)
     asm volatile("" : "+v"(l31v));
     const int s = qt * 32 + l31;
     const int64_t grow = qrow(qt);
     if (sizeof(T) != 2 || qt != qt0 + wave) qf.load(q + grow * ld + h * 64, half);
-    // online softmax over the key tiles (running max m, running sum l, output rescaled when m grows): only one
-    // score tile is live, so the kernel fits 128 VGPRs and TWO workgroups share a CU -- the 384 (image, head)
-    // workgroups of a B=32 launch are then all resident at once instead of running in two rounds.
-    float m = -INFINITY, l = 0.f;
+    float m, l;
     f32x16_t o[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    if constexpr (TWO_PASS) {
-      // EXPERIMENT (round 4): exact two-pass softmax at the SAME register budget (two workgroups per CU): pass 1
-      // recomputes nothing but the row maximum (4 MFMAs + 10 VALU per key tile, one cross-half exchange per QUERY tile),
-      // pass 2 recomputes the scores and has no running maximum, no rescale of the output tile.  VALU per key tile
-      // 115 -> ~75, MFMAs 8 -> 12.
-#pragma unroll 1
-      for (int t = 0; t < NT; ++t) {
-        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-        if (32 * t + 32 > N) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half;
-            sc[r] = key < N ? sc[r] : -INFINITY;
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) m = fmaxf(m, sc[r]);
-      }
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
-#pragma unroll 1
-      for (int t = 0; t < NT; ++t) {
-        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-        if (32 * t + 32 > N) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half;
-            sc[r] = key < N ? sc[r] : -INFINITY;
-          }
-        }
-        l += exp_tile<T>(sc, m, scale);
-        contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-      }
-    } else
-#ifndef RPO_ATTN_OLD_LOOP           // (A/B build: the round-2..5 loop below for the 16-bit modes too)
-    if constexpr (sizeof(T) == 2) {
-      // round 6 (see fwd_tile_tail): full key tiles as before, the partial one peeled, key tiles past N skipped
-      const int nfull = min(N >> 5, NT), rem = N - 32 * nfull;
-      int t0 = 0;
-#ifdef RPO_ATTN_TPI2
-      // A/B build: TWO key tiles per trip -- independent score accumulators, one row maximum / exchange / rescale per 64
-      // keys: 4 dependent chains per query tile instead of 7 (not bit-identical: the maximum moves in other steps)
-#pragma unroll 1
-      for (; t0 + 1 < nfull; t0 += 2) {
-        f32x16_t sa = tile_times_frag<T>(ks, t0, qf, l31v, half);
-        f32x16_t sb = tile_times_frag<T>(ks, t0 + 1, qf, l31v, half);
-        float tm = fmaxf(sa[0], sb[0]);
-#pragma unroll
-        for (int r = 1; r < 16; ++r) tm = fmaxf(tm, fmaxf(sa[r], sb[r]));
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-        const float alpha = move_max<T>(tm, scale, m, o);
-        l = l * alpha + (exp_tile<T>(sa, m, scale) + exp_tile<T>(sb, m, scale));
-        contract_keys<T, NT>(vs, t0, sa, o, l31v, half);
-        contract_keys<T, NT>(vs, t0 + 1, sb, o, l31v, half);
-      }
-#endif
-#pragma unroll 1
-      for (int t = t0; t < nfull; ++t) {
-        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-        float tm = sc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-        const float alpha = move_max<T>(tm, scale, m, o);
-        l = l * alpha + exp_tile<T>(sc, m, scale);
-        contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-      }
-      if (rem > 0 && nfull < NT) fwd_tile_tail<T, NT>(ks, vs, nfull, rem, qf, scale, m, l, o, l31v, half);
-    } else
-#endif
-#pragma unroll 1
-    for (int t = 0; t < NT; ++t) {
-      // (issuing the score tile of key tile t+1 before the softmax arithmetic of tile t -- one more live tile, 118 VGPRs --
-      //  measured nothing: loop 9.5 k vs 9.7 k cycles per workgroup, in-step 14.7 vs 13.6 us, step 3.008 vs 3.009 ms)
-      f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-      const float mn = fmaxf(m, mask_and_max(sc, t, N, half));     // finite from tile 0 on (N >= 1)
-      const float alpha = exp_scalar<T>(m - mn, scale);           // first tile: exp(-inf) = 0
-      l = l * alpha + exp_tile<T>(sc, mn, scale);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-      contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-      m = mn;
-    }
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-    if (s < S && s >= q_first) {
-      T* orow = out + grow * ldo + h * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
-                        o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-    }
+    fwd_reset(m, l, o);
+    fwd_walk_keys<T, NT>(ks, vs, 0, nfull, rem, N, qf, scale, m, l, o, l31v, half);
+    fwd_store_tile<T>(out + grow * ldo + h * 64, o, l, s < S && s >= q_first, half);
     RPO_STAMP(6);
   }
 #ifdef RPO_TIMELINE
@@ -616,45 +572,38 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const T* __restrict__ 
 // profiles/r06_attn_timeline.txt: of a workgroup's 16.6 k (one per CU) .. 25 k (two per CU) cycles, 4.3 .. 8.9 k pass before
 // the staging barrier -- all 384 workgroups of a launch pull their 57 KB of K / V at once, ~41 MB at the rate the fabric
 // delivers -- and the key loop (7 dependent chains of ~1.4 k cycles) cannot start before the LAST byte has landed.  Here:
-//  * K goes HBM -> LDS by DMA (global_load_lds_dwordx4: no staging registers; rows of 128 B, XOR-swizzled chunks as in
-//    gemm.hip instead of 144-B padded rows), every request of the prologue issued up front in the order q fragment, V rows,
-//    K rows [0, 128) (phase A), the rest of K (phase B);
+//  * every request of the prologue is issued up front in the order q fragment, V rows, K rows [0, 128) (phase A), the rest
+//    of K (phase B) -- K as 16-B register loads into the 144-B padded rows of attn_fwd_kernel;
 //  * the waves retire them with COUNTED waits: q + V -> V^T fragments on the matrix core; phase A -> barrier A -> the key
 //    loop over key tiles 0 .. 3; phase B -> barrier B -> the remaining tiles.  Left to hipcc the V loads sink into the
 //    `tile < NT` branch that uses them and every wait merges to vmcnt(0) (ISA of the first version) -- hence inline asm
 //    for the issue and the waits; the compiler issues no vector-memory instruction of its own before barrier B.
-//  * 104 VGPRs as in round 5 (a register-staged phase B: 114): two workgroups per CU AND room for the side queue's waves
+//  * its VGPR budget (110 at NT = 7) decides whether the side queue's waves fit beside two workgroups per CU
 //    (same-box step time by VGPR budget of this kernel: profiles/r06_attn_variants.txt).
 // Arithmetic per query row is that of attn_fwd_kernel: bit-identical results.
-template <typename T, int NT, bool DMA> struct AL16 {
+template <typename T, int NT> struct AL16 {
   static constexpr int NPAD = NT * 32;
-  static constexpr int K_BYTES = NPAD * (DMA ? 128 : 144);       // DMA: swizzled, unpadded rows; else rows padded to 144 B
+  static constexpr int K_BYTES = NPAD * 144;                     // rows padded to 144 B
   static constexpr int F_BYTES = NT * 4 * 1024;                  // V^T fragments
   static constexpr int BYTES = K_BYTES + F_BYTES;
-  static constexpr int NDMA = (NPAD / 8 + 7) / 8;                // K requests per wave / thread (= ceil(NPAD * 8 / 512))
+  static constexpr int NKR = (NPAD / 8 + 7) / 8;                 // K requests per thread (= ceil(NPAD * 8 / 512))
 };
 
-template <typename T, int NT, bool DMA>
+template <typename T, int NT>
 __global__ __launch_bounds__(512, 4) void attn_fwd16_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                          const T* __restrict__ v, int64_t ld, T* out,
                                                          int64_t ldo, int B, int H, int N, int Kp, float scale,
                                                          int q_first) {
   static_assert(sizeof(T) == 2, "16-bit storage only");
   extern __shared__ __attribute__((aligned(128))) char smem[];
-  using L = AL16<T, NT, DMA>;
-  // K requests per thread / wave: DMA instructions of 8 rows (wave w: rows 8 (w + 8 i) ..), or 16-B register loads
-  // (thread t: chunk t + 512 i); phase A = the first PH of them = K rows [0, 128) either way
-  constexpr int NDMA = L::NDMA, PH = 2;
-  static_assert(NDMA > PH && NDMA <= 5, "the counted waits below are written out for 3 .. 5 requests");
+  using L = AL16<T, NT>;
+  // K requests per thread: 16-B register loads (thread t: chunk t + 512 i); phase A = the first PH of them = K rows [0, 128)
+  constexpr int NKR = L::NKR, PH = 2;
+  static_assert(NKR > PH && NKR <= 5, "the counted waits below are written out for 3 .. 5 requests");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
-  int unit;
-  {   // block bid runs on XCD bid % 8: every XCD takes a contiguous run of (image, head) pairs, i.e. whole images
-    const int i = blockIdx.x, n = gridDim.x;
-    const int qd = n >> 3, rm = n & 7, xcd = i & 7;
-    unit = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (i >> 3);
-  }
+  const int unit = xcd_unit(blockIdx.x, gridDim.x);
   const int b = unit / H, h = unit % H;
   const T* kb = k + (int64_t)b * N * ld + h * 64;
   const T* vb = v + (int64_t)b * N * ld + h * 64;
@@ -662,16 +611,13 @@ __global__ __launch_bounds__(512, 4) void attn_fwd16_kernel(const T* __restrict_
   char* vs = smem + L::K_BYTES;
   const int S = N + Kp;
   RPO_STAMP(0);
-  auto qrow = [&](int qt) -> int64_t {
-    const int sc = min(qt * 32 + l31, S - 1);
-    return sc < N ? (int64_t)b * N + sc : (int64_t)B * N + (int64_t)b * Kp + (sc - N);
-  };
+  auto qrow = [&](int qt) { return frozen_prompt_row(qt * 32 + l31, b, B, N, Kp, S); };
   const int qt0 = q_first >> 5, qt_end = (S + 31) >> 5;
   const int qt_mine = qt0 + wave;
   typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
   constexpr int NVT = (NT + 7) / 8;
   RowFrag<T> qf;
-  u32x4 qreg[4], vreg[NVT][4], kreg[DMA ? 1 : NDMA];
+  u32x4 qreg[4], vreg[NVT][4], kreg[NKR];
   {
     const T* qp = q + qrow(qt_mine) * ld + h * 64 + half * 8;      // (rows are clamped: waves without a tile load a valid row)
 #pragma unroll
@@ -684,45 +630,29 @@ __global__ __launch_bounds__(512, 4) void attn_fwd16_kernel(const T* __restrict_
       for (int kk = 0; kk < 4; ++kk)
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vreg[ti][kk]) : "v"(vp + kk * 16) : "memory");
     }
-    // K: DMA instruction j of the workgroup = rows [8 j, 8 j + 8); wave w issues j = w, w + 8, ...; lane l -> row 8 j + (l >> 3),
-    // physical 16-B slot l & 7, which must receive logical chunk (l & 7) ^ ((row >> 1) & 7).  Rows >= N re-read row N - 1
-    // (their scores are masked or never formed); an instruction past the last one repeats the last one (same bytes).
-    if constexpr (DMA) {
-      const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ks;
+    // K: rows >= N re-read row N - 1 (commit_k zeroes them); a chunk past the panel is loaded and not written
 #pragma unroll
-      for (int i = 0; i < NDMA; ++i) {
-        const int j = min(wave + 8 * i, L::NPAD / 8 - 1);
-        const int row = 8 * j + (lane >> 3);
-        const T* kp = kb + (int64_t)min(row, N - 1) * ld + (((lane & 7) ^ ((row >> 1) & 7)) << 3);
-        const uint32_t dst = lds0 + (uint32_t)j * 1024u;           // (uniform)
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(kp), "s"(dst) : "memory", "m0");
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NDMA; ++i) {
-        const int id = tid + i * 512;
-        const T* kp = kb + (int64_t)min(id >> 3, N - 1) * ld + (id & 7) * 8;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kreg[i]) : "v"(kp) : "memory");
-      }
+    for (int i = 0; i < NKR; ++i) {
+      const int id = tid + i * 512;
+      const T* kp = kb + (int64_t)min(id >> 3, N - 1) * ld + (id & 7) * 8;
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kreg[i]) : "v"(kp) : "memory");
     }
   }
-  // (register path) chunk id = tid + 512 i of the [NPAD][8]-chunk K panel -> its padded LDS row; rows >= N are zeroed
+  // chunk id = tid + 512 i of the [NPAD][8]-chunk K panel -> its padded LDS row; rows >= N are zeroed
   auto commit_k = [&](int i) {
-    if constexpr (!DMA) {
-      const int id = tid + i * 512;
-      const int key = id >> 3, c = id & 7;
-      const u32x4 z = {0u, 0u, 0u, 0u};
-      if (id < L::NPAD * 8) *reinterpret_cast<u32x4*>(ks + key * 144 + c * 16) = key < N ? kreg[i] : z;
-    }
+    const int id = tid + i * 512;
+    const int key = id >> 3, c = id & 7;
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    if (id < L::NPAD * 8) *reinterpret_cast<u32x4*>(ks + key * 144 + c * 16) = key < N ? kreg[i] : z;
   };
-  // q and V have landed once at most the NDMA K requests are outstanding (returns are in order)
+  // q and V have landed once at most the NKR K requests are outstanding (returns are in order)
   if constexpr (NVT == 1)
     asm volatile("s_waitcnt vmcnt(%8)" : "+v"(qreg[0]), "+v"(qreg[1]), "+v"(qreg[2]), "+v"(qreg[3]), "+v"(vreg[0][0]),
-                 "+v"(vreg[0][1]), "+v"(vreg[0][2]), "+v"(vreg[0][3]) : "n"(NDMA) : "memory");
+                 "+v"(vreg[0][1]), "+v"(vreg[0][2]), "+v"(vreg[0][3]) : "n"(NKR) : "memory");
   else
     asm volatile("s_waitcnt vmcnt(%12)" : "+v"(qreg[0]), "+v"(qreg[1]), "+v"(qreg[2]), "+v"(qreg[3]), "+v"(vreg[0][0]),
                  "+v"(vreg[0][1]), "+v"(vreg[0][2]), "+v"(vreg[0][3]), "+v"(vreg[NVT - 1][0]), "+v"(vreg[NVT - 1][1]),
-                 "+v"(vreg[NVT - 1][2]), "+v"(vreg[NVT - 1][3]) : "n"(NDMA) : "memory");
+                 "+v"(vreg[NVT - 1][2]), "+v"(vreg[NVT - 1][3]) : "n"(NKR) : "memory");
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) qf.f[kk] = __builtin_bit_cast(bf16x8_t, qreg[kk]);
   // V^T fragments: wave w transposes key tiles w, w + 8 on the matrix core (rows >= N contribute zeros)
@@ -736,232 +666,55 @@ __global__ __launch_bounds__(512, 4) void attn_fwd16_kernel(const T* __restrict_
         bf16x8_t vrows[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) vrows[kk] = __builtin_bit_cast(bf16x8_t, 32 * t + l31 < N ? vreg[ti][kk] : z);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          bf16x8_t fr[2];
-          transpose_tile<T>(vrows, dt, i0, i1, fr);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2)
-            *reinterpret_cast<bf16x8_t*>(vs + (((t * 2 + dt) * 2 + g2) * 64 + lane) * 16) = fr[g2];
-        }
+        stage_vt<T>(vs, t, vrows, i0, i1, lane);
       }
     }
   }
   RPO_STAMP(1);
-  if constexpr (DMA) {
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA - PH) : "memory");   // this wave's phase-A rows are in LDS
-  } else {
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[0]) : "n"(NDMA - 1) : "memory");
-    commit_k(0);
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[DMA ? 0 : 1]) : "n"(NDMA - 2) : "memory");
-    commit_k(1);
-  }
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[0]) : "n"(NKR - 1) : "memory");
+  commit_k(0);
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[1]) : "n"(NKR - 2) : "memory");
+  commit_k(1);
   RPO_STAMP(2);
   __syncthreads();                                               // barrier A: V^T of every tile, K rows [0, 128)
   RPO_STAMP(3);
-  const int nfull = min(N >> 5, NT), rem = N - 32 * nfull;
+  const int nfull = min(N >> 5, NT), rem = nfull < NT ? N - 32 * nfull : 0;   // full key tiles; keys of the partial one
   const int nA = min(nfull, 2 * PH);                             // full key tiles inside phase A's rows
-  float m = -INFINITY, l = 0.f;
+  float m, l;
   f32x16_t o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-  auto tiles = [&](int ta, int tb, int l31v) {
-#pragma unroll 1
-    for (int t = ta; t < tb; ++t) {
-      f32x16_t sc = tile_times_frag<T, DMA>(ks, t, qf, l31v, half);
-      float tm = sc[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
-      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-      const float alpha = move_max<T>(tm, scale, m, o);
-      l = l * alpha + exp_tile<T>(sc, m, scale);
-      contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-    }
-  };
-  auto finish = [&](int qt, int l31v) {
-    if (rem > 0 && nfull < NT) fwd_tile_tail<T, NT, DMA>(ks, vs, nfull, rem, qf, scale, m, l, o, l31v, half);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
+  fwd_reset(m, l, o);
+  auto store = [&](int qt) {
     const int s = qt * 32 + l31;
-    if (s < S && s >= q_first) {
-      T* orow = out + qrow(qt) * ldo + h * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
-                        o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-    }
+    fwd_store_tile<T>(out + qrow(qt) * ldo + h * 64, o, l, s < S && s >= q_first, half);
   };
-  // K / V fragments in LDS do not depend on the query tile; without this opaque copy the compiler hoists their
-  // ds_reads out of the loops and spills them
-  int l31v = l31;
+  int l31v = l31;                                                // (opaque copy: see fwd_walk_keys)
   asm volatile("" : "+v"(l31v));
   const bool have = qt_mine < qt_end;                            // (wave-uniform)
-  if (have) tiles(0, nA, l31v);
+  if (have) fwd_walk_keys<T, NT>(ks, vs, 0, nA, 0, N, qf, scale, m, l, o, l31v, half);
   RPO_STAMP(4);
-  if constexpr (DMA) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's phase-B rows are in LDS
-  } else {
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[DMA ? 0 : 2]) : "n"(NDMA - 3) : "memory");
-    commit_k(2);
-    if constexpr (NDMA > 3) {
-      asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[DMA ? 0 : (NDMA > 3 ? 3 : 0)]) : "n"(NDMA > 3 ? NDMA - 4 : 0) : "memory");
-      commit_k(3);
-    }
-    if constexpr (NDMA > 4) {
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(kreg[DMA ? 0 : NDMA - 1]) : : "memory");
-      commit_k(NDMA - 1);
-    }
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[2]) : "n"(NKR - 3) : "memory");
+  commit_k(2);
+  if constexpr (NKR > 3) {
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kreg[NKR > 3 ? 3 : 0]) : "n"(NKR > 3 ? NKR - 4 : 0) : "memory");
+    commit_k(3);
+  }
+  if constexpr (NKR > 4) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(kreg[NKR - 1]) : : "memory");
+    commit_k(NKR - 1);
   }
   __syncthreads();                                               // barrier B: the rest of K
   RPO_STAMP(5);
   if (have) {
-    tiles(nA, nfull, l31v);
-    finish(qt_mine, l31v);
+    fwd_walk_keys<T, NT>(ks, vs, nA, nfull, rem, N, qf, scale, m, l, o, l31v, half);
+    store(qt_mine);
   }
   RPO_STAMP(6);
   for (int qt = qt_mine + 8; qt < qt_end; qt += 8) {             // (S > 256: ViT-L/14's ninth query tile)
     asm volatile("" : "+v"(l31v));
     qf.load(q + qrow(qt) * ld + h * 64, half);
-    m = -INFINITY; l = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    tiles(0, nfull, l31v);
-    finish(qt, l31v);
-  }
-#ifdef RPO_TIMELINE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  RPO_STAMP(7);
-}
-
-// ---- forward, 16-bit storage, round 4: every score tile of a query tile in registers, exact two-pass softmax ----------
-// The online-softmax loop above is one dependent chain per key tile (4 score MFMAs on one accumulator -> max -> cross-half
-// exchange -> exp -> rescale of the output tile -> 4 P.V MFMAs): ~1.4 k cycles per key tile for a wave, 9.7 k per
-// workgroup (profiles/r03_attn_timeline.txt), whatever else the CU does.  With N <= 288 keys a lane's whole score row is
-// only NT x 16 registers, so here a wave first issues ALL NT score tiles (independent accumulators: the MFMAs pipeline),
-// takes the row maximum ONCE (one cross-half exchange per query tile instead of one per key tile), then exponentiates
-// and contracts tile by tile with nothing to rescale.  ~200 VGPRs: one 8-wave workgroup per CU instead of two.
-template <typename T, int NT>
-__global__ __launch_bounds__(512, 2) void attn_fwd2_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                        const T* __restrict__ v, int64_t ld, T* out,
-                                                        int64_t ldo, int B, int H, int N, int Kp, float scale,
-                                                        int q_first) {
-  static_assert(sizeof(T) == 2, "16-bit storage only");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using L = AL<T, NT>;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int wgid = [&] {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-    return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-  }();
-  const int b = wgid / H, h = wgid % H;
-  const T* kb = k + (int64_t)b * N * ld + h * 64;
-  const T* vb = v + (int64_t)b * N * ld + h * 64;
-  char* ks = smem;
-  char* vs = smem + L::K_BYTES;
-  const int S = N + Kp;
-  RPO_STAMP(0);
-  auto qrow = [&](int qt) -> int64_t {
-    const int sc = min(qt * 32 + l31, S - 1);
-    return sc < N ? (int64_t)b * N + sc : (int64_t)B * N + (int64_t)b * Kp + (sc - N);
-  };
-  RowFrag<T> qf;
-  const int qt0 = q_first >> 5;
-  qf.load(q + qrow(qt0 + wave) * ld + h * 64, half);
-  {
-    bf16x8_t vrows[(NT + 7) / 8][4];
-#pragma unroll
-    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
-      const int key = 32 * (wave + 8 * ti) + l31;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        uint4 z = make_uint4(0, 0, 0, 0);
-        if (wave + 8 * ti < NT && key < N) z = *reinterpret_cast<const uint4*>(vb + (int64_t)key * ld + kk * 16 + half * 8);
-        vrows[ti][kk] = __builtin_bit_cast(bf16x8_t, z);
-      }
-    }
-    stage_rows_bf16<NT, 512>(ks, reinterpret_cast<const bf16_t*>(kb), ld, N, tid);
-    RPO_STAMP(1);
-    const bf16x8_t i0 = ident_frag<T>(0, l31, half), i1 = ident_frag<T>(1, l31, half);
-#pragma unroll
-    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
-      const int t = wave + 8 * ti;
-      if (t < NT) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          bf16x8_t fr[2];
-          transpose_tile<T>(vrows[ti], dt, i0, i1, fr);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2)
-            *reinterpret_cast<bf16x8_t*>(vs + (((t * 2 + dt) * 2 + g2) * 64 + lane) * 16) = fr[g2];
-        }
-      }
-    }
-  }
-  RPO_STAMP(2);
-  __syncthreads();
-  RPO_STAMP(3);
-  const float c = scale * LOG2E;
-  for (int qt = qt0 + wave; qt * 32 < S; qt += 8) {
-    int l31v = l31;
-    asm volatile("" : "+v"(l31v));
-    const int s = qt * 32 + l31;
-    const int64_t grow = qrow(qt);
-    if (qt != qt0 + wave) qf.load(q + grow * ld + h * 64, half);
-    // pass 1: all score tiles (S^T = K . Q^T: a lane holds 16 of the 32 keys of every tile for ONE query)
-    f32x16_t sc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) sc[t] = tile_times_frag<T>(ks, t, qf, l31v, half);
-    float m = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      if (32 * t + 32 > N) {                       // (uniform) keys >= N of a tile that can hold padding -> -inf
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half;
-          sc[t][r] = key < N ? sc[t][r] : -INFINITY;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) m = fmaxf(m, sc[t][r]);
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));           // finite: tile 0 always holds keys
-    RPO_STAMP(4);
-    // pass 2: p = exp((s - m) * scale), row sum, O += V^T-contraction -- nothing to rescale
-    const float mc = m * c;
-    float l = 0.f;
-    f32x16_t o[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { sc[t][r] = __builtin_amdgcn_exp2f(fmaf(sc[t][r], c, -mc)); l += sc[t][r]; }
-      contract_keys<T, NT>(vs, t, sc[t], o, l31v, half);
-    }
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-    RPO_STAMP(5);
-    if (s < S && s >= q_first) {
-      T* orow = out + grow * ldo + h * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
-                        o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-    }
-    RPO_STAMP(6);
+    fwd_reset(m, l, o);
+    fwd_walk_keys<T, NT>(ks, vs, 0, nfull, rem, N, qf, scale, m, l, o, l31v, half);
+    store(qt);
   }
 #ifdef RPO_TIMELINE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1004,17 +757,8 @@ __device__ __forceinline__ void attn_bwd_body(char* smem, const int bid, const i
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
-  // Block bid runs on XCD bid % 8: every XCD takes a contiguous run of (image, head) pairs, i.e. whole images -- the
-  // images whose rows the out-proj / c_fc / c_proj kernels around this one handle on the same XCD (row units).
-#ifdef RPO_ATTN_PLAIN_ORDER
-  const int wgid = bid;
-#else
   // (plain_order: bid IS the (group, head) index -- the persistent chain kernel, chain.hip, places its items itself)
-  const int wgid = plain_order ? bid : [&] {
-    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
-    return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
-  }();
-#endif
+  const int wgid = plain_order ? bid : xcd_unit(bid, nwg);
   // fused variant with Kp > 32: nqt_wg workgroups per (group, head), one per 32-query tile (adjacent: same XCD)
   const int pair_id = wgid / nqt_wg, qt_wg = wgid - pair_id * nqt_wg;
   const int b = pair_id / H, h = pair_id % H;
@@ -1374,16 +1118,12 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_long_kernel(const T* __restri
   const int qt = (q_first >> 5) + 8 * grp + wave;
   const bool active = qt < ((S + 31) >> 5);        // wave-uniform; an idle wave still stages and meets the barriers
   const int s = qt * 32 + l31;
-  const int sc_ = min(s, S - 1);
-  const int64_t grow = sc_ < N ? (int64_t)b * N + sc_ : (int64_t)B * N + (int64_t)b * Kp + (sc_ - N);
+  const int64_t grow = frozen_prompt_row(s, b, B, N, Kp, S);
   RowFrag<T> qf;
   qf.load(q + grow * ld + h * 64, half);
-  float m = -INFINITY, l = 0.f;
+  float m, l;
   f32x16_t o[2];
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+  fwd_reset(m, l, o);
 #pragma unroll 1
   for (int c0 = 0; c0 < N; c0 += C) {
     const int Nc = min(N - c0, C);                 // keys of this chunk
@@ -1400,73 +1140,23 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_long_kernel(const T* __restri
       // in flight at once do not fit 128 VGPRs
       stage_rows_bf16<NT, 512>(ks, reinterpret_cast<const bf16_t*>(kc), ld, Nc, tidv);
       asm volatile("" ::: "memory");
-      bf16x8_t vrows[4];                           // wave w transposes key tile w of the chunk
-      const int key = 32 * wave + l31s;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        uint4 z = make_uint4(0, 0, 0, 0);
-        if (key < Nc) z = *reinterpret_cast<const uint4*>(vc + (int64_t)key * ld + kk * 16 + halfs * 8);
-        vrows[kk] = __builtin_bit_cast(bf16x8_t, z);
-      }
-      const bf16x8_t i0 = ident_frag<T>(0, l31s, halfs), i1 = ident_frag<T>(1, l31s, halfs);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        bf16x8_t fr[2];
-        transpose_tile<T>(vrows, dt, i0, i1, fr);
-#pragma unroll
-        for (int g2 = 0; g2 < 2; ++g2)
-          *reinterpret_cast<bf16x8_t*>(vs + (((wave * 2 + dt) * 2 + g2) * 64 + lanev) * 16) = fr[g2];
-      }
+      VtRows<T, NT> vt;                            // wave w transposes key tile w of the chunk
+      vt.load(vc, ld, Nc, wave, l31s, halfs);
+      vt.park(vs, wave, lanev, l31s, halfs);
     } else {
       stage_rows_f32<NT, 512>(reinterpret_cast<float*>(ks), kc, ld, Nc, tidv);
       stage_rows_f32<NT, 512>(reinterpret_cast<float*>(vs), vc, ld, Nc, tidv);
     }
     __syncthreads();
     if (active) {
-      int l31v = l31;                              // (keeps the K / V reads of the key loop inside it: see attn_fwd_kernel)
+      int l31v = l31;                              // (opaque copy: see fwd_walk_keys)
       asm volatile("" : "+v"(l31v));
-      if constexpr (sizeof(T) == 2) {
-        const int nfull = Nc >> 5, rem = Nc - 32 * nfull;
-#pragma unroll 1
-        for (int t = 0; t < nfull; ++t) {
-          f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-          float tm = sc[0];
-#pragma unroll
-          for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
-          tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-          const float alpha = move_max<T>(tm, scale, m, o);
-          l = l * alpha + exp_tile<T>(sc, m, scale);
-          contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-        }
-        if (rem > 0) fwd_tile_tail<T, NT>(ks, vs, nfull, rem, qf, scale, m, l, o, l31v, half);   // (rem > 0: nfull < NT)
-      } else {
-#pragma unroll 1
-        for (int t = 0; 32 * t < Nc; ++t) {        // every tile visited holds a key: the maximum is finite
-          f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-          const float mn = fmaxf(m, mask_and_max(sc, t, Nc, half));
-          const float alpha = exp_scalar<T>(m - mn, scale);        // first tile: exp(-inf) = 0
-          l = l * alpha + exp_tile<T>(sc, mn, scale);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-          contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-          m = mn;
-        }
-      }
+      // 16-bit: the chunk's full tiles, then its partial one (rem > 0: nfull < NT); f32: the tiles that hold a key, masked
+      const int nt = sizeof(T) == 2 ? Nc >> 5 : (Nc + 31) >> 5;
+      fwd_walk_keys<T, NT>(ks, vs, 0, nt, Nc & 31, Nc, qf, scale, m, l, o, l31v, half);
     }
   }
-  l += __shfl_xor(l, 32, 64);
-  const float inv = 1.0f / l;
-  if (active && s < S && s >= q_first) {
-    T* orow = out + grow * ldo + h * 64;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
-                      o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-  }
+  fwd_store_tile<T>(out + grow * ldo + h * 64, o, l, active && s < S && s >= q_first, half);
 }
 
 // Backward for the prompt rows (dq; K and V are frozen).  One workgroup per (image, head, 32-query tile), the four waves
@@ -1658,71 +1348,28 @@ int launch_bwd_long(const void* qr, int64_t ldq, const void* k, const void* v, i
 }
 
 template <typename T, int NT>
-int launch_fwd2(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo, int B, int H,
-                int N, int Kp, float scale, int q_first, hipStream_t s) {
-  static rpo_lds_mask_t lds_ok{0};
-  auto kern = attn_fwd2_kernel<T, NT>;
-  constexpr int bytes = AL<T, NT>::FWD_BYTES;
-  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), bytes, s, static_cast<const T*>(q),
-                     static_cast<const T*>(k), static_cast<const T*>(v), ld, static_cast<T*>(out), ldo, B, H,
-                     N, Kp, scale, q_first);
-  return rpo_launch_status();
-}
-
-template <typename T, int NT>
 int launch_fwd(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo, int B, int H,
                int N, int Kp, float scale, int q_first, hipStream_t s) {
-#ifdef RPO_ATTN_FWD_V2            // (A/B build: every score tile in registers, one workgroup per CU -- attn_fwd2_kernel)
-  if constexpr (sizeof(T) == 2) return launch_fwd2<T, NT>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-#endif
-#if !defined(RPO_ATTN_OLD_LOOP) && !defined(RPO_ATTN_ONE_BARRIER) && !defined(RPO_ATTN_SPLIT) && !defined(RPO_ATTN_FWD_2PASS)
   // round 6: two-phase staging where the launch has more (image, head) units than CUs and seven key tiles (ViT-B/16 from
   // batch 22 on) -- there the staging burst is long and the early start pays (batch 64: -0.5 % on the step); with fewer
   // units (or ViT-L/14's nine key tiles, 256 units at batch 16) the second barrier's wave skew costs more than the early start
-  // returns (ViT-L/14 +0.8 %): profiles/r06_ab_attn_configs.txt.  A/B builds: -DRPO_ATTN_ONE_BARRIER never, -DRPO_ATTN_TWO_PHASE always.
-#ifdef RPO_ATTN_TWO_PHASE
-  const bool two_phase = true;
-#else
+  // returns (ViT-L/14 +0.8 %): profiles/r06_ab_attn_configs.txt.
   const bool two_phase = NT == 7 && B * H > rpo_cu_count();
-#endif
   if constexpr (sizeof(T) == 2) if (two_phase) {
     static rpo_lds_mask_t lds16_ok{0};
-#ifdef RPO_ATTN_DMA                 // (A/B build: K by LDS-DMA into swizzled rows; default: 16-B register loads, padded rows)
-    constexpr bool kdma = true;
-#else
-    constexpr bool kdma = false;
-#endif
-    auto k16 = attn_fwd16_kernel<T, NT, kdma>;
-    constexpr int bytes16 = AL16<T, NT, kdma>::BYTES;
+    auto k16 = attn_fwd16_kernel<T, NT>;
+    constexpr int bytes16 = AL16<T, NT>::BYTES;
     if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(k16), bytes16, &lds16_ok)) return rc;
     hipLaunchKernelGGL(k16, dim3(B * H), dim3(512), bytes16, s, static_cast<const T*>(q), static_cast<const T*>(k),
                        static_cast<const T*>(v), ld, static_cast<T*>(out), ldo, B, H, N, Kp, scale, q_first);
     return rpo_launch_status();
   }
-#endif
   static rpo_lds_mask_t lds_ok{0};
-#ifdef RPO_ATTN_FWD_2PASS         // (A/B build: two-pass softmax with recomputed scores, two workgroups per CU)
-  auto kern = attn_fwd_kernel<T, NT, sizeof(T) == 2>;
-#else
   auto kern = attn_fwd_kernel<T, NT>;
-#endif
   constexpr int bytes = AL<T, NT>::FWD_BYTES;
   if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
-  // Two workgroups fit a CU.  EXPERIMENT (round 4, off: -DRPO_ATTN_SPLIT): with more units than CUs but fewer than
-  // slots, split units until the slots are full.  Measured same-box: the kernel's in-stream time drops 14.5 -> 12.5 us
-  // (B = 32: no CU hosts two whole units any more), but the STEP is 0.5 % slower (2.958 vs 2.943 ms, three alternating
-  // pairs) and the forward pair with the text tower beside it unchanged: a grid that fills every resident slot has no
-  // room left for the side queue's workgroups, whose hosts then run a third half-unit (profiles/r04_ab_attn_fwd_variants.txt).
-  const int units = B * H;
-  int nsplit = 0;
-#ifdef RPO_ATTN_SPLIT
-  const int cus = rpo_cu_count();
-  if (sizeof(T) == 2 && q_first == 0 && units > cus && units < 2 * cus) nsplit = 2 * cus - units < units ? 2 * cus - units : units;
-#endif
-  hipLaunchKernelGGL(kern, dim3(units + nsplit), dim3(512), bytes, s, static_cast<const T*>(q),
-                     static_cast<const T*>(k), static_cast<const T*>(v), ld, static_cast<T*>(out), ldo, B, H,
-                     N, Kp, scale, q_first, units - nsplit);
+  hipLaunchKernelGGL(kern, dim3(B * H), dim3(512), bytes, s, static_cast<const T*>(q), static_cast<const T*>(k),
+                     static_cast<const T*>(v), ld, static_cast<T*>(out), ldo, B, H, N, Kp, scale, q_first);   // two workgroups fit a CU
   return rpo_launch_status();
 }
 
@@ -1755,98 +1402,31 @@ __global__ __launch_bounds__(512, 4) void attn_prompt_fwd_kernel(const T* __rest
   char* vs = smem + L::K_BYTES;
   const int Q = sets * Kp;                               // this image's queries, set-major
   const int qt_end = (Q + 31) >> 5;
-  auto qrow = [&](int qt) -> int64_t {                   // (queries past Q: the last one again, computed and not stored)
-    const int vq = min(qt * 32 + l31, Q - 1);
-    const int s = vq / Kp, j = vq - s * Kp;
-    return ((int64_t)s * B + b) * Kp + j;
-  };
+  // (queries past Q: the last one again, computed and not stored)
+  auto qrow = [&](int qt) { return set_major_row(qt * 32 + l31, b, B, Kp, Q); };
   RowFrag<T> qf;
   if constexpr (sizeof(T) == 2) qf.load(q + qrow(wave) * ldq + h * 64, half);
   if constexpr (sizeof(T) == 2) {
-    bf16x8_t vrows[(NT + 7) / 8][4];
-#pragma unroll
-    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
-      const int key = 32 * (wave + 8 * ti) + l31;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        uint4 z = make_uint4(0, 0, 0, 0);
-        if (wave + 8 * ti < NT && key < N) z = *reinterpret_cast<const uint4*>(vb + (int64_t)key * ldkv + kk * 16 + half * 8);
-        vrows[ti][kk] = __builtin_bit_cast(bf16x8_t, z);
-      }
-    }
+    VtRows<T, NT> vt;
+    vt.load(vb, ldkv, N, wave, l31, half);
     stage_rows_bf16<NT, 512>(ks, reinterpret_cast<const bf16_t*>(kb), ldkv, N, tid);
-    const bf16x8_t i0 = ident_frag<T>(0, l31, half), i1 = ident_frag<T>(1, l31, half);
-#pragma unroll
-    for (int ti = 0; ti < (NT + 7) / 8; ++ti) {
-      const int t = wave + 8 * ti;
-      if (t < NT) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          bf16x8_t fr[2];
-          transpose_tile<T>(vrows[ti], dt, i0, i1, fr);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2)
-            *reinterpret_cast<bf16x8_t*>(vs + (((t * 2 + dt) * 2 + g2) * 64 + lane) * 16) = fr[g2];
-        }
-      }
-    }
+    vt.park(vs, wave, lane, l31, half);
   } else {
     stage_rows_f32<NT, 512>(reinterpret_cast<float*>(ks), kb, ldkv, N, tid);
     stage_rows_f32<NT, 512>(reinterpret_cast<float*>(vs), vb, ldkv, N, tid);
   }
   __syncthreads();
+  const int nfull = sizeof(T) == 2 ? min(N >> 5, NT) : NT, rem = nfull < NT ? N - 32 * nfull : 0;   // (as attn_fwd_kernel)
   for (int qt = wave; qt < qt_end; qt += 8) {
-    int l31v = l31;                                      // (keeps the K / V ds_reads inside the loop: attn_fwd_kernel)
+    int l31v = l31;                                      // (opaque copy: see fwd_walk_keys)
     asm volatile("" : "+v"(l31v));
-    const int vq = qt * 32 + l31;
     const int64_t grow = qrow(qt);
     if (sizeof(T) != 2 || qt != wave) qf.load(q + grow * ldq + h * 64, half);
-    float m = -INFINITY, l = 0.f;
+    float m, l;
     f32x16_t o[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    if constexpr (sizeof(T) == 2) {
-      const int nfull = min(N >> 5, NT), rem = N - 32 * nfull;
-#pragma unroll 1
-      for (int t = 0; t < nfull; ++t) {
-        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-        float tm = sc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) tm = fmaxf(tm, sc[r]);
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-        const float alpha = move_max<T>(tm, scale, m, o);
-        l = l * alpha + exp_tile<T>(sc, m, scale);
-        contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-      }
-      if (rem > 0 && nfull < NT) fwd_tile_tail<T, NT>(ks, vs, nfull, rem, qf, scale, m, l, o, l31v, half);
-    } else {
-#pragma unroll 1
-      for (int t = 0; t < NT; ++t) {
-        f32x16_t sc = tile_times_frag<T>(ks, t, qf, l31v, half);
-        const float mn = fmaxf(m, mask_and_max(sc, t, N, half));     // finite from tile 0 on (N >= 1)
-        const float alpha = exp_scalar<T>(m - mn, scale);           // first tile: exp(-inf) = 0
-        l = l * alpha + exp_tile<T>(sc, mn, scale);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-        contract_keys<T, NT>(vs, t, sc, o, l31v, half);
-        m = mn;
-      }
-    }
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-    if (vq < Q) {
-      T* orow = out + grow * ldo + h * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv,
-                        o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
-    }
+    fwd_reset(m, l, o);
+    fwd_walk_keys<T, NT>(ks, vs, 0, nfull, rem, N, qf, scale, m, l, o, l31v, half);
+    fwd_store_tile<T>(out + grow * ldo + h * 64, o, l, qt * 32 + l31 < Q, half);
   }
 }
 
@@ -1900,11 +1480,8 @@ __global__ __launch_bounds__(512) void attn_prompt_bwd_kernel(const T* q, int64_
   char* vs = smem + L::K_BYTES;
   const int Q = sets * Kp;                               // this image's queries, set-major
   const int qt_end = (Q + 31) >> 5;
-  auto qrow = [&](int qt) -> int64_t {                   // (queries past Q: the last one again, computed and not stored)
-    const int vq = min(qt * 32 + l31, Q - 1);
-    const int s = vq / Kp, j = vq - s * Kp;
-    return ((int64_t)s * B + b) * Kp + j;
-  };
+  // (queries past Q: the last one again, computed and not stored)
+  auto qrow = [&](int qt) { return set_major_row(qt * 32 + l31, b, B, Kp, Q); };
   RowFrag<T> qf, df;
   if constexpr (sizeof(T) == 2) {                        // the first tile's operands ride in the staging loads' round trip
     const int64_t r0 = qrow(wave);
@@ -1981,15 +1558,7 @@ __global__ __launch_bounds__(512) void attn_prompt_bwd_kernel(const T* q, int64_
         contract_keys<T, NT>(ks, t, ds, u, l31v, half);
       }
     }
-    if (vq < Q) {
-      T* orow = dq + grow * lddq + h * 64;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          ActIO<T>::st4(orow + 32 * dt + 8 * g + 4 * half, scale * u[dt][4 * g], scale * u[dt][4 * g + 1],
-                        scale * u[dt][4 * g + 2], scale * u[dt][4 * g + 3]);
-    }
+    if (vq < Q) store_tile<T>(dq + grow * lddq + h * 64, u, scale, half);
   }
 }
 
@@ -2264,6 +1833,14 @@ int rpo_text_attn_wave(int bwd, const void* q, int64_t ldq, const void* kc, cons
              : launch_text_wave<f16_t, false>(q, ldq, kc, vc, ldkv, da, ldda, out, ldo, len, n_cls, n_kv, rows, Lmax, H, scale, s);
 }
 
+// LAUNCH<T, NT>(...) by storage type (`dtype`: checked by the caller) and key tiles (`N` <= 224: seven, else nine)
+#define RPO_BY_TYPE_NT(LAUNCH, ...)                                                                            \
+  do {                                                                                                         \
+    if (dtype == RPO_BF16) return N <= 224 ? LAUNCH<bf16_t, 7>(__VA_ARGS__) : LAUNCH<bf16_t, 9>(__VA_ARGS__);  \
+    if (dtype == RPO_F16) return N <= 224 ? LAUNCH<f16_t, 7>(__VA_ARGS__) : LAUNCH<f16_t, 9>(__VA_ARGS__);     \
+    return N <= 224 ? LAUNCH<float, 7>(__VA_ARGS__) : LAUNCH<float, 9>(__VA_ARGS__);                           \
+  } while (0)
+
 extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const void* v, int64_t ld, void* out,
                                           int64_t ldo, int dtype, int B, int H, int N, int Kp, float scale,
                                           int q_first, void* stream);
@@ -2290,16 +1867,7 @@ extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const vo
     if (dtype == RPO_F16) return launch_fwd_long<f16_t>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
     return launch_fwd_long<float>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
   }
-  if (dtype == RPO_BF16) {
-    if (N <= 224) return launch_fwd<bf16_t, 7>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-    return launch_fwd<bf16_t, 9>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-  }
-  if (dtype == RPO_F16) {
-    if (N <= 224) return launch_fwd<f16_t, 7>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-    return launch_fwd<f16_t, 9>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-  }
-  if (N <= 224) return launch_fwd<float, 7>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-  return launch_fwd<float, 9>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
+  RPO_BY_TYPE_NT(launch_fwd, q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
 }
 
 extern "C" int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
@@ -2313,16 +1881,7 @@ extern "C" int rpo_attn_prompt_fwd(const void* q_rows, int64_t ldq, const void* 
       reinterpret_cast<uintptr_t>(out) % (4 * esz) || (ldo * esz) % (4 * esz) ||
       reinterpret_cast<uintptr_t>(first_image) % 4) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == RPO_BF16) {
-    if (N <= 224) return launch_prompt_fwd<bf16_t, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
-    return launch_prompt_fwd<bf16_t, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
-  }
-  if (dtype == RPO_F16) {
-    if (N <= 224) return launch_prompt_fwd<f16_t, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
-    return launch_prompt_fwd<f16_t, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
-  }
-  if (N <= 224) return launch_prompt_fwd<float, 7>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
-  return launch_prompt_fwd<float, 9>(q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
+  RPO_BY_TYPE_NT(launch_prompt_fwd, q_rows, ldq, k, v, ldkv, out, ldo, B, H, N, Kp, sets, first_image, scale, s);
 }
 
 extern "C" int rpo_attn_prompt_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
@@ -2337,18 +1896,7 @@ extern "C" int rpo_attn_prompt_bwd(const void* q_rows, int64_t ldq, const void* 
       !ok_ld(ldda, esz) || reinterpret_cast<uintptr_t>(dq) % (4 * esz) || (lddq * esz) % (4 * esz) ||
       reinterpret_cast<uintptr_t>(first_image) % 4) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define RPO_PB(T_, NT_) return launch_prompt_bwd<T_, NT_>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, sets, first_image, scale, s)
-  if (dtype == RPO_BF16) {
-    if (N <= 224) RPO_PB(bf16_t, 7);
-    RPO_PB(bf16_t, 9);
-  }
-  if (dtype == RPO_F16) {
-    if (N <= 224) RPO_PB(f16_t, 7);
-    RPO_PB(f16_t, 9);
-  }
-  if (N <= 224) RPO_PB(float, 7);
-  RPO_PB(float, 9);
-#undef RPO_PB
+  RPO_BY_TYPE_NT(launch_prompt_bwd, q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, sets, first_image, scale, s);
 }
 
 extern "C" int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void* k, const void* v,
@@ -2367,16 +1915,7 @@ extern "C" int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void
     if (dtype == RPO_F16) return launch_bwd_long<f16_t>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
     return launch_bwd_long<float>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
   }
-  if (dtype == RPO_BF16) {
-    if (N <= 224) return launch_bwd<bf16_t, 7>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-    return launch_bwd<bf16_t, 9>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-  }
-  if (dtype == RPO_F16) {
-    if (N <= 224) return launch_bwd<f16_t, 7>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-    return launch_bwd<f16_t, 9>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-  }
-  if (N <= 224) return launch_bwd<float, 7>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-  return launch_bwd<float, 9>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
+  RPO_BY_TYPE_NT(launch_bwd, q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
 }
 
 extern "C" int rpo_attn_readonly_bwd_proj(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,

@@ -744,8 +744,7 @@ def test_attn_readonly_fwd(mode, B, H, N, Kp):
 @pytest.mark.parametrize("B,H,N,Kp", [(32, 12, 197, 24), (24, 12, 197, 4), (20, 16, 257, 24)])
 def test_attn_readonly_fwd_split_units_change_nothing(mode, B, H, N, Kp):
     """A query's arithmetic does not depend on which workgroup computes it or on how many units a launch holds: the
-    whole-batch launch must give the bits of image-by-image launches.  (Also the check of the -DRPO_ATTN_SPLIT build,
-    which splits some units' query tiles over two workgroups when there are more units than CUs: attn_image.hip.)"""
+    whole-batch launch must give the bits of image-by-image launches."""
     o = ops()
     d = 64 * H
     qkv = _img_rows(B, N, Kp, d, 21)
