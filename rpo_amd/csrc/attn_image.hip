@@ -729,6 +729,59 @@ __global__ __launch_bounds__(512, 4) void attn_fwd16_kernel(const T* __restrict_
 // statistics, then takes the key tiles t = wave, wave+4, ... for dP / U / W; partial U, W, delta are
 // combined through LDS (the staging area is dead by then).
 //
+// bwd_pass2_tile is the pass-2 step of one key tile, written once for attn_bwd_body (all keys staged at once) and
+// attn_bwd_long_kernel (the keys in chunks), both storage forms and both forms of `da`.  The pass-1 tile step, the rowstat
+// merge, the partial combine with the dq store and the dS . K contraction of attn_prompt_bwd_kernel are stated per kernel on
+// purpose: as helpers they change the register allocation (profiles/image_attn_bwd_refactor_ab.txt).
+//
+// Pass 2, one key tile: P from the merged (m, 1 / l), dP = da . V^T, delta += sum P o dP, and the contractions
+// u (U) += (P o dP) . K, w (W) += P . K.  `da` is this lane's query row of d(attention output): a RowFrag, or
+// -- folded d out-proj -- the four fragments in C/D order that the prologue of attn_bwd_body leaves (tile_times_cdfrag).
+template <typename T, int NT, typename DA>
+__device__ __forceinline__ void bwd_pass2_tile(const char* ks, const char* vs, int t, int N, const RowFrag<T>& qf,
+                                               const DA& da, float m, float inv, float scale, f32x16_t (&u)[2], f32x16_t (&w)[2],
+                                               float& delta, const bf16x8_t& i0, const bf16x8_t& i1, int l31, int half) {
+  f32x16_t pt = tile_times_frag<T>(ks, t, qf, l31, half);
+  (void)mask_and_max(pt, t, N, half);
+  (void)exp_tile<T>(pt, m, scale);
+  f32x16_t dp;
+  if constexpr (std::is_same<DA, RowFrag<T>>::value) dp = tile_times_frag<T>(vs, t, da, l31, half);
+  else dp = tile_times_cdfrag<T>(vs, t, da, l31, half);
+  if constexpr (sizeof(T) == 2) {
+    const char* krow = ks + (32 * t + l31) * 144 + half * 16;
+    bf16x8_t krows[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) krows[kk] = *reinterpret_cast<const bf16x8_t*>(krow + kk * 32);
+    float pw[16], pp[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      pp[r] = pt[r] * inv;
+      pw[r] = dp[r] * pp[r];                       // P * dP  (P = 0 on padded keys)
+      delta += pw[r];
+    }
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+      bf16x8_t ktf[2];
+      transpose_tile<T>(krows, dt, i0, i1, ktf);   // K^T fragments of this key tile, in registers
+#pragma unroll
+      for (int g2 = 0; g2 < 2; ++g2) {
+        u[dt] = mfma16<T>(ktf[g2], pack8<T>(pw + 8 * g2), u[dt]);
+        w[dt] = mfma16<T>(ktf[g2], pack8<T>(pp + 8 * g2), w[dt]);
+      }
+    }
+  } else {
+    f32x16_t pn;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      pn[r] = pt[r] * inv;
+      dp[r] *= pn[r];
+      delta += dp[r];
+    }
+    contract_keys<T, NT>(ks, t, dp, u, l31, half);
+    contract_keys<T, NT>(ks, t, pn, w, l31, half);
+  }
+}
+
 // NCW > 0 (16-bit storage): the d out-proj GEMM is folded in.  `da` then is d(out-proj output) [B*Kp, d] (d = 256 * NCW)
 // and `wo` the transposed out-proj weight [d (in), d (out)]: the workgroup first forms its head's slice
 // da_h = da . W_out[:, 64h .. 64h+63] -- 32 x 64 x d on the matrix cores, the four waves taking d / 4 of the contraction
@@ -843,11 +896,7 @@ __device__ __forceinline__ void attn_bwd_body(char* smem, const int bid, const i
         }
       };
       // younger than chunk 0: chunk 1 (8) + xb / qf
-#ifdef RPO_FUSED_SAFE
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
       asm volatile("s_waitcnt vmcnt(%0)" :: "n"((NCW == 4 ? 24 : 8) + NXQ) : "memory");
-#endif
       mfma_chunk(0, 0);
       if constexpr (NCW == 3) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // slot 0 has been read
@@ -861,30 +910,16 @@ __device__ __forceinline__ void attn_bwd_body(char* smem, const int bid, const i
         ka[it] = *reinterpret_cast<const uint4*>(kb + (int64_t)key * ldkv + c * 8);
         va[it] = *reinterpret_cast<const uint4*>(vb + (int64_t)key * ldkv + c * 8);
       }
-#ifdef RPO_FUSED_SAFE
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
       asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NXQ + (NCW == 3 ? 8 : NCW == 4 ? 16 : 0) + 2 * ITERS) : "memory");   // younger than chunk 1
-#endif
       mfma_chunk(1, 1);
       if constexpr (NCW == 4) {
-#ifdef RPO_FUSED_SAFE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NXQ + 8 + 2 * ITERS) : "memory");                    // younger than chunk 2
-#endif
         mfma_chunk(2, 2);
-#ifndef RPO_FUSED_SAFE
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NXQ + 2 * ITERS) : "memory");                        // younger than chunk 3
-#endif
         mfma_chunk(3, 3);
       }
       if constexpr (NCW == 3) {
-#ifdef RPO_FUSED_SAFE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * ITERS) : "memory");                            // younger than chunk 2
-#endif
         mfma_chunk(2, 0);
       }
       RPO_STAMP(11);
@@ -965,45 +1000,8 @@ __device__ __forceinline__ void attn_bwd_body(char* smem, const int bid, const i
     float delta = 0.f;
 #pragma unroll 1
     for (int t = wave; t < NT; t += 4) {           // wave-uniform trip count
-      f32x16_t pt = tile_times_frag<T>(ks, t, qf, l31v, half);
-      (void)mask_and_max(pt, t, N, half);
-      (void)exp_tile<T>(pt, m, scale);
-      f32x16_t dp;
-      if constexpr (NCW > 0) dp = tile_times_cdfrag<T>(vs, t, dcd, l31v, half);
-      else dp = tile_times_frag<T>(vs, t, df, l31v, half);
-      if constexpr (sizeof(T) == 2) {
-        const char* krow = ks + (32 * t + l31v) * 144 + half * 16;
-        bf16x8_t krows[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) krows[kk] = *reinterpret_cast<const bf16x8_t*>(krow + kk * 32);
-        float pw[16], pp[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          pp[r] = pt[r] * inv;
-          pw[r] = dp[r] * pp[r];                   // P * dP  (P = 0 on padded keys)
-          delta += pw[r];
-        }
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          bf16x8_t ktf[2];
-          transpose_tile<T>(krows, dt, i0, i1, ktf);  // K^T fragments of this key tile, in registers
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) {
-            u[dt] = mfma16<T>(ktf[g2], pack8<T>(pw + 8 * g2), u[dt]);
-            w[dt] = mfma16<T>(ktf[g2], pack8<T>(pp + 8 * g2), w[dt]);
-          }
-        }
-      } else {
-        f32x16_t pn;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          pn[r] = pt[r] * inv;
-          dp[r] *= pn[r];
-          delta += dp[r];
-        }
-        contract_keys<T, NT>(ks, t, dp, u, l31v, half);
-        contract_keys<T, NT>(ks, t, pn, w, l31v, half);
-      }
+      if constexpr (NCW > 0) bwd_pass2_tile<T, NT>(ks, vs, t, N, qf, dcd, m, inv, scale, u, w, delta, i0, i1, l31v, half);
+      else bwd_pass2_tile<T, NT>(ks, vs, t, N, qf, df, m, inv, scale, u, w, delta, i0, i1, l31v, half);
     }
     delta += __shfl_xor(delta, 32, 64);
     RPO_STAMP(15);
@@ -1162,8 +1160,9 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_long_kernel(const T* __restri
 // Backward for the prompt rows (dq; K and V are frozen).  One workgroup per (image, head, 32-query tile), the four waves
 // sharing the tile as in attn_bwd_body: wave w owns key tiles w, w + 4 of EVERY chunk.  Pass 1 walks the chunks (K only)
 // for the row maximum and sum -- per wave online over its tiles, merged once through LDS; pass 2 walks them again (K and V)
-// and accumulates U, W and delta in registers across the chunks; the four waves' partials are summed through LDS in a
-// fixed order.  No atomics: two calls give the same bits.
+// and accumulates U, W and delta in registers across the chunks (for each chunk: stage, barrier, bwd_pass2_tile per key tile
+// -- the step attn_bwd_body runs); the four waves' partials are summed through LDS in a fixed order.  No atomics: two calls
+// give the same bits.
 template <typename T>
 __global__ __launch_bounds__(256, 2) void attn_bwd_long_kernel(const T* qr, int64_t ldq, const T* k, const T* v,
                                                             int64_t ldkv, const T* da, int64_t ldda, T* dq,
@@ -1249,43 +1248,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_long_kernel(const T* qr, int6
     asm volatile("" : "+v"(l31v));
 #pragma unroll 1
     for (int t = wave; 32 * t < Nc; t += 4) {      // wave-uniform trip count
-      f32x16_t pt = tile_times_frag<T>(ks, t, qf, l31v, half);
-      (void)mask_and_max(pt, t, Nc, half);
-      (void)exp_tile<T>(pt, m, scale);
-      f32x16_t dp = tile_times_frag<T>(vs, t, df, l31v, half);
-      if constexpr (sizeof(T) == 2) {
-        const char* krow = ks + (32 * t + l31v) * 144 + half * 16;
-        bf16x8_t krows[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) krows[kk] = *reinterpret_cast<const bf16x8_t*>(krow + kk * 32);
-        float pw[16], pp[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          pp[r] = pt[r] * inv;
-          pw[r] = dp[r] * pp[r];                   // P * dP  (P = 0 on padded keys)
-          delta += pw[r];
-        }
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          bf16x8_t ktf[2];
-          transpose_tile<T>(krows, dt, i0, i1, ktf);
-#pragma unroll
-          for (int g2 = 0; g2 < 2; ++g2) {
-            u[dt] = mfma16<T>(ktf[g2], pack8<T>(pw + 8 * g2), u[dt]);
-            w[dt] = mfma16<T>(ktf[g2], pack8<T>(pp + 8 * g2), w[dt]);
-          }
-        }
-      } else {
-        f32x16_t pn;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          pn[r] = pt[r] * inv;
-          dp[r] *= pn[r];
-          delta += dp[r];
-        }
-        contract_keys<T, NT>(ks, t, dp, u, l31v, half);
-        contract_keys<T, NT>(ks, t, pn, w, l31v, half);
-      }
+      bwd_pass2_tile<T, NT>(ks, vs, t, Nc, qf, df, m, inv, scale, u, w, delta, i0, i1, l31v, half);
     }
   }
   delta += __shfl_xor(delta, 32, 64);
@@ -1576,61 +1539,34 @@ int launch_prompt_bwd(const void* q, int64_t ldq, const void* k, const void* v, 
   return rpo_launch_status();
 }
 
-template <typename T, int NT>
-int launch_bwd(const void* qr, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* da,
-               int64_t ldda, void* dq, int64_t lddq, int B, int H, int N, int Kp, float scale, hipStream_t s) {
-  static rpo_lds_mask_t lds_ok{0};
-  auto kern = attn_bwd_kernel<T, NT>;
-  constexpr int bytes = AL<T, NT>::BWD_BYTES + 2048;
-  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(256), bytes, s, static_cast<const T*>(qr), ldq,
-                     static_cast<const T*>(k), static_cast<const T*>(v), ldkv, static_cast<const T*>(da), ldda,
-                     static_cast<T*>(dq), lddq, B, H, N, Kp, scale, static_cast<const T*>(nullptr), (int64_t)0,
-                     static_cast<const int32_t*>(nullptr), 0, 1);
-  return rpo_launch_status();
-}
-
-constexpr int bwd_proj_lds(int bwd_bytes, int ncw) {
-  const int slots = 4 * (ncw == 4 ? 4 : 2) * 8192;
+// dynamic LDS of attn_bwd_kernel<T, NT, NCW>: the staging area / the partials -- NCW > 0: or the 4 waves x 2 (NCW = 4: 4)
+// weight slots of 8 KiB that the folded out-proj lands in first -- and 2 KB of row statistics behind them
+constexpr int bwd_lds(int bwd_bytes, int ncw) {
+  const int slots = ncw == 0 ? 0 : 4 * (ncw == 4 ? 4 : 2) * 8192;
   return (bwd_bytes > slots ? bwd_bytes : slots) + 2048;
-}
-
-template <typename T, int NT, int NCW>
-int launch_bwd_proj(const void* qr, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* dx,
-                    int64_t lddx, const void* wo, int64_t ldwo, void* dq, int64_t lddq, int B, int H, int N, int Kp,
-                    float scale, hipStream_t s) {
-  static rpo_lds_mask_t lds_ok{0};
-  auto kern = attn_bwd_kernel<T, NT, NCW>;
-  constexpr int bytes = bwd_proj_lds(AL<T, NT>::BWD_BYTES, NCW);   // 4 waves x 2 (4) weight slots of 8 KiB + row statistics
-  if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
-  const int nqt = (Kp + 31) / 32;                  // one workgroup per (image, head, 32-query tile)
-  hipLaunchKernelGGL(kern, dim3(B * H * nqt), dim3(256), bytes, s, static_cast<const T*>(qr), ldq,
-                     static_cast<const T*>(k), static_cast<const T*>(v), ldkv, static_cast<const T*>(dx), lddx,
-                     static_cast<T*>(dq), lddq, B, H, N, Kp, scale, static_cast<const T*>(wo), ldwo,
-                     static_cast<const int32_t*>(nullptr), 0, nqt);
-  return rpo_launch_status();
 }
 
 bool ok_ld(int64_t ld, int esz) { return (ld * esz) % 16 == 0; }
 
-// one problem with per-group key counts (the text tower)
-template <typename T, int NT, int NCW>
-int launch_bwd_proj_var(const AttnBwdProblem& a, hipStream_t s) {
+// The one launcher of attn_bwd_kernel: nqt_wg workgroups per (group, head), one per 32-query tile (NCW > 0 with Kp > 32),
+// or one that walks the query tiles itself (nqt_wg = 1).  a.key_len: per-group key counts (the text tower).
+template <typename T, int NT, int NCW = 0>
+int launch_bwd(const AttnBwdProblem& a, int nqt_wg, hipStream_t s) {
   static rpo_lds_mask_t lds_ok{0};
   auto kern = attn_bwd_kernel<T, NT, NCW>;
-  constexpr int bytes = bwd_proj_lds(AL<T, NT>::BWD_BYTES, NCW);
+  constexpr int bytes = bwd_lds(AL<T, NT>::BWD_BYTES, NCW);
   if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
-  hipLaunchKernelGGL(kern, dim3(a.B * a.H), dim3(256), bytes, s, static_cast<const T*>(a.qr), a.ldq,
+  hipLaunchKernelGGL(kern, dim3(a.B * a.H * nqt_wg), dim3(256), bytes, s, static_cast<const T*>(a.qr), a.ldq,
                      static_cast<const T*>(a.k), static_cast<const T*>(a.v), a.ldkv, static_cast<const T*>(a.da), a.ldda,
                      static_cast<T*>(a.dq), a.lddq, a.B, a.H, a.N, a.Kp, a.scale, static_cast<const T*>(a.wo), a.ldwo,
-                     a.key_len, a.key_stride, 1);
+                     a.key_len, a.key_stride, nqt_wg);
   return rpo_launch_status();
 }
 template <typename T, int NT0, int NCW0, int NT1, int NCW1>
 int launch_bwd_proj_pair(const AttnBwdProblem& a, const AttnBwdProblem& b, hipStream_t s) {
   static rpo_lds_mask_t lds_ok{0};
   auto kern = attn_bwd_pair_kernel<T, NT0, NCW0, NT1, NCW1>;
-  constexpr int b0 = bwd_proj_lds(AL<T, NT0>::BWD_BYTES, NCW0), b1 = bwd_proj_lds(AL<T, NT1>::BWD_BYTES, NCW1);
+  constexpr int b0 = bwd_lds(AL<T, NT0>::BWD_BYTES, NCW0), b1 = bwd_lds(AL<T, NT1>::BWD_BYTES, NCW1);
   constexpr int bytes = b0 > b1 ? b0 : b1;
   if (int rc = rpo_allow_lds(reinterpret_cast<const void*>(kern), bytes, &lds_ok)) return rc;
   const int items0 = a.B * a.H, items1 = b.B * b.H, slots = 2 * rpo_cu_count();
@@ -1666,7 +1602,7 @@ int dispatch_bwd_proj_args(const rpo_attn_bwd_args* a0, const rpo_attn_bwd_args*
   if (!bwd_proj_geometry(*a0, &nt0, &ncw0) || (a1 && !bwd_proj_geometry(*a1, &nt1, &ncw1))) return RPO_E_SHAPE;
   const AttnBwdProblem p0 = bwd_problem(*a0);
   if (a1 == nullptr) {
-#define RPO_BV(NT_, NCW_) if (nt0 == NT_ && ncw0 == NCW_) return launch_bwd_proj_var<T, NT_, NCW_>(p0, s)
+#define RPO_BV(NT_, NCW_) if (nt0 == NT_ && ncw0 == NCW_) return launch_bwd<T, NT_, NCW_>(p0, 1, s)
     RPO_BV(3, 2); RPO_BV(3, 3); RPO_BV(7, 2); RPO_BV(7, 3); RPO_BV(9, 2); RPO_BV(9, 3);
 #undef RPO_BV
     return RPO_E_SHAPE;
@@ -1680,10 +1616,9 @@ int dispatch_bwd_proj_args(const rpo_attn_bwd_args* a0, const rpo_attn_bwd_args*
   return RPO_E_SHAPE;
 }
 template <typename T>
-int dispatch_bwd_proj(int ncw, bool big, const void* qr, int64_t ldq, const void* k, const void* v, int64_t ldkv,
-                      const void* dx, int64_t lddx, const void* wo, int64_t ldwo, void* dq, int64_t lddq, int B, int H,
-                      int N, int Kp, float scale, hipStream_t s) {
-#define RPO_BP(NT_, NCW_) return launch_bwd_proj<T, NT_, NCW_>(qr, ldq, k, v, ldkv, dx, lddx, wo, ldwo, dq, lddq, B, H, N, Kp, scale, s)
+int dispatch_bwd_proj(int ncw, bool big, const AttnBwdProblem& a, hipStream_t s) {
+  const int nqt = (a.Kp + 31) / 32;                // one workgroup per (image, head, 32-query tile)
+#define RPO_BP(NT_, NCW_) return launch_bwd<T, NT_, NCW_>(a, nqt, s)
   if (ncw == 2) { if (big) RPO_BP(9, 2); RPO_BP(7, 2); }
   if (ncw == 3) { if (big) RPO_BP(9, 3); RPO_BP(7, 3); }
   if (ncw == 4) { if (big) RPO_BP(9, 4); RPO_BP(7, 4); }
@@ -1840,6 +1775,13 @@ int rpo_text_attn_wave(int bwd, const void* q, int64_t ldq, const void* kc, cons
     if (dtype == RPO_F16) return N <= 224 ? LAUNCH<f16_t, 7>(__VA_ARGS__) : LAUNCH<f16_t, 9>(__VA_ARGS__);     \
     return N <= 224 ? LAUNCH<float, 7>(__VA_ARGS__) : LAUNCH<float, 9>(__VA_ARGS__);                           \
   } while (0)
+// LAUNCH<T>(...) by storage type (the long kernels: the keys in chunks)
+#define RPO_BY_TYPE(LAUNCH, ...)                                     \
+  do {                                                               \
+    if (dtype == RPO_BF16) return LAUNCH<bf16_t>(__VA_ARGS__);       \
+    if (dtype == RPO_F16) return LAUNCH<f16_t>(__VA_ARGS__);         \
+    return LAUNCH<float>(__VA_ARGS__);                               \
+  } while (0)
 
 extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const void* v, int64_t ld, void* out,
                                           int64_t ldo, int dtype, int B, int H, int N, int Kp, float scale,
@@ -1862,11 +1804,7 @@ extern "C" int rpo_attn_readonly_fwd_rows(const void* q, const void* k, const vo
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !ok_ld(ld, esz) ||
       reinterpret_cast<uintptr_t>(out) % (4 * esz) || (ldo * esz) % (4 * esz)) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (N > 288) {                                   // the keys in chunks (attn_fwd_long_kernel)
-    if (dtype == RPO_BF16) return launch_fwd_long<bf16_t>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-    if (dtype == RPO_F16) return launch_fwd_long<f16_t>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-    return launch_fwd_long<float>(q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
-  }
+  if (N > 288) RPO_BY_TYPE(launch_fwd_long, q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);   // the keys in chunks
   RPO_BY_TYPE_NT(launch_fwd, q, k, v, ld, out, ldo, B, H, N, Kp, scale, q_first, s);
 }
 
@@ -1910,12 +1848,10 @@ extern "C" int rpo_attn_readonly_bwd(const void* q_rows, int64_t ldq, const void
       !ok_ld(ldkv, esz) || !ok_ld(ldda, esz) || reinterpret_cast<uintptr_t>(dq) % (4 * esz) ||
       (lddq * esz) % (4 * esz)) return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (N > 288) {                                   // the keys in chunks (attn_bwd_long_kernel)
-    if (dtype == RPO_BF16) return launch_bwd_long<bf16_t>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-    if (dtype == RPO_F16) return launch_bwd_long<f16_t>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-    return launch_bwd_long<float>(q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
-  }
-  RPO_BY_TYPE_NT(launch_bwd, q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
+  if (N > 288)                                     // the keys in chunks (attn_bwd_long_kernel)
+    RPO_BY_TYPE(launch_bwd_long, q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, s);
+  const AttnBwdProblem a{q_rows, ldq, k, v, ldkv, da, ldda, dq, lddq, B, H, N, Kp, scale, nullptr, 0, nullptr, 0};
+  RPO_BY_TYPE_NT(launch_bwd, a, 1, s);             // one workgroup per (image, head) walks the (Kp + 31) / 32 query tiles
 }
 
 extern "C" int rpo_attn_readonly_bwd_proj(const void* q_rows, int64_t ldq, const void* k, const void* v, int64_t ldkv,
@@ -1931,9 +1867,9 @@ extern "C" int rpo_attn_readonly_bwd_proj(const void* q_rows, int64_t ldq, const
       !ok_ld(ldkv, 2) || !ok_ld(lddx, 2) || !ok_ld(ldw, 2) || reinterpret_cast<uintptr_t>(dq) % 8 || (lddq * 2) % 8)
     return RPO_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == RPO_BF16)
-    return dispatch_bwd_proj<bf16_t>(d / 256, N > 224, q_rows, ldq, k, v, ldkv, dx, lddx, w_out_t, ldw, dq, lddq, B, H, N, Kp, scale, s);
-  return dispatch_bwd_proj<f16_t>(d / 256, N > 224, q_rows, ldq, k, v, ldkv, dx, lddx, w_out_t, ldw, dq, lddq, B, H, N, Kp, scale, s);
+  const AttnBwdProblem a{q_rows, ldq, k, v, ldkv, dx, lddx, dq, lddq, B, H, N, Kp, scale, w_out_t, ldw, nullptr, 0};
+  if (dtype == RPO_BF16) return dispatch_bwd_proj<bf16_t>(d / 256, N > 224, a, s);
+  return dispatch_bwd_proj<f16_t>(d / 256, N > 224, a, s);
 }
 
 // rpo_attn_readonly_bwd_proj for one or two problems in ONE launch, each with optional per-group key counts

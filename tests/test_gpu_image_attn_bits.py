@@ -4,7 +4,9 @@ one case on seeded CPU-generated inputs (test_gpu_attn_long.make_qkv: queries x 
 rows; every buffer inside a NaN-filled allocation; outputs pre-filled with NaN, so a hash also pins which rows are NOT
 written) and returns sha256 hashes.  tools/capture_attn_bits.py --image recorded them with a library built from the parent
 commit on the device type the suite runs on (tests/golden/image_attn_parent_bits.json), twice in separate processes with
-equal results.  Every later tree is held to those hashes: kernel selection by shape and every output bit stay as they were."""
+equal results.  Every later tree is held to those hashes: kernel selection by shape and every output bit stay as they were.
+The backward cases beyond the first six were added, and recorded the same way, with the library of the commit before the
+backward kernels were put on one pass-2 tile step and one launcher; the 77 earlier hashes came out unchanged."""
 import functools
 import hashlib
 import json
@@ -39,9 +41,21 @@ FWD_LONG = [(289, 1, 2, 24, 0), (513, 1, 1, 1, 0), (577, 1, 2, 24, 577)]
 # over 3 cached images ([3 N, 2 d] K | V), 0 = device scalar 0
 PFWD = [(197, 2, 2, 24, 1, None), (197, 2, 2, 5, 3, "dev1"), (257, 1, 2, 33, 2, 0), (5, 1, 1, 1, 1, None),
         (224, 1, 2, 24, 12, None)]                                  # the last: Q = 288, nine query tiles
-PBWD = [(197, 2, 2, 5, 3, "dev1"), (257, 1, 2, 33, 2, 0)]
-BWD = [(197, 2, 3, 24), (257, 1, 2, 33), (289, 1, 2, 24)]           # the last: the long backward
-BWD_PROJ = [(197, 2, 12, 24)]                                       # bf16
+# the added three: smallest problem; Q = 288 (a wave takes a second query tile and reloads qf / df); NT = 9 full
+PBWD = [(197, 2, 2, 5, 3, "dev1"), (257, 1, 2, 33, 2, 0), (5, 1, 1, 1, 1, None), (224, 1, 2, 24, 12, None),
+        (288, 1, 1, 1, 1, None)]
+# rpo_attn_readonly_bwd, (N, B, H, Kp).  Base shape, NT = 9, the long backward; then: only tile 0 holds keys (waves 1 to 3
+# keep (-inf, 0)); one full tile plus a one-key tile; four full tiles, one per wave; NT = 7 full with two query tiles through
+# the in-kernel loop; four query tiles (the entry point's maximum); NT = 9 smallest and full; long kernel: two full chunks
+# and two workgroups per head, one key in the last chunk (three waves skip it), ViT-L/14 at 336 px, the limit
+BWD = [(197, 2, 3, 24), (257, 1, 2, 33), (289, 1, 2, 24),
+       (5, 1, 1, 1), (33, 1, 2, 7), (128, 1, 2, 32), (224, 1, 2, 40), (50, 1, 1, 128), (225, 1, 2, 24), (288, 1, 2, 1),
+       (512, 1, 1, 33), (513, 1, 1, 1), (577, 1, 2, 24), (1025, 1, 1, 1)]
+# rpo_attn_readonly_bwd_proj, bf16 and f16 (the folded out-proj, NCW = H / 4).  Base shape (NCW = 3); NCW = 2 and 4 at
+# NT = 7; NT = 9 with each NCW (the middle one has Kp > 32: two workgroups per (image, head)); the Kp limit; only tile 0
+# holds keys; NT = 9 full
+BWD_PROJ = [(197, 2, 12, 24), (197, 1, 8, 24), (197, 1, 16, 24), (257, 1, 8, 5), (257, 1, 12, 33), (257, 1, 16, 24),
+            (224, 1, 12, 64), (5, 1, 12, 1), (288, 1, 8, 32)]
 
 
 def _id(kind, mode, p):
@@ -56,7 +70,7 @@ for _m in MODES:
     SPECS.update({_id("bwd", _m, p): ("bwd", _m, p) for p in BWD})
 for _m in HALF:
     SPECS.update({_id("fwd2phase", _m, p): ("fwd2phase", _m, p) for p in FWD_2PHASE})
-SPECS.update({_id("bwdproj", "bf16", p): ("bwdproj", "bf16", p) for p in BWD_PROJ})
+    SPECS.update({_id("bwdproj", _m, p): ("bwdproj", _m, p) for p in BWD_PROJ})
 CASES = list(SPECS)
 
 
