@@ -649,6 +649,45 @@ int rpo_features_classify(const float* feat, int64_t ldf, const float* cls, cons
                           float scale, int norm_feat, int norm_cls, int64_t* counts, int32_t* cmat, int32_t* pred,
                           float* logits_out, int n, int C, int e, int S, void* stream);
 
+/* (ABI 8 addition) CLIP's linear-probe protocol on CACHED image features: S L2-regularised multinomial logistic
+ * regressions (the members of a regularisation / few-shot sweep) over one feature matrix.  rpo_amd/csrc/logreg.hip,
+ * rpo_amd/logreg.py.  Member s < S, row i < n, class c < C:
+ *   z_sic = a_i <feat[i,:], W_s[c,:]> + b_s[c],   a_i = 1 / ||feat[i,:]|| if norm_feat else 1
+ *           (rpo_features_classify's logits at scale = 1, norm_cls = 0, a_i formed by the same sum)
+ *   J_s   = (1 / omega[s]) sum_i w_si CE(softmax(z_si.), label[i]) + (l2[s] / 2) ||W_s||_F^2
+ * rpo_logreg_loss_grad_sets: loss[s] = J_s and grads row s = dJ_s / d[W_s | b_s] at params row s.  feat [n, e] fp32 with
+ * leading dimension ldf >= e; label int64 [n]; weight [S, n] fp32 >= 0 or NULL (all ones); omega float64 [S]: Omega_s =
+ * sum_i w_si AS THE CALLER SUMMED IT (a_i comes from the call's own first launch, Omega_s from the caller); l2 fp32 [S];
+ * params and grads [S, set_stride] fp32, row s = [W_s (C x e) | b_s (C)], floats past C e + C of a row never addressed;
+ * done int32 [S] or NULL: a member with done[s] != 0 is skipped (its grads row and loss[s] stay as they are); fit_bias = 0
+ * writes a zero bias gradient; loss fp32 [S]; workspace fp32, rpo_logreg_workspace_floats(n, C, e, S) elements, no
+ * initialisation needed; all device memory.  A row whose label lies outside [0, C) behaves as weight 0 and reads nothing
+ * out of bounds.  Three launches: logits -> softmax -> residuals r_sic = (w_si / omega[s])(p_sic - [c == label[i]]) into
+ * the workspace; G_s = R_s^T (a . feat) over row chunks of 1024; the chunk partials in ascending order + l2[s] W_s.  All
+ * products on the fp32 matrix pipe in a fixed k order, the softmax sums and the weight in double rounded once, every
+ * cross-workgroup sum through fp32 partials added in ascending order by a later launch, no float atomics: the bits repeat
+ * from run to run, and member s has the bits of an S = 1 call on its slices.
+ * rpo_logreg_step_sets: one iteration of accelerated gradient descent with a fixed step and gradient restart on rows
+ * x, y, grads of [S, set_stride] (`count` <= set_stride valid floats each), grads = dJ_s at y:
+ *   x+ = y - grads / L[s];  t <- 1 if <grads, x+ - x> > 0;  t+ = (1 + sqrt(1 + 4 t^2)) / 2;  y+ = x+ + ((t - 1) / t+)(x+ - x)
+ * t, L, tol, grad_inf fp32 [S]; done, iters int32 [S].  grad_inf[s] = ||grads_s||_inf (NaN if any entry is); where it is
+ * <= tol[s], done[s] = 1 and nothing else of the member is written -- the point kept is y, the one whose gradient was
+ * tested -- else x, y, t are updated and iters[s] += 1.  A member with done[s] != 0 on entry is not touched.  One
+ * workgroup per member, the restart product (double) and the max-norm reduced in a fixed order.
+ * Limits: e a multiple of 32 up to 1024, 1 <= C <= 1024, 1 <= S <= 1024, n >= 1, S ceil(n / 1024) <= 65535, set_stride >= C e + C, else
+ * RPO_E_SHAPE;
+ * a null pointer (weight and done excepted) or a non-positive stride: RPO_E_BADARG; feat, params, grads, workspace not
+ * 16-byte aligned, set_stride % 4 != 0 or omega not 8-byte aligned: RPO_E_ALIGN; nothing is launched on an error.
+ * rpo_logreg_workspace_floats: 0 for a non-positive argument.  The calls only enqueue on `stream`, allocate nothing and
+ * are capturable in a HIP graph. */
+int64_t rpo_logreg_workspace_floats(int n, int C, int e, int S);
+int rpo_logreg_loss_grad_sets(const float* feat, int64_t ldf, const int64_t* label, const float* weight, const double* omega,
+                              const float* l2, const float* params, int64_t set_stride, const int32_t* done, int norm_feat,
+                              int fit_bias, float* grads, float* loss, int n, int C, int e, int S, float* workspace,
+                              void* stream);
+int rpo_logreg_step_sets(float* x, float* y, const float* grads, int64_t set_stride, int64_t count, float* t, const float* L,
+                         const float* tol, int32_t* done, int32_t* iters, float* grad_inf, int S, void* stream);
+
 /* ---- CLIP ResNet image tower (clip/model.py:10-152, rpo_amd/csrc/conv.hip) ------------------------------------------
  * Activations are NHWC in the act dtype (`dtype`: RPO_F32 / RPO_BF16 / RPO_F16): row m = (b, y, x), channels contiguous.
  * Eval-mode BatchNorm is folded into weight and bias by the caller.  Every sum runs in a fixed order (same bits per call).

@@ -196,6 +196,10 @@ SIGNATURES = {
     "rpo_eval_accumulate": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rpo_features_classify": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                       c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rpo_logreg_workspace_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "rpo_logreg_loss_grad_sets": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
+                                          c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "rpo_logreg_step_sets": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rpo_conv2d_plan": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "rpo_conv2d_nhwc": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                 c_vp]),

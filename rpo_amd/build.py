@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librpo_hip.so")
 SOURCES = ["gemm.hip", "gemm_ws.hip", "norm.hip", "attn_image.hip", "attn_text.hip", "misc.hip", "preprocess.hip", "lp_head.hip", "conv.hip",
-           "eval.hip", "jpeg.hip", "ensemble.hip", "optim.hip", "classify.hip", "cocoop_sets.hip", "coop_sets.hip"]
+           "eval.hip", "jpeg.hip", "ensemble.hip", "optim.hip", "classify.hip", "cocoop_sets.hip", "coop_sets.hip", "logreg.hip"]
 # The measured-slower experiments of rounds 3 / 4 (include/rpo_amd_experimental.h: paired launches, the fused MLP launch,
 # the persistent backward chain) are compiled only into a SECOND library, with -DRPO_EXPERIMENTAL, that nothing loads
 # unless RPO_EXPERIMENTAL=1 is set (rpo_amd/_lib.py): `python -m rpo_amd.build --experimental`

@@ -749,6 +749,53 @@ def features_classify(feat, cls, bias, label, scale: float, norm_feat: bool, nor
     return counts
 
 
+def logreg_workspace_floats(n: int, Cc: int, e: int, S: int) -> int:
+    return int(_lib.load().rpo_logreg_workspace_floats(n, Cc, e, S))
+
+
+def logreg_loss_grad_sets(feat, label, weight, omega, l2, params, n_cls: int, grads, loss, ws, norm_feat: bool = False,
+                          fit_bias: bool = True, done=None):
+    """Loss and gradient of S multinomial logistic regressions on cached features (include/rpo_amd.h
+    rpo_logreg_loss_grad_sets): feat [n, e] fp32 (row stride >= e), label int64 [n], weight [S, n] fp32 or None, omega
+    float64 [S], l2 fp32 [S], params / grads [S, stride] fp32 with row s = [W_s (n_cls x e) | b_s (n_cls)], loss fp32 [S],
+    done int32 [S] or None.  Enqueue only."""
+    n, e = feat.shape
+    S = params.shape[0]
+    assert feat.dtype == torch.float32 and feat.stride(1) == 1
+    assert label.dtype == torch.int64 and label.numel() == n and label.is_contiguous()
+    assert weight is None or (weight.dtype == torch.float32 and weight.shape == (S, n) and weight.is_contiguous())
+    assert omega.dtype == torch.float64 and omega.numel() == S and omega.is_contiguous()
+    assert l2.dtype == torch.float32 and l2.numel() == S and l2.is_contiguous()
+    assert params.dtype == torch.float32 and params.dim() == 2 and params.stride(1) == 1
+    assert grads.dtype == torch.float32 and grads.shape == params.shape and grads.stride() == params.stride()
+    assert loss.dtype == torch.float32 and loss.numel() == S and loss.is_contiguous()
+    assert done is None or (done.dtype == torch.int32 and done.numel() == S and done.is_contiguous())
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= logreg_workspace_floats(n, n_cls, e, S)
+    check(_lib.load().rpo_logreg_loss_grad_sets(feat.data_ptr(), feat.stride(0), label.data_ptr(), _p(weight),
+                                                omega.data_ptr(), l2.data_ptr(), params.data_ptr(), params.stride(0),
+                                                _p(done), int(bool(norm_feat)), int(bool(fit_bias)), grads.data_ptr(),
+                                                loss.data_ptr(), n, int(n_cls), e, S, ws.data_ptr(), _stream()),
+          "rpo_logreg_loss_grad_sets")
+    return loss
+
+
+def logreg_step_sets(x, y, grads, count: int, t, L, tol, done, iters, grad_inf):
+    """One accelerated-gradient iteration with gradient restart per member (include/rpo_amd.h rpo_logreg_step_sets) on
+    rows x, y, grads [S, stride] fp32 (`count` valid floats each); t, L, tol, grad_inf fp32 [S], done, iters int32 [S].
+    Enqueue only."""
+    S = x.shape[0]
+    for a in (x, y, grads):
+        assert a.dtype == torch.float32 and a.dim() == 2 and a.shape[0] == S and a.stride() == x.stride() and a.stride(1) == 1
+    for a in (t, L, tol, grad_inf):
+        assert a.dtype == torch.float32 and a.numel() == S and a.is_contiguous()
+    for a in (done, iters):
+        assert a.dtype == torch.int32 and a.numel() == S and a.is_contiguous()
+    check(_lib.load().rpo_logreg_step_sets(x.data_ptr(), y.data_ptr(), grads.data_ptr(), x.stride(0), int(count),
+                                           t.data_ptr(), L.data_ptr(), tol.data_ptr(), done.data_ptr(), iters.data_ptr(),
+                                           grad_inf.data_ptr(), S, _stream()),
+          "rpo_logreg_step_sets")
+
+
 def metanet_fwd(img_f, w1, b1, w2, b2, f_norm, hidden, bias):
     B, e = img_f.shape
     h, d = w1.shape[0], w2.shape[0]
